@@ -23,6 +23,11 @@ per GPU, rowbowt_amd/launch.py), relays rank 0's JSON line and exits non-zero if
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` the ranks already exist and --gpus
 must equal WORLD_SIZE.  `n_gpus` in the line is the size of the RCCL group that was actually formed.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the --steps steps and prints the headline line (with --dump-outputs DIR it first
+writes what the last timed step computed).  Everything else -- the count-only, capped, u32, markers and two-stream legs,
+the instrumented passes behind the per-kernel and roofline blocks, the full-size properties, the oracle parity sample,
+the CPU baselines, the space_speed rebuilds, the pangenome_shape child and --replicas -- runs with --full only.
 """
 import argparse
 import ctypes as C
@@ -56,8 +61,14 @@ def parse():
     ap.add_argument("--launch-check", action="store_true",
                     help="start the ranks as --gpus asks, have each print the environment it was given as one JSON line and exit "
                          "(no GPU is touched: the launcher's own test)")
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (count-only, capped, u32, markers, instrumented per-kernel / roofline passes, "
+                         "full-size properties, oracle parity, CPU baselines, space_speed, pangenome_shape); the per-leg options below apply under it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last step computed on rank 0 as DIR/<name>.npy (float64): ranges, toeholds, "
+                         "location offsets and locations of a fixed seeded sample of the reads, and sums over the whole batch")
     ap.add_argument("--reads", type=int, default=10_000_000, help="reads per GPU per step")
     ap.add_argument("--read-len", type=int, default=100)
     ap.add_argument("--L", type=int, default=40_000_000, help="base sequence length")
@@ -71,7 +82,7 @@ def parse():
     ap.add_argument("--markers", action="store_true",
                     help="also run BASELINE.json configs[4] (rb_align -m: find_range + markers_at on a synthetic marker array "
                          "over the same index) and rb_markers' seeding kernel, checked against the oracle on --check-reads reads; "
-                         "on by default on one GPU (about 25 s), off under torch.distributed.run unless asked for")
+                         "with --full on by default on one GPU (about 25 s), off under torch.distributed.run unless asked for")
     ap.add_argument("--no-markers", action="store_true", help="skip the markers leg")
     ap.add_argument("--two-stream", action="store_true",
                     help="also time the K steps as successive batches on two HIP streams (informational; off by default so "
@@ -209,6 +220,43 @@ def cpu_budget():
     return max(1, n)
 
 
+DUMP_SAMPLE_READS = 65536        # reads of the batch whose outputs --dump-outputs writes
+DUMP_MAX_LOCATIONS = 6_000_000   # at most this many of their locations (48 MB as float64): the files stay under 64 MB
+
+
+def dump_outputs(torch, out_dir, seed, d_lo, d_hi, d_k, d_loc_off, d_locs):
+    """What the last timed step handed its caller, as float64 .npy files in out_dir: for a fixed sample of the batch's reads
+    (seeded, sorted) their index, range [lo, hi], toehold, offset and number of locations, and their locations in order
+    (capped at DUMP_MAX_LOCATIONS); batch_sums = sums of lo, hi, toehold and locations over the WHOLE batch (int64 on the
+    device, wrapping) and its number of locations.  Every value below 2^53 is exact in float64; u64 sentinels (2^64-1) read
+    as 1.8446744073709552e19."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    N = d_lo.numel()
+    total = int(d_loc_off[-1].item())
+    S = min(N, DUMP_SAMPLE_READS)
+    idx = np.sort(np.random.default_rng(seed).choice(N, size=S, replace=False))
+    d_idx = torch.from_numpy(idx).to(d_lo.device)
+    start = d_loc_off[d_idx]
+    occ = d_loc_off[d_idx + 1] - start
+    n_loc = min(int(occ.sum().item()), DUMP_MAX_LOCATIONS)
+    # the gather index of the sample's locations: each read's start offset, repeated once per location, plus 0, 1, ...
+    first = torch.cumsum(occ, 0) - occ
+    gidx = torch.repeat_interleave(start - first, occ)[:n_loc] + torch.arange(n_loc, device=d_lo.device)
+    locs = d_locs[:total][gidx]
+    sums = torch.stack([d_lo.sum(), d_hi.sum(), d_k.sum(), d_locs[:total].sum()])
+
+    def f64(t):   # the ABI's u64 values (held in int64 tensors) as float64
+        return t.cpu().numpy().view(np.uint64).astype(np.float64)
+
+    arrays = {"read_index": idx.astype(np.float64), "lo": f64(d_lo[d_idx]), "hi": f64(d_hi[d_idx]), "toehold": f64(d_k[d_idx]),
+              "loc_off": f64(start), "occ": f64(occ), "locs": f64(locs),
+              "batch_sums": np.append(f64(sums), np.float64(total))}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    assert sum(a.nbytes for a in arrays.values()) < 64 << 20
+
+
 def run():
     args = parse()
     launch = load_launch()
@@ -224,10 +272,15 @@ def run():
     if args.launch_check:
         launch.echo_rank()
         return
-    # the markers leg (BASELINE.json configs[4]) rides along on one GPU unless switched off
-    args.markers = (args.markers or (world == 1 and "RANK" not in os.environ)) and not args.no_markers
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.replicas and world > 1:
         raise SystemExit("--replicas (one process, G replicas) and --gpus N (one process per GPU) are two ways to use several GPUs: pick one")
+    legs = [name for name, on in (("--markers", args.markers), ("--two-stream", args.two_stream), ("--replicas", args.replicas)) if on]
+    if legs and not args.full:
+        raise SystemExit(f"{', '.join(legs)}: legs of --full (a plain run times the headline only)")
+    # the markers leg (BASELINE.json configs[4]) rides along a --full run on one GPU unless switched off
+    args.markers = args.full and (args.markers or (world == 1 and "RANK" not in os.environ)) and not args.no_markers
     if args.replicas and not args.no_space_speed:
         # (the space_speed block rebuilds the replica in other forms; the --replicas leg replicates and scales the HEADLINE replica)
         args.no_space_speed = True
@@ -430,15 +483,99 @@ def run():
         ev[s][3].record(stream)
 
     rb.counters_reset()
-    clocks = DeviceClocks(torch, dev)
-    clocks.start()
+    clocks = DeviceClocks(torch, dev) if args.full else None
+    if clocks:
+        clocks.start()
     el = timed(step_ev, K, events=True)
-    device_state = clocks.stop()
+    device_state = clocks.stop() if clocks else None
     counters = rb.counters().astype(np.int64)
     ms_toe = float(np.mean([ev[s][0].elapsed_time(ev[s][1]) for s in range(K)]))
     ms_plan = float(np.mean([ev[s][1].elapsed_time(ev[s][2]) for s in range(K)]))
     ms_order = float(np.mean([ev[s][2].elapsed_time(ev[s][4]) for s in range(K)]))
     ms_fill = float(np.mean([ev[s][4].elapsed_time(ev[s][3]) for s in range(K)]))
+    if args.dump_outputs and rank == 0:
+        stage(f"write the last timed step's outputs to {args.dump_outputs}")
+        dump_outputs(torch, args.dump_outputs, args.seed, d_lo, d_hi, d_k, d_loc_off, d_locs)
+
+    def reduce_over_ranks(times):
+        """max over ranks of the elapsed times, counters summed over RCCL, and the per-rank diagnostics a post-mortem of a
+        multi-GPU run needs (outside the timed region; an all_gather of eight doubles)"""
+        stage("all_reduce(MAX) of the times, all_reduce(SUM) of the counters")
+        t_el = torch.tensor(times, dtype=torch.float64, device=cdev)
+        if use_dist:
+            dist.all_reduce(t_el, op=dist.ReduceOp.MAX)
+        g_counters = shard.reduce_counters(counters, device=cdev)  # the only collective of the run: 4 x u64 over RCCL
+        stage("all_gather of the per-rank diagnostics")
+        mine = torch.tensor([rank, local_rank, t_load, t_wait, times[0] / K * 1e3, ms_toe, ms_fill, float(ix.hbm_bytes)], dtype=torch.float64, device=cdev)
+        if use_dist:
+            rows_t = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(rows_t, mine)
+        else:
+            rows_t = [mine]
+        per_rank = [{"rank": int(r_[0].item()), "device": int(r_[1].item()), "load_s": float(r_[2].item()), "wait_for_rank0_s": float(r_[3].item()),
+                     "ms_per_step": float(r_[4].item()), "k2_ms": float(r_[5].item()), "k3_ms": float(r_[6].item()), "hbm_bytes": int(r_[7].item())} for r_ in rows_t]
+        return [float(x) for x in t_el.tolist()], g_counters, per_rank
+
+    def headline(el_max, g_counters, per_rank):
+        """the fields of the line that every run prints: the headline figure and what it was measured on"""
+        li = rb.layout_info() if int(ix.rank_layout) == 2 else None
+        return {
+            "metric": f"reads/s ({args.read_len} bp, count+locate)",
+            "value": N * world * K / el_max,
+            "unit": "reads/s",
+            "n_gpus": world,
+            "steps": K,
+            "warmup": args.warmup,
+            "ms_per_step": el_max / K * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u64" if ix.pos_bytes == 8 else "u32/u64",
+            "data": "synthetic",
+            "full": args.full,
+            "config": {
+                "workload": f"count+locate (find_range_w_toehold + locs_at, max_hits={'2^64-1' if max_hits == MAXU else max_hits}) on a "
+                            f"synthetic chr22-scale pangenome r-index, {N} x {m} bp reads per GPU per step (BASELINE.json configs[2])",
+                "index": {"L": args.L, "H": args.H, "n": int(inp["n"]), "r": int(inp["r"]), "site_rate": args.site_rate,
+                          "hbm_bytes": int(ix.hbm_bytes), "pos_bytes": int(ix.pos_bytes), "seed": args.seed,
+                          "slot_bytes": int(ix.slot_bytes) or 16, "symbols_per_gather": int(ix.kmer_steps), "symbols_per_gather_requested": int(ix.kmer_steps_requested),
+                          "hbm_free_at_load": int(ix.hbm_free_at_load), "hbm_budget": int(ix.hbm_budget),
+                          "rank_layout": "runs" if int(ix.rank_layout) == 2 else "slots",
+                          "hbm_budget_source": ("bench.py --hbm-budget-gb -1: three quarters of the free HBM" if args.hbm_budget_gb < 0
+                                                else "the library's default (a quarter of the free HBM)" if args.hbm_budget_gb == 0 else f"--hbm-budget-gb {args.hbm_budget_gb}"), "ftab_k": int(ix.ftab_k), "depth_runs": [int(x) for x in ix.depth_runs],
+                          # what the load's budget rules decided (rbg_layout_info; tools/layout_rules_table.py makes DESIGN.md 2c's table from these)
+                          **({"layout_info": {"budget_raised": int(li.budget_raised), "depths_kept": [d_ + 1 for d_ in range(8) if int(li.depth_mask_kept) >> d_ & 1],
+                                              "depths_with_records": [d_ + 1 for d_ in range(8) if int(li.rec_bytes[d_])], "depths_dropped_budget": int(li.depths_dropped_budget),
+                                              "entries": [int(x) for x in li.entries], "rec_bytes": [int(x) for x in li.rec_bytes], "rec_overflow": [int(x) for x in li.rec_overflow],
+                                              "phi_slots": int(li.phi_slots), "phi_slot_bytes": int(li.phi_slot_bytes), "phi_entries": int(li.phi_entries),
+                                              "rank_directories": int(li.rank_directories), "phi_directory": int(li.phi_directory)}} if li else {})},
+                "reads_per_gpu": N, "read_len": m, "substituted_fraction": 0.1,
+                "documents": info["H"] if args.docs == "on" else 0,
+                "chain_order": ("by locus: offset inside the document, then document"
+                                if args.docs == "on" and os.environ.get("RBG_LOCATE_ORDER") != "abs" and (info["H"] >= 128 or os.environ.get("RBG_LOCATE_ORDER") == "locus")
+                                else "by absolute text position"),
+                "parallelism": f"index replicated x{world}, reads sharded, no data-path collective",
+                **({"rehearsal": f"NOT A MEASUREMENT: {world} ranks on {torch.cuda.device_count()} GPU(s), collectives over gloo (--rehearse-ranks)"}
+                   if args.rehearse_ranks else {}),
+            },
+            # the kernels of the timed steps (HIP events around each launch, mean over the steps; this rank)
+            "kernels_ms": {"k_find_range<toehold>": ms_toe, "locate_plan(k_occ+scan)": ms_plan, "locate_order(radix sort of toeholds)": ms_order,
+                           "k_locate_fill": ms_fill},
+            "counters": {"reads": g_counters[0], "matched": g_counters[1], "sum_occ": g_counters[2], "sum_locs": g_counters[3],
+                         "reduced_over": (f"{'gloo (rehearsal)' if args.rehearse_ranks else 'RCCL'} all_reduce over {world} rank(s)" if use_dist else "single GPU (no process group)")},
+            # the multi-GPU run's post-mortem block: who ran where, how long each rank loaded / waited / stepped, what the one-per-node cache cost
+            "per_rank": per_rank,
+            "rccl_ranks_seen": len({r_["rank"] for r_ in per_rank}),
+            "collective_backend": ("gloo (rehearsal)" if args.rehearse_ranks else "nccl (RCCL)") if use_dist else None,
+            "cache_write_s": t_cache_write if cache_path else None, "cache_bytes": cache_bytes if cache_path else None,
+            "cache_path": cache_path, "suffix_array_s": t_sa,
+        }
+
+    if not args.full:
+        (el,), g_counters, per_rank = reduce_over_ranks([el])
+        out = headline(el, g_counters, per_rank) if rank == 0 else None
+        rb.close()
+        return out, dict(rank=rank, world=world, use_dist=use_dist, args=args, dev=dev)
 
     # ---- count-only (configs[1]) ---------------------------------------------------------------
     stage("count-only steps")
@@ -727,33 +864,13 @@ def run():
     rb.counters_reset()
 
     # max over ranks, counters over RCCL
-    stage("all_reduce(MAX) of the times, all_reduce(SUM) of the counters")
-    el_own = el
-    t_el = torch.tensor([el, el_count, el_pipe], dtype=torch.float64, device=cdev)
-    if use_dist:
-        dist.all_reduce(t_el, op=dist.ReduceOp.MAX)
-    el, el_count, el_pipe = float(t_el[0].item()), float(t_el[1].item()), float(t_el[2].item())
-    g_counters = shard.reduce_counters(counters, device=cdev)  # the only collective of the run: 4 x u64 over RCCL
-    # what a post-mortem of a multi-GPU run needs, per rank (outside the timed region; an all_gather of eight doubles)
-    stage("all_gather of the per-rank diagnostics")
-    mine = torch.tensor([rank, local_rank, t_load, t_wait, el_own / K * 1e3, ms_toe, ms_fill, float(ix.hbm_bytes)], dtype=torch.float64, device=cdev)
-    if use_dist:
-        rows_t = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(rows_t, mine)
-    else:
-        rows_t = [mine]
-    per_rank = [{"rank": int(r_[0].item()), "device": int(r_[1].item()), "load_s": float(r_[2].item()), "wait_for_rank0_s": float(r_[3].item()),
-                 "ms_per_step": float(r_[4].item()), "k2_ms": float(r_[5].item()), "k3_ms": float(r_[6].item()), "hbm_bytes": int(r_[7].item())} for r_ in rows_t]
-    ranks_seen = len({r_["rank"] for r_ in per_rank})
+    (el, el_count, el_pipe), g_counters, per_rank = reduce_over_ranks([el, el_count, el_pipe])
 
     out = None
     if rank == 0:
-        total_reads = N * world * K
-        value = total_reads / el
         # ---- bytes of the algorithm AS RUN, from the instrumented pass: what each kernel has to
         # move for the steps it actually executed, at the sizes it is stored in HBM -- no sector padding, no re-reads.
         P = int(ix.pos_bytes)
-        slot_b = int(ix.slot_bytes) or 16
         ftab_entry = 16 if P == 4 else 32
 
         runs_layout = int(ix.rank_layout) == 2
@@ -846,43 +963,7 @@ def run():
         elif dom == "k_find_range<toehold>":
             gathers = st_toe["slots"] + st_toe["dense"] + st_toe["ftab"] + 2 * st_toe["resamples"] + 4 * st_toe["searched_ranks"]
         out = {
-            "metric": f"reads/s ({args.read_len} bp, count+locate)",
-            "value": value,
-            "unit": "reads/s",
-            "n_gpus": world,
-            "steps": K,
-            "warmup": args.warmup,
-            "ms_per_step": el / K * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u64" if ix.pos_bytes == 8 else "u32/u64",
-            "data": "synthetic",
-            "config": {
-                "workload": f"count+locate (find_range_w_toehold + locs_at, max_hits={'2^64-1' if max_hits == MAXU else max_hits}) on a "
-                            f"synthetic chr22-scale pangenome r-index, {N} x {m} bp reads per GPU per step (BASELINE.json configs[2])",
-                "index": {"L": args.L, "H": args.H, "n": int(inp["n"]), "r": int(inp["r"]), "site_rate": args.site_rate,
-                          "hbm_bytes": int(ix.hbm_bytes), "pos_bytes": int(ix.pos_bytes), "seed": args.seed,
-                          "slot_bytes": slot_b, "symbols_per_gather": int(ix.kmer_steps), "symbols_per_gather_requested": int(ix.kmer_steps_requested),
-                          "hbm_free_at_load": int(ix.hbm_free_at_load), "hbm_budget": int(ix.hbm_budget),
-                          "rank_layout": "runs" if int(ix.rank_layout) == 2 else "slots",
-                          "hbm_budget_source": ("bench.py --hbm-budget-gb -1: three quarters of the free HBM" if args.hbm_budget_gb < 0
-                                                else "the library's default (a quarter of the free HBM)" if args.hbm_budget_gb == 0 else f"--hbm-budget-gb {args.hbm_budget_gb}"), "ftab_k": int(ix.ftab_k), "depth_runs": [int(x) for x in ix.depth_runs],
-                          # what the load's budget rules decided (rbg_layout_info; tools/layout_rules_table.py makes DESIGN.md 2c's table from these)
-                          **({"layout_info": {"budget_raised": int(li.budget_raised), "depths_kept": [d_ + 1 for d_ in range(8) if int(li.depth_mask_kept) >> d_ & 1],
-                                              "depths_with_records": [d_ + 1 for d_ in range(8) if int(li.rec_bytes[d_])], "depths_dropped_budget": int(li.depths_dropped_budget),
-                                              "entries": [int(x) for x in li.entries], "rec_bytes": [int(x) for x in li.rec_bytes], "rec_overflow": [int(x) for x in li.rec_overflow],
-                                              "phi_slots": int(li.phi_slots), "phi_slot_bytes": int(li.phi_slot_bytes), "phi_entries": int(li.phi_entries),
-                                              "rank_directories": int(li.rank_directories), "phi_directory": int(li.phi_directory)}} if li else {})},
-                "reads_per_gpu": N, "read_len": m, "substituted_fraction": 0.1,
-                "documents": info["H"] if args.docs == "on" else 0,
-                "chain_order": ("by locus: offset inside the document, then document"
-                                if args.docs == "on" and os.environ.get("RBG_LOCATE_ORDER") != "abs" and (info["H"] >= 128 or os.environ.get("RBG_LOCATE_ORDER") == "locus")
-                                else "by absolute text position"),
-                "parallelism": f"index replicated x{world}, reads sharded, no data-path collective",
-                **({"rehearsal": f"NOT A MEASUREMENT: {world} ranks on {torch.cuda.device_count()} GPU(s), collectives over gloo (--rehearse-ranks)"}
-                   if args.rehearse_ranks else {}),
-            },
+            **headline(el, g_counters, per_rank),
             "two_stream_pipeline": ({"value": N * world * K / el_pipe, "unit": "reads/s", "ms_per_step": el_pipe / K * 1e3,
                                      "identical_output": same_out,
                                      "workload": "the same K count+locate steps issued as successive batches on two HIP streams"}
@@ -894,15 +975,7 @@ def run():
                                   "workload": "count+locate with max_hits = 1 (diagnostic: search cost without the phi walks)"},
             "count_only": {"value": N * world * K / el_count, "unit": "reads/s", "ms_per_step": el_count / K * 1e3,
                            "workload": "BASELINE.json configs[1]: find_range only"},
-            "counters": {"reads": g_counters[0], "matched": g_counters[1], "sum_occ": g_counters[2], "sum_locs": g_counters[3],
-                         "reduced_over": (f"{'gloo (rehearsal)' if args.rehearse_ranks else 'RCCL'} all_reduce over {world} rank(s)" if use_dist else "single GPU (no process group)")},
-            # the multi-GPU run's post-mortem block: who ran where, how long each rank loaded / waited / stepped, what the one-per-node cache cost
             "device_state_during_the_timed_steps": device_state,
-            "per_rank": per_rank,
-            "rccl_ranks_seen": ranks_seen,
-            "collective_backend": ("gloo (rehearsal)" if args.rehearse_ranks else "nccl (RCCL)") if use_dist else None,
-            "cache_write_s": t_cache_write if cache_path else None, "cache_bytes": cache_bytes if cache_path else None,
-            "cache_path": cache_path, "suffix_array_s": t_sa,
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": ach / HBM_PEAK_GBS, "traffic": traffic,
                          "alg_bytes_per_launch": kernels[dom]["alg_bytes"], "kernel_ms": kernels[dom]["ms"],
@@ -1529,7 +1602,7 @@ def main():
     out, c = res
     args, rank, world, use_dist = c["args"], c["rank"], c["world"], c["use_dist"]
     default_workload = (args.L, args.H, args.reads, args.read_len, args.site_rate) == (40_000_000, 50, 10_000_000, 100, 0.01)
-    if rank == 0 and world == 1 and not use_dist and default_workload and not args.no_pangenome_shape and not args.replicas:
+    if args.full and rank == 0 and world == 1 and not use_dist and default_workload and not args.no_pangenome_shape and not args.replicas:
         stage("pangenome_shape block (child process)")
         out["pangenome_shape"] = pangenome_shape_block(args, c["dev"])
         if "error" in out["pangenome_shape"]:

@@ -299,7 +299,7 @@ def test_bench_two_ranks_rehearsal():
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse-ranks", "--L", "1500000", "--H", "8", "--reads", "150000",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--rehearse-ranks", "--L", "1500000", "--H", "8", "--reads", "150000",
                         "--steps", "2", "--warmup", "1", "--no-space-speed", "--no-markers", "--no-cpu-baseline", "--check-reads", "2000",
                         "--property-reads", "20000"], capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -325,7 +325,7 @@ def test_full_size_properties_and_parity_sample():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
                         "--check-reads", "5000", "--property-reads", "300000", "--markers", "--no-pangenome-shape"],   # (that block is the test below)
                        capture_output=True, timeout=1500, cwd=root)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
@@ -426,7 +426,7 @@ def test_bench_replicas_flag_three_replicas_on_device_0():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--replicas", "3", "--replica-devices", "0,0,0", "--L", "1500000", "--H", "8", "--reads", "150000",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--replicas", "3", "--replica-devices", "0,0,0", "--L", "1500000", "--H", "8", "--reads", "150000",
                         "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-space-speed", "--no-markers", "--check-reads", "2000", "--property-reads", "20000"],
                        capture_output=True, timeout=600, cwd=root)
     assert p.returncode == 0, p.stderr.decode()[-3000:]

@@ -13,7 +13,7 @@ trap 'cp $keep rowbowt_amd/librbg.so; rm -f $keep' EXIT
 one() {  # tag, library, extra bench args
   tag=$1; lib=$2; shift 2
   cp rowbowt_amd/librbg_$lib.so rowbowt_amd/librbg.so || return 1
-  python bench.py --steps 10 --warmup 2 --no-pangenome-shape --no-cpu-baseline --no-space-speed --no-markers --check-reads 2000 --property-reads 0 "$@" > $out/$tag.json 2> $out/$tag.log || { echo "FAILED $tag"; tail -5 $out/$tag.log; return 1; }
+  python bench.py --full --steps 10 --warmup 2 --no-pangenome-shape --no-cpu-baseline --no-space-speed --no-markers --check-reads 2000 --property-reads 0 "$@" > $out/$tag.json 2> $out/$tag.log || { echo "FAILED $tag"; tail -5 $out/$tag.log; return 1; }
   python - <<P
 import json
 d=json.loads(open("$out/$tag.json").read().strip().splitlines()[-1])

@@ -4,8 +4,8 @@
 # usage: tools/lib_ab.sh cur flat cond ...   (writes gpurun_out/ab_<v>_{4,8}.json)
 set -u
 mkdir -p gpurun_out
-# RBG_AB_ARGS: other bench.py arguments (default: the run-indexed layout), e.g. "--no-space-speed --no-markers --no-cpu-baseline" for the slot tables
-A=${RBG_AB_ARGS:-"--layout runs --no-space-speed --no-markers --no-cpu-baseline --steps 3 --warmup 1"}
+# RBG_AB_ARGS: other bench.py arguments (default: the run-indexed layout), e.g. "--full --no-space-speed --no-markers --no-cpu-baseline" for the slot tables
+A=${RBG_AB_ARGS:-"--full --layout runs --no-space-speed --no-markers --no-cpu-baseline --steps 3 --warmup 1"}
 # RBG_AB_WIDTHS: position widths to run ("4 8" by default; "4" halves the time of an A/B that needs many samples)
 W=${RBG_AB_WIDTHS:-"4 8"}
 for v in "$@"; do

@@ -13,7 +13,7 @@ for v in "$@"; do
   for grp in "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_SALU" \
              "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCP_TCC_READ_REQ_sum" "SQ_BUSY_CYCLES SQ_WAVES SQ_INST_CYCLES_VMEM SQ_INSTS_LDS GRBM_GUI_ACTIVE"; do
     i=$((i+1))
-    timeout -k 10 300 rocprofv3 --pmc $grp --kernel-include-regex "k_find_range_runs" --output-format csv -d $out/$v/p$i -- python3 bench.py --layout runs --pos-bytes 8 --steps 2 --warmup 0 --no-cpu-baseline --check-reads 0 --no-space-speed --no-markers --property-reads 0 > $out/$v.p$i.json 2> $out/$v.p$i.err || echo "$v pass $i ($grp) failed"
+    timeout -k 10 300 rocprofv3 --pmc $grp --kernel-include-regex "k_find_range_runs" --output-format csv -d $out/$v/p$i -- python3 bench.py --full --layout runs --pos-bytes 8 --steps 2 --warmup 0 --no-cpu-baseline --check-reads 0 --no-space-speed --no-markers --property-reads 0 > $out/$v.p$i.json 2> $out/$v.p$i.err || echo "$v pass $i ($grp) failed"
   done
 done
 {

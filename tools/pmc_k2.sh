@@ -14,7 +14,7 @@ for grp in "FETCH_SIZE" "WRITE_SIZE TCC_REQ_sum" "TCC_HIT_sum TCC_MISS_sum" \
            "SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_VMEM SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" \
            "TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum"; do
   i=$((i+1))
-  timeout -k 10 200 rocprofv3 --pmc $grp --kernel-include-regex "k_find_range_runs" --output-format csv -d $out/p$i -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-space-speed --no-markers --check-reads 0 --property-reads 0 > $out/p$i.json 2> $out/p$i.err || echo "pass $i ($grp) failed"
+  timeout -k 10 200 rocprofv3 --pmc $grp --kernel-include-regex "k_find_range_runs" --output-format csv -d $out/p$i -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-space-speed --no-markers --check-reads 0 --property-reads 0 > $out/p$i.json 2> $out/p$i.err || echo "pass $i ($grp) failed"
 done
 {
   echo "# rocprofv3 --pmc (separate passes, tools/pmc_k2.sh $*) of bench.py's search kernels on the bench index, 10 M x 100 bp per launch; FETCH_SIZE / WRITE_SIZE in KiB; SQ_*_CYCLES, SQ_WAIT_*, SQ_ACTIVE_INST_* in quad-cycles summed over waves or SIMDs, SQ_BUSY_CYCLES over the 32 shader engines"

@@ -6,11 +6,11 @@ cd "$(dirname "$0")/.."
 for per in 2.5 4 6; do
   for pb in 4 8; do
     echo "## bench.py --layout runs --pos-bytes $pb RBG_RUN_REC_PER=$per"
-    RBG_RUN_REC_PER=$per timeout -k 10 300 python3 bench.py --layout runs --pos-bytes $pb --steps 10 --warmup 2 --no-cpu-baseline --no-space-speed --check-reads 5000 --property-reads 100000 2> gpurun_out/rps.err | python3 -c "
+    RBG_RUN_REC_PER=$per timeout -k 10 300 python3 bench.py --full --layout runs --pos-bytes $pb --steps 10 --warmup 2 --no-cpu-baseline --no-space-speed --check-reads 5000 --property-reads 100000 2> "${TMPDIR:-/tmp}/rps.err" | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.readline()); m = d['markers']
 print(json.dumps({'value': round(d['value'] / 1e9, 4), 'hbm_GB': round(d['config']['index']['hbm_bytes'] / 1e9, 2), 'ms': {k.split('(')[0]: round(v['ms'], 3) for k, v in d['kernels'].items()},
-                  'greedy_ms': round(m['greedy_seed']['ms_per_step'], 2), 'seeds_two_walk_ms': round(m['marker_seeds']['two_walks_ms_per_step'], 2), 'seeds_logged_ms': round(m['marker_seeds']['logged']['ms_per_step'], 2)}))" || { echo FAILED; tail -5 gpurun_out/rps.err; exit 1; }
+                  'greedy_ms': round(m['greedy_seed']['ms_per_step'], 2), 'seeds_two_walk_ms': round(m['marker_seeds']['two_walks_ms_per_step'], 2), 'seeds_logged_ms': round(m['marker_seeds']['logged']['ms_per_step'], 2)}))" || { echo FAILED; tail -5 "${TMPDIR:-/tmp}/rps.err"; exit 1; }
   done
 done
 for per in 2.5 5; do

@@ -7,8 +7,8 @@ tag=${1:-r06}
 out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-timeout 900 python3 bench.py --steps 20 --warmup 3 > $out/bench.json 2> $out/bench.err
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --check-reads 0 --property-reads 0 --no-space-speed --no-pangenome-shape > $out/stats_bench.json 2> $out/stats.err
+timeout 900 python3 bench.py --full --steps 20 --warmup 3 > $out/bench.json 2> $out/bench.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --check-reads 0 --property-reads 0 --no-space-speed --no-pangenome-shape > $out/stats_bench.json 2> $out/stats.err
 python3 tools/summarize_rocprof.py $out/stats/*/*_kernel_stats.csv $out/stats/*/*_kernel_trace.csv > $out/kernel_stats.md 2>&1
 rm -rf $out/stats
 timeout 400 python3 tools/host_api_rate.py 2>&1 | grep -v amdgpu.ids > $out/host_api.txt

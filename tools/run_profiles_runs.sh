@@ -17,9 +17,9 @@ python3 tools/make_pmc_traffic.py --merge-runs profiles/pmc_traffic.json $out/ru
 mv $out/run_indexed_pmc.txt $out/run_indexed_pmc_pos4.txt
 cp profiles/pmc_traffic.json $out/pmc_traffic_with_runs.json
 for pb in 4 8; do
-  timeout -k 10 600 python3 bench.py --layout runs --pos-bytes $pb --no-cpu-baseline --no-space-speed > $out/bench_runs_pos$pb.json 2> $out/bench_runs_pos$pb.err || { echo "bench --layout runs --pos-bytes $pb failed"; tail -5 $out/bench_runs_pos$pb.err; exit 1; }
+  timeout -k 10 600 python3 bench.py --full --layout runs --pos-bytes $pb --no-cpu-baseline --no-space-speed > $out/bench_runs_pos$pb.json 2> $out/bench_runs_pos$pb.err || { echo "bench --layout runs --pos-bytes $pb failed"; tail -5 $out/bench_runs_pos$pb.err; exit 1; }
 done
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_runs -- python3 bench.py --layout runs --pos-bytes 8 --steps 3 --warmup 1 --no-cpu-baseline --check-reads 0 --property-reads 0 --no-space-speed > $out/stats_runs_bench.json 2> $out/stats_runs.err || { echo "rocprofv3 stats failed"; exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_runs -- python3 bench.py --full --layout runs --pos-bytes 8 --steps 3 --warmup 1 --no-cpu-baseline --check-reads 0 --property-reads 0 --no-space-speed > $out/stats_runs_bench.json 2> $out/stats_runs.err || { echo "rocprofv3 stats failed"; exit 1; }
 python3 tools/summarize_rocprof.py $out/stats_runs/*/*_kernel_stats.csv $out/stats_runs/*/*_kernel_trace.csv > $out/kernel_stats_run_indexed.md 2>&1
 rm -rf $out/stats_runs
 bash tools/fmt_ab.sh > $out/fmt_ab.txt 2>&1 || { echo "fmt_ab failed"; tail -5 $out/fmt_ab.txt; exit 1; }

@@ -3,7 +3,7 @@ out=gpurun_out/r06uni
 mkdir -p $out
 for rep in 1 2 3; do
 for v in 0 1; do
-  RBG_RUN_UNIFORM=$v python bench.py --steps 10 --warmup 2 --no-pangenome-shape --no-cpu-baseline --no-space-speed --no-markers --check-reads 2000 --property-reads 0 > $out/b_$v.json 2> $out/b_$v.log || { echo "FAILED $v"; tail -5 $out/b_$v.log; exit 1; }
+  RBG_RUN_UNIFORM=$v python bench.py --full --steps 10 --warmup 2 --no-pangenome-shape --no-cpu-baseline --no-space-speed --no-markers --check-reads 2000 --property-reads 0 > $out/b_$v.json 2> $out/b_$v.log || { echo "FAILED $v"; tail -5 $out/b_$v.log; exit 1; }
   python - <<P
 import json
 d=json.loads(open("$out/b_$v.json").read().strip().splitlines()[-1])
