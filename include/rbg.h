@@ -190,6 +190,21 @@ typedef struct rbg_layout_info_t {
 } rbg_layout_info_t;
 int rbg_layout_info(const rbg_index *, rbg_layout_info_t *out, uint64_t out_bytes);
 
+/* The jump table (RBG_OPT_JUMP_K): for every K-mer that OCCURS in the text, the search state after it, so that a read of
+ * at least K symbols replaces its first K backward-search steps by one probe.  The reference's ftab (RowBowt::search_ftab,
+ * rowbowt.hpp:121-131, :726-758) made sparse; result-neutral.  Built last at load (rbg_load, rbg_load_cache, rbg_build_*), from what
+ * the HBM budget leaves after every other decision -- the layout is the one the load makes without it -- and copied by rbg_replicate;
+ * not stored in a cache file.  4-byte positions and the run-indexed layout only.  All zero when no table was built (RBG_VERBOSE=1
+ * says why). */
+typedef struct rbg_jump_info_t {
+    uint64_t k;          /* symbols per key */
+    uint64_t keys;       /* K-mers in the table */
+    uint64_t bytes;      /* HBM of the table (counted in rbg_info().hbm_bytes) */
+    uint64_t buckets;    /* 64-byte buckets of two slots */
+    double build_ms;     /* wall time of enumerating, searching and inserting the keys */
+} rbg_jump_info_t;
+int rbg_jump_info(const rbg_index *, rbg_jump_info_t *out);
+
 /* RowBowt::get_f(), rowbowt.hpp:719 / build_f :770-778: 256 entries. */
 int rbg_get_f(const rbg_index *, uint64_t f_out[256]);
 /* ToeholdSA::get_last_run_sample(), toehold_sa.hpp:97-99 */
@@ -549,7 +564,7 @@ int rbg_sample_reads_pangenome_dev(const uint8_t *d_base, const uint64_t *d_site
  * RBG_RUN_FILL_SHIFT / RBG_PHI_SUPER_SHIFT lower the filler distance / super-count spacing of 8-byte positions so that tests
  * meet both on small indexes;  RBG_HOST_THREADS, RBG_HOST_CHUNK_READS, RBG_HOST_DIRECT_OUT=0, RBG_HOST_COMBINE=0,
  * RBG_HOST_TRACE=1|2 tune / trace the host-pointer pipeline;  RBG_LAYOUT=auto|slots|runs|prefer-slots, RBG_RUN_DEPTHS,
- * RBG_KMER_STEPS, RBG_HBM_BUDGET_MB, RBG_FTAB_K, RBG_RUN_PHI, RBG_RUN_REC give the options of the same names their initial values (for
+ * RBG_KMER_STEPS, RBG_HBM_BUDGET_MB, RBG_FTAB_K, RBG_JUMP_K, RBG_RUN_PHI, RBG_RUN_REC give the options of the same names their initial values (for
  * the command-line tools, which keep the reference's flags; rbg_set_default_option overrides them);  RBG_H2D_STAGED=0 uploads the big
  * arrays of a load by plain hipMemcpy;  RBG_VERBOSE=1 prints what the budget rule did and the seconds of every stage of a load. */
 enum { RBG_OPT_BLOCK_THREADS = 1, RBG_OPT_RANK_BUCKET_SHIFT = 2, RBG_OPT_PHI_BUCKET_SHIFT = 3, RBG_OPT_POS_BYTES = 4,
@@ -580,7 +595,9 @@ enum { RBG_OPT_BLOCK_THREADS = 1, RBG_OPT_RANK_BUCKET_SHIFT = 2, RBG_OPT_PHI_BUC
                                   value, RBG_RUN_REC_PER the entries per bucket; rbg_layout_info().rec_bytes says what was built, per depth. */,
        RBG_OPT_RUN_REC_DEPTHS = 18 /* with RBG_OPT_RUN_REC = 2: bit d - 1 = the k-mer depth d gets bucket records, the other kept depths keep their
                                   directories (0, the default: every kept depth).  An index of r = 1e9 runs has room for the records of its deepest depth
-                                  but not of all (profiles/r05_pangenome_stream_r1e9.json).  RBG_RUN_REC_DEPTHS gives the initial value. */ };
+                                  but not of all (profiles/r05_pangenome_stream_r1e9.json).  RBG_RUN_REC_DEPTHS gives the initial value. */,
+       RBG_OPT_JUMP_K = 19 /* the jump table (rbg_jump_info): 0 = none, 16..64 = a table of that many symbols per key, -1 (default) = 60 symbols
+                                  when the replica is larger than the device's 256 MB last-level cache and the table adds at most half of it, none otherwise.  RBG_JUMP_K gives the initial value. */ };
 int rbg_set_default_option(int opt, int64_t value);
 /* the value a later load would use (so that a caller can change a knob for one load and put it back) */
 int rbg_get_default_option(int opt, int64_t *value);

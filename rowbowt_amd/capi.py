@@ -22,6 +22,7 @@ DEVICE_NONE = -1
 
 OPT_BLOCK_THREADS, OPT_RANK_BUCKET_SHIFT, OPT_PHI_BUCKET_SHIFT, OPT_POS_BYTES, OPT_KMER_STEPS, OPT_HBM_BUDGET_MB, OPT_FTAB_K, OPT_PACKED_READS, OPT_DEEP_BUCKET_SHIFT, OPT_DENSE_OVERFLOW, OPT_RANK_LAYOUT = range(1, 12)
 OPT_RUN_DEPTHS, OPT_RUN_PHI, OPT_RUN_REC, OPT_RUN_REC_DEPTHS = 14, 16, 17, 18   # (12, 13, 15 were TREE_TOP_KB, SLOT_BYTES, RUN_FMT: retired with ABI 3)
+OPT_JUMP_K = 19          # the jump table (rbg_jump_info): 0 = off, -1 = automatic, 16..64 = symbols per key
 ABI_VERSION = 3          # include/rbg.h RBG_ABI_VERSION this binding is written against
 MAX_KMER_DEPTH = 8       # RBG_OPT_KMER_STEPS / the depth arrays of Info and LayoutInfo
 LAYOUT_AUTO, LAYOUT_SLOTS, LAYOUT_RUNS, LAYOUT_PREFER_SLOTS = 0, 1, 2, 3
@@ -64,6 +65,11 @@ class LayoutInfo(C.Structure):
                 ("phi_entries", U64), ("phi_fillers", U64), ("phi_dir_bytes", U64), ("phi_dir_shift", U64), ("phi_slots", U64), ("phi_slot_bytes", U64), ("rec_bytes", U64 * 8), ("rec_overflow", U64 * 8), ("budget_raised", U64)]
 
 
+class JumpInfo(C.Structure):
+    """rbg_jump_info_t"""
+    _fields_ = [("k", U64), ("keys", U64), ("bytes", U64), ("buckets", U64), ("build_ms", C.c_double)]
+
+
 # every symbol include/rbg.h declares: (name, restype, argtypes)
 _PROTOS = [
     ("rbg_abi_version", C.c_int, []),
@@ -89,6 +95,7 @@ _PROTOS = [
     ("rbg_info", C.c_int, [VP, C.POINTER(Info)]),
     ("rbg_info_sized", C.c_int, [VP, C.POINTER(Info), U64]),
     ("rbg_layout_info", C.c_int, [VP, C.POINTER(LayoutInfo), U64]),
+    ("rbg_jump_info", C.c_int, [VP, C.POINTER(JumpInfo)]),
     ("rbg_get_f", C.c_int, [VP, VP]),
     ("rbg_last_run_sample", C.c_int, [VP, C.POINTER(U64)]),
     ("rbg_host_array", C.c_int, [VP, C.c_int, VP, U64, C.POINTER(U64)]),
@@ -147,6 +154,7 @@ _PROTOS = [
     ("rbg_get_default_option", C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
 ]
 EXPORTS = [p[0] for p in _PROTOS]
+_OPTIONAL = {"rbg_jump_info"}
 
 _lib = None
 
@@ -183,6 +191,8 @@ def lib():
         if have != ABI_VERSION:   # (the structs above and the option numbers are this ABI's: never bind another one's symbols blindly)
             raise ImportError(f"{_SO} reports ABI {have}, this binding is written against ABI {ABI_VERSION}: rebuild it with `make -C rowbowt_amd/csrc`")
         for name, res, args in _PROTOS:
+            if name in _OPTIONAL and not hasattr(L, name):   # (an addition within ABI 3: bound when the library has it)
+                continue
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -339,6 +349,12 @@ class RowBowt:
     def info(self):
         i = Info()
         _check(self.L.rbg_info(self.h, C.byref(i)), "rbg_info")
+        return i
+
+    def jump_info(self):
+        """the jump table of this replica (rbg_jump_info_t; all zero when none was built)"""
+        i = JumpInfo()
+        _check(self.L.rbg_jump_info(self.h, C.byref(i)), "rbg_jump_info")
         return i
 
     def layout_info(self):

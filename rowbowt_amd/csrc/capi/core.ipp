@@ -39,6 +39,9 @@ struct rbg_index {
     bool auto_runs = false;        // RBG_LAYOUT_AUTO chose the run-indexed layout because the slot tables of every requested symbol per step exceed the budget
     bool runs_forced = false;      // the composition already gave back the depths the run-indexed layout leaves out: no way back to slot tables
     uint32_t run_depth_mask = 0;   // run-indexed layout: the k-mer depths that have run lists (bit d - 1)
+    // the jump table (rbg_jump_info): K, keys, bytes, buckets, build time (0 when none was built)
+    uint64_t jump_k = 0, jump_keys = 0, jump_bytes = 0, jump_buckets = 0;
+    double jump_build_ms = 0.0;
     // what the load decided about the run-indexed layout (rbg_layout_info): nothing is left out without a line here
     struct RunsReport {
         uint32_t fmt = 0, depth_mask_asked = 0, depth_mask_kept = 0, depths_composed = 0;
@@ -105,6 +108,16 @@ std::atomic<int64_t> g_opt_pos_bytes{0};
 std::atomic<int64_t> g_opt_kmer_steps{env_opt("RBG_KMER_STEPS", kMaxKmerDepth, 1, kMaxKmerDepth)};   // (the slot layout stages at most kMaxSlotKmerDepth = 5)
 std::atomic<int64_t> g_opt_hbm_budget_mb{env_opt("RBG_HBM_BUDGET_MB", 0, 0, int64_t(1) << 40)};
 std::atomic<int64_t> g_opt_ftab_k{env_opt("RBG_FTAB_K", -1, -1, 16)};
+// RBG_OPT_JUMP_K: -1 = automatic (kJumpDefaultK once the replica outgrows the last-level cache), 0 = off, kJumpMinK..kJumpMaxK = that K
+int64_t env_jump_k() {
+    const int64_t v = env_opt("RBG_JUMP_K", -1, -1, kJumpMaxK);
+    if (v > 0 && v < static_cast<int64_t>(kJumpMinK)) {
+        std::fprintf(stderr, "rbg: RBG_JUMP_K=%lld ignored (expected -1, 0 or %u..%u)\n", static_cast<long long>(v), kJumpMinK, kJumpMaxK);
+        return -1;
+    }
+    return v;
+}
+std::atomic<int64_t> g_opt_jump_k{env_jump_k()};
 std::atomic<int64_t> g_opt_deep_shift{-1};
 std::atomic<int64_t> g_opt_dense_overflow{1};
 std::atomic<int64_t> g_opt_rank_layout{env_opt("RBG_LAYOUT", RBG_LAYOUT_AUTO, RBG_LAYOUT_AUTO, RBG_LAYOUT_PREFER_SLOTS)};    // RBG_LAYOUT_AUTO / _SLOTS / _RUNS / _PREFER_SLOTS

@@ -265,6 +265,53 @@ int upload(rbg_index *ix) {
             HIP_TRY(hipMemset(d.counters, 0, 4 * sizeof(uint64_t)));  // the build's own searches are not user queries
         }
     }
+    // jump table (rbg_jump.h, k_jump.hip): built after the ftab and after every decision above -- the lowest priority of the budget, so the
+    // layout is the one the replica has without it (rbg_layout_info identical).  What the budget leaves holds the table or nothing.
+    d.jump = nullptr;
+    d.jump_buckets = 0;
+    d.jump_k = 0;
+    int64_t jk = g_opt_jump_k.load();
+    const bool jump_auto = jk < 0;
+    if (jump_auto) jk = ix->hbm_bytes > kJumpAutoMinBytes ? kJumpDefaultK : 0;
+    if (jk > 0) {
+        VStage vs("jump table");
+        const auto t0 = std::chrono::steady_clock::now();
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        // what the HBM budget leaves after the replica holds the build at its peak (scratch + table), and at most half of the free memory
+        const uint64_t budget = ix->hbm_budget;
+        const uint64_t room = budget > ix->hbm_bytes ? budget - ix->hbm_bytes : 0;
+        const uint64_t peak_budget = std::min<uint64_t>(room, free_b / 2);
+        uint64_t table_budget = std::min<uint64_t>(room, free_b / 4);
+        // (by default the table may add at most half of the replica: on a text of few repeats -- nearly every K-mer distinct -- it would
+        //  outgrow the index it serves; the bench index's is a third)
+        if (jump_auto) table_budget = std::min<uint64_t>(table_budget, ix->hbm_bytes / 2);
+        void *tab = nullptr;
+        uint64_t bytes = 0, nb = 0, keys = 0;
+        const char *why = nullptr;
+        int rc = launch_build_jump(d, ix->cfg, static_cast<uint32_t>(jk), table_budget, peak_budget, &tab, &bytes, &nb, &keys, &why, nullptr);
+        if (rc == static_cast<int>(hipErrorOutOfMemory)) { (void)hipGetLastError(); rc = 0; why = "out of device memory while building it"; }
+        if (rc) return RBG_ENODEV;
+        HIP_TRY(hipMemset(d.counters, 0, 4 * sizeof(uint64_t)));  // (the build's own searches are not user queries)
+        ix->jump_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (tab) {
+            ix->allocs.push_back({tab, static_cast<size_t>(bytes)});
+            ix->hbm_bytes += bytes;
+            d.jump = tab;
+            d.jump_buckets = nb;
+            d.jump_k = static_cast<uint32_t>(jk);
+            ix->jump_k = static_cast<uint64_t>(jk);
+            ix->jump_keys = keys;
+            ix->jump_bytes = bytes;
+            ix->jump_buckets = nb;
+            if (std::getenv("RBG_VERBOSE"))
+                std::fprintf(stderr, "rbg: device %d: jump table of %lld-mers: %llu keys, %.2f GB, %.0f ms\n", ix->device, static_cast<long long>(jk),
+                             static_cast<unsigned long long>(keys), bytes / 1e9, ix->jump_build_ms);
+        } else if (std::getenv("RBG_VERBOSE")) {
+            std::fprintf(stderr, "rbg: device %d: no jump table of %lld-mers (%llu occur): %s\n", ix->device, static_cast<long long>(jk),
+                         static_cast<unsigned long long>(keys), why ? why : "skipped");
+        }
+    }
     return RBG_OK;
 }
 
@@ -836,6 +883,9 @@ int rbg_set_default_option(int opt, int64_t value) {
         case RBG_OPT_RUN_REC_DEPTHS:
             if (value < 0 || value >= (1 << kMaxRunDepth)) return RBG_EARG;
             g_opt_run_rec_depths = value; return RBG_OK;
+        case RBG_OPT_JUMP_K:
+            if (value < -1 || value > static_cast<int64_t>(kJumpMaxK) || (value > 0 && value < static_cast<int64_t>(kJumpMinK))) return RBG_EARG;
+            g_opt_jump_k = value; return RBG_OK;
         default: return RBG_EARG;
     }
     });
@@ -860,6 +910,7 @@ int rbg_get_default_option(int opt, int64_t *value) {
         case RBG_OPT_RUN_PHI: *value = g_opt_run_phi.load(); return RBG_OK;
         case RBG_OPT_RUN_REC: *value = g_opt_run_rec.load(); return RBG_OK;
         case RBG_OPT_RUN_REC_DEPTHS: *value = g_opt_run_rec_depths.load(); return RBG_OK;
+        case RBG_OPT_JUMP_K: *value = g_opt_jump_k.load(); return RBG_OK;
         default: return RBG_EARG;
     }
     });
@@ -1236,6 +1287,21 @@ int rbg_info_sized(const rbg_index *ix, rbg_info_t *out, uint64_t out_bytes) {
     if (rc) return rc;
     std::memcpy(out, &v, static_cast<size_t>(std::min<uint64_t>(out_bytes, sizeof(v))));
     return RBG_OK;
+}
+
+int rbg_jump_info(const rbg_index *ix, rbg_jump_info_t *out) {
+    return guarded([&]() -> int {
+    if (!ix || !out) return RBG_EARG;
+    const rbg_index *s = ix->primary ? ix->primary : ix;   // (a replica holds a copy of its primary's table)
+    std::memset(out, 0, sizeof(*out));
+    if (!ix->dev.jump) return RBG_OK;
+    out->k = ix->dev.jump_k;
+    out->keys = s->jump_keys;
+    out->bytes = s->jump_bytes;
+    out->buckets = ix->dev.jump_buckets;
+    out->build_ms = s->jump_build_ms;
+    return RBG_OK;
+    });
 }
 
 int rbg_info(const rbg_index *ix, rbg_info_t *out) {

@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "rbg_runs2_device.hpp"
+#include "rbg_jump.h"
 
 namespace rbg {
 namespace {
@@ -41,6 +42,17 @@ struct PackedBits {   // per-lane reader of a packed read: peek / drop of up to 
         sr >>= nb;
         navail -= nb;
         return v;
+    }
+};
+
+// a slot of the jump table as two 16-byte loads (rbg_jump.h jump_probe)
+struct JumpLoad {
+    const uint4 *__restrict__ tab;
+    __device__ __forceinline__ void operator()(uint64_t b, uint32_t s, uint32_t kw[4], uint32_t vw[4]) const {
+        const uint4 *sl = tab + (4 * b + 2 * s);
+        const uint4 k = sl[0], v = sl[1];
+        kw[0] = k.x; kw[1] = k.y; kw[2] = k.z; kw[3] = k.w;
+        vw[0] = v.x; vw[1] = v.y; vw[2] = v.z; vw[3] = v.w;
     }
 };
 
@@ -127,7 +139,25 @@ __global__ __launch_bounds__(512, STATS ? 2 : 4) void k_find_range_runs(const De
             uint32_t pend_d = 0, pend_rec = 0;
             uint64_t pend_e = 0;
             ByteCursor rd{reinterpret_cast<const uint4 *>(seqs), ~uint64_t(0), make_uint4(0, 0, 0, 0)};
-            if (valid && ix.ftab_k && p - beg >= ix.ftab_k) {      // rowbowt.hpp:124-125, :745-758 (k_search.hip)
+            // JUMP (rbg_jump.h): a staged read of at least jump_k symbols looks its last jump_k up in the table of the K-mers that occur -- one
+            // probe in place of the ftab entry and the first (jump_k - ftab_k) / 8 steps; a key that is absent takes the ftab path below
+            bool jumped = false;
+            if constexpr (STAGED && sizeof(P) == 4) {
+                if (valid && ix.jump && m32 >= ix.jump_k) {
+                    JumpKey key{{codes[0], codes[64], codes[128], codes[192]}};   // the first 64 symbols in consumption order
+                    jump_key_mask(key, ix.jump_k);
+                    uint32_t v[3] = {0, 0, 0}, nbk = 0;
+                    if (jump_probe(JumpLoad{static_cast<const uint4 *>(ix.jump)}, ix.jump_buckets, key, v, nbk)) {
+                        lo = v[0]; hi = v[1];
+                        if (TOEHOLD) k = v[2] == 0xFFFFFFFFu ? ~uint64_t(0) : static_cast<uint64_t>(v[2]);
+                        p -= ix.jump_k;
+                        jumped = true;
+                        if (STATS) st[kStSymbols] += ix.jump_k;
+                    }
+                    if (STATS) st[kStFtab] += nbk;                   // (the ftab slot counts probed buckets too: 64 bytes each)
+                }
+            }
+            if (!jumped && valid && ix.ftab_k && p - beg >= ix.ftab_k) {      // rowbowt.hpp:124-125, :745-758 (k_search.hip)
                 uint64_t idx = 0;
                 bool all_major = true;
                 PackedBits probe = bs;                             // consumed only if the entry is usable

@@ -26,6 +26,7 @@
 
 #include "../../include/rbg.h"
 #include "rbg_dev.h"
+#include "rbg_jump.h"
 #include "rbg_host.hpp"
 
 

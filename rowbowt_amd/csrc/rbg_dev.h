@@ -325,6 +325,11 @@ struct DevIndex {
     uint32_t stage_ok, stage_shift;
     uint32_t stage_code[2];    // byte t of {[0], [1]}: the major index of the symbol whose (byte >> shift) & 7 == t (0 where there is none)
     uint32_t stage_byte[2];    // ... and that symbol's byte (a byte no symbol of the alphabet has where there is none)
+    // jump table (rbg_jump.h; k_jump.hip builds it, the staged walk of k_find_range_runs probes it): the state after every OCCURRING
+    // K-mer, K = jump_k; 4-byte positions and the run-indexed layout only.  nullptr = none.
+    const void *jump;          // jump_buckets x 64 bytes
+    uint64_t jump_buckets;
+    uint32_t jump_k;
 };
 
 // What the instrumented instantiations count (sums over the launch; include/rbg.h rbg_search_stats_t mirrors it).
@@ -566,6 +571,12 @@ int launch_lf(const DevIndex &ix, const LaunchCfg &cfg, const uint64_t *lo, cons
 // fills ix.ftab-shaped table `tab` (nmajor^k entries x 4 u64) by searching every k-symbol word
 int launch_build_ftab(const DevIndex &ix, const LaunchCfg &cfg, uint32_t k, void *tab, void *stream);
 size_t ftab_build_scratch_bytes(uint64_t words, uint32_t k);  // device scratch the build takes besides the table
+// jump table (k_jump.hip): enumerates the K-mers that occur by backward extension level by level (launch_lf), then -- if the table of
+// those keys fits `table_budget` bytes -- allocates it (*tab, *tab_bytes; the caller owns it) and fills it with the states k_find_range_runs
+// itself computes for them.  *keys = K-mers that occur; *tab = nullptr with `why` set when the table was skipped.  Device scratch is
+// allocated and freed inside; scratch and table together never exceed `peak_budget` bytes (checked before every allocation; skipped otherwise).
+int launch_build_jump(const DevIndex &ix, const LaunchCfg &cfg, uint32_t K, uint64_t table_budget, uint64_t peak_budget, void **tab,
+                      uint64_t *tab_bytes, uint64_t *buckets, uint64_t *keys, const char **why, void *stream);
 int launch_sample_reads(const uint8_t *text, uint64_t unit, uint64_t H, uint64_t L, uint64_t m, uint64_t seed, uint64_t first,
                         uint64_t N, uint32_t sub_ppm, uint8_t *seqs, uint64_t *off, uint64_t *start_out /*nullable*/, void *stream);
 int launch_sample_reads_pg(const uint8_t *base, const uint64_t *sites, const uint8_t *alt, const uint8_t *G, uint64_t S, const uint32_t *site_dir, uint32_t site_dir_shift,

@@ -1,0 +1,96 @@
+// rbg_jump.h -- the jump table: for every K-mer (K <= 64) that OCCURS in the text, the search state {lo, hi, toehold} after
+// backward search over it.  It is the reference's ftab (rowbowt.hpp:121-131, :726-758) made sparse: the ftab holds every word of
+// ftab_k symbols, this table only the words that occur, so K can be four or five times longer.  A read of at least K symbols
+// looks up its last K in one probe (usually one 64-byte bucket) instead of the ftab entry and (K - ftab_k) / 8 bucket records;
+// a key that is absent -- the read has a symbol in its last K that the text does not -- costs one probe and the read takes the
+// ftab path.  Built at load by the library's own kernels (k_jump.hip), result-neutral by construction.
+//
+// Key: the K symbols as 2-bit major codes in CONSUMPTION order (symbol t of the key = the read's symbol m - 1 - t at bits
+// [2t, 2t + 2) of the 128-bit key; bits from 2K up are zero) -- the layout of the staged reads (rbg_runs_device.hpp) and of the
+// packed chunks, so a staged read's key is its first four LDS words, masked.
+// Slot: 32 bytes = key (4 words), lo, hi, toehold, tag (1 = occupied, 0 = empty).  A toehold of 2^64 - 1 travels as 0xFFFFFFFF
+// (as in the ftab); a word whose toehold fits neither is not inserted.  Two slots per 64-byte bucket; `nb` buckets, open
+// addressing over buckets (linear, wrapping at the end).  A probe ends at the matching key or at the first empty slot: the build
+// keeps the load at or below one half, so a chain ends soon for absent keys as well.
+// Plain C++ (host and device): tests/cpp/jump_table_check.cpp checks the key packing and the probe on a host model of the table.
+#pragma once
+
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define RBG_JUMP_HD __host__ __device__ __forceinline__
+#else
+#define RBG_JUMP_HD inline
+#endif
+
+namespace rbg {
+
+constexpr uint32_t kJumpMaxK = 64;     // symbols of a key (128 bits)
+constexpr uint32_t kJumpMinK = 16;     // RBG_OPT_JUMP_K: shorter keys would not reach past the ftab
+constexpr uint32_t kJumpSlotWords = 8;
+constexpr uint32_t kJumpBucketBytes = 64;
+constexpr uint32_t kJumpEmptyTag = 0, kJumpFullTag = 1;
+constexpr uint32_t kJumpDefaultK = 60;  // RBG_OPT_JUMP_K = -1 (the sweep over 44 / 52 / 60; 60 + 5 x 8 = 100)
+// ... built by default only for a replica larger than MI355X's 256 MB last-level cache (below that an index's gathers are cache hits and a
+// probe saves nothing; the small indexes of the tests, too, keep today's path unless they ask for the table), and only when the table adds
+// at most half of the replica (capi/load.ipp)
+constexpr uint64_t kJumpAutoMinBytes = uint64_t(256) << 20;
+
+struct JumpKey {
+    uint32_t w[4];
+};
+
+// keep the first K symbols of the key (bits [0, 2K)), zero the rest
+RBG_JUMP_HD void jump_key_mask(JumpKey &key, uint32_t K) {
+    for (uint32_t i = 0; i < 4; ++i) {
+        const uint32_t lo_sym = 16u * i;
+        const uint32_t keep = K <= lo_sym ? 0u : (K - lo_sym >= 16u ? 16u : K - lo_sym);
+        key.w[i] = keep == 16u ? key.w[i] : (key.w[i] & ((1u << (2u * keep)) - 1u));
+    }
+}
+
+// symbol t (consumption order) set to the 2-bit code c
+RBG_JUMP_HD void jump_key_set(JumpKey &key, uint32_t t, uint32_t c) {
+    key.w[t >> 4] |= (c & 3u) << (2u * (t & 15u));
+}
+
+RBG_JUMP_HD uint64_t jump_hash(const JumpKey &key) {
+    const uint64_t a = key.w[0] | (static_cast<uint64_t>(key.w[1]) << 32);
+    const uint64_t b = key.w[2] | (static_cast<uint64_t>(key.w[3]) << 32);
+    uint64_t h = (a * 0x9E3779B97F4A7C15ull) ^ ((b + 0x632BE59BD9B4E019ull) * 0xC2B2AE3D27D4EB4Full);
+    h ^= h >> 29;
+    h *= 0xBF58476D1CE4E5B9ull;
+    h ^= h >> 32;
+    return h;
+}
+
+// the home bucket of a hash among nb (< 2^32) buckets: the high 32 bits scaled to [0, nb)
+RBG_JUMP_HD uint64_t jump_home(uint64_t h, uint64_t nb) {
+    return ((h >> 32) * nb) >> 32;
+}
+
+// The probe.  load(bucket, slot, key_words[4], val_words[4]) reads one slot.  On a hit fills v = {lo, hi, toehold} and returns true;
+// `buckets` = buckets read (the STATS count).  At most nb buckets are visited (a table that is never full ends far sooner).
+template <typename Load>
+RBG_JUMP_HD bool jump_probe(const Load &load, uint64_t nb, const JumpKey &key, uint32_t v[3], uint32_t &buckets) {
+    uint64_t b = jump_home(jump_hash(key), nb);
+    for (uint64_t step = 0; step < nb; ++step) {
+        ++buckets;
+        for (uint32_t s = 0; s < 2; ++s) {
+            uint32_t kw[4], vw[4];
+            load(b, s, kw, vw);
+            if (vw[3] == kJumpEmptyTag) return false;
+            if (kw[0] == key.w[0] && kw[1] == key.w[1] && kw[2] == key.w[2] && kw[3] == key.w[3]) {
+                v[0] = vw[0]; v[1] = vw[1]; v[2] = vw[2];
+                return true;
+            }
+        }
+        b = b + 1 == nb ? 0 : b + 1;
+    }
+    return false;
+}
+
+// buckets of a table holding `keys` keys at a load of at most one half (two slots per bucket), at least one
+inline uint64_t jump_buckets_for(uint64_t keys) { return keys ? keys : 1; }
+
+}  // namespace rbg
