@@ -280,6 +280,23 @@ typedef struct rbg_marker_seed {
 int rbg_get_markers_greedy_seeding(rbg_index *, const uint8_t *seqs, const uint64_t *off, uint64_t N,
                                    uint64_t wsize, uint64_t max_range, uint64_t ftab_k,
                                    uint64_t *seed_off, rbg_marker_seed_t **seeds, uint64_t **mk);
+/* RowBowt::get_markers_lmems(query, wsize, max_range, fn), rowbowt.hpp:341-404 (rb_markers --ftab --lmem): a fresh backward
+ * search from every end position e = m, m-1, ..., 1 of each sequence, in callback order; the same records and arguments as
+ * rbg_get_markers_greedy_seeding.  Only the non-empty calls are returned -- exactly len(sequence) records per sequence, so
+ * seed_off[] == off[] -- the reference's second call after a failed extension (the empty range, the same q, an empty mbuf)
+ * is left to the caller (rowbowt_gpu.hpp replays it; rb_markers drops it).  ftab_k = 0: plain longest matches from the full
+ * range; ftab_k = K > 0: as with the ftab of k-mer size K loaded (the check "ftab must be enabled!" and K - 1 <= wsize are the
+ * caller's, as in the reference, :346-354).  Quirks kept:
+ *   1. search_ftab answers a miss (an absent K-mer, or any byte outside ACGT) with the FULL range (:746-758), so :371-373 is
+ *      never taken: the walk goes on from the full range with K symbols counted, and the record includes them.
+ *   2. the ftab part does not move the window end: the first window query comes after the first step past the K-mer.
+ *   3. a suffix shorter than K starts from the full range without the ftab (no substr past the end, unlike the greedy mode).
+ *   4. a failure at the first symbol (e.g. an N at e - 1) reports the full range with length 0 (qstart = qend = e).
+ * Markers are unsorted and not deduplicated, as in the greedy call.  The batch is walked on the device in passes of about
+ * 4 Mi records (RBG_LMEM_CHUNK), so device memory stays bounded; the host result is 48 bytes per symbol. */
+int rbg_get_markers_lmems(rbg_index *, const uint8_t *seqs, const uint64_t *off, uint64_t N,
+                          uint64_t wsize, uint64_t max_range, uint64_t ftab_k,
+                          uint64_t *seed_off, rbg_marker_seed_t **seeds, uint64_t **mk);
 /* Next-row f4 (greedy seeding).  RowBowt::get_seeds_greedy_w_sample(query, min_length),
  * rowbowt.hpp:222-256, reduced by the choice locate_from_longest_seed makes (rowbowt.hpp:669-677):
  * per read the FIRST seed of strictly greatest length, as LFData {rn, qstart, qend, ssamp}; a read
@@ -402,6 +419,16 @@ int rbg_marker_seeds_plan_log_dev(rbg_index *, const uint8_t *d_seqs, const uint
 int rbg_marker_seeds_fill_log_dev(rbg_index *, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t wsize,
                                   uint64_t max_range, uint64_t ftab_k, const uint64_t *d_seed_off, const uint64_t *d_mk_off,
                                   rbg_marker_seed_t *d_seeds, uint64_t *d_mk, void *d_log, size_t log_bytes, void *stream);
+/* lmem marker seeds (rbg_get_markers_lmems), two-phase.  total: any upper bound on d_off[N] - d_off[0] (the number of records).
+ * d_tmp: rbg_marker_lmems_tmp_bytes(N, total) bytes, 8-byte aligned: the plan leaves every record's marker offset there and the
+ * fill reads it, so d_tmp must be left untouched between the two calls.  The plan writes d_mk_off[N+1], the exclusive scan of
+ * the markers per sequence (d_mk_off[N] sizes d_mk); the fill writes record k of sequence i at d_seeds[d_off[i] - d_off[0] + k]
+ * (caller provides (d_off[N] - d_off[0]) * 48 bytes) and the markers (caller provides d_mk_off[N] * 8 bytes; NULL when 0). */
+size_t rbg_marker_lmems_tmp_bytes(uint64_t N, uint64_t total);
+int rbg_marker_lmems_plan_dev(rbg_index *, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t total, uint64_t wsize,
+                              uint64_t max_range, uint64_t ftab_k, uint64_t *d_mk_off, void *d_tmp, size_t tmp_bytes, void *stream);
+int rbg_marker_lmems_fill_dev(rbg_index *, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t total, uint64_t wsize,
+                              uint64_t max_range, uint64_t ftab_k, const void *d_tmp, rbg_marker_seed_t *d_seeds, uint64_t *d_mk, void *stream);
 /* markers, same two-phase shape */
 int rbg_markers_plan_dev(rbg_index *, const uint64_t *d_lo, const uint64_t *d_hi, uint64_t N,
                          uint64_t *d_mk_off, void *d_tmp, size_t tmp_bytes, void *stream);

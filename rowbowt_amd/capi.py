@@ -150,6 +150,10 @@ _PROTOS = [
     ("rbg_counters", C.c_int, [VP, VP]),
     ("rbg_counters_reset", C.c_int, [VP]),
     ("rbg_combine_stats", C.c_int, [VP, VP]),
+    ("rbg_get_markers_lmems", C.c_int, [VP, VP, VP, U64, U64, U64, U64, VP, C.POINTER(VP), C.POINTER(VP)]),
+    ("rbg_marker_lmems_tmp_bytes", C.c_size_t, [U64, U64]),
+    ("rbg_marker_lmems_plan_dev", C.c_int, [VP, VP, VP, U64, U64, U64, U64, U64, VP, VP, C.c_size_t, VP]),
+    ("rbg_marker_lmems_fill_dev", C.c_int, [VP, VP, VP, U64, U64, U64, U64, U64, VP, VP, VP, VP]),
     ("rbg_set_default_option", C.c_int, [C.c_int, C.c_int64]),
     ("rbg_get_default_option", C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
 ]
@@ -452,6 +456,20 @@ class RowBowt:
         ps, pm = VP(), VP()
         _check(self.L.rbg_get_markers_greedy_seeding(self.h, _p(seqs), _p(off), N, wsize, max_range & MAXU, ftab_k, _p(seed_off),
                                                      C.byref(ps), C.byref(pm)), "rbg_get_markers_greedy_seeding")
+        S = int(seed_off[N])
+        seeds = _take(ps, 6 * S).reshape(S, 6)
+        nmk = int(seeds[-1, 5]) if S else 0
+        return seed_off, seeds, _take(pm, nmk)
+
+    def get_markers_lmems(self, seqs, off, wsize, max_range=MAXU, ftab_k=0):
+        """RowBowt::get_markers_lmems (rowbowt.hpp:341-404): one record per end position m, m-1, ..., 1 of each sequence (the
+        non-empty calls of the callback), ftab_k = k-mer size of the ftab or 0: -> seed_off[N+1] (== off), seeds[S,6] =
+        (lo, hi, qstart, qend, mk_begin, mk_end), mk"""
+        N = len(off) - 1
+        seed_off = np.zeros(N + 1, np.uint64)
+        ps, pm = VP(), VP()
+        _check(self.L.rbg_get_markers_lmems(self.h, _p(seqs), _p(off), N, wsize, max_range & MAXU, ftab_k, _p(seed_off),
+                                            C.byref(ps), C.byref(pm)), "rbg_get_markers_lmems")
         S = int(seed_off[N])
         seeds = _take(ps, 6 * S).reshape(S, 6)
         nmk = int(seeds[-1, 5]) if S else 0

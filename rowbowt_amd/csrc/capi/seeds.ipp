@@ -250,6 +250,105 @@ static int marker_seeds_host(rbg_index *ix, const uint8_t *seqs, const uint64_t 
     }
 }
 
+// ---- lmem marker seeds: get_markers_lmems, rowbowt.hpp:341-404 -------------------------------------------------
+// One record per (sequence, end position): record k of sequence i at off[i] - off[0] + k.  The plan walks every end position
+// once to count its markers, scans those counts in d_tmp and writes the per-sequence scan; the fill walks again and writes.
+
+size_t rbg_marker_lmems_tmp_bytes(uint64_t N, uint64_t total) {
+    (void)N;
+    return marker_lmems_tmp_bytes(total);
+}
+
+int rbg_marker_lmems_plan_dev(rbg_index *ix, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t total, uint64_t wsize,
+                              uint64_t max_range, uint64_t ftab_k, uint64_t *d_mk_off, void *d_tmp, size_t tmp_bytes, void *stream) {
+    return guarded([&]() -> int {
+    if (!queryable(ix)) return RBG_ENODEV;
+    if (!d_mk_off || (N && (!d_seqs || !d_off || !d_tmp))) return RBG_EARG;
+    if (reinterpret_cast<uintptr_t>(d_seqs) & 15 || reinterpret_cast<uintptr_t>(d_tmp) & 7) return RBG_EARG;
+    if (N && tmp_bytes < marker_lmems_tmp_bytes(total)) return RBG_EARG;
+    return launch_marker_lmems_plan(ix->dev, ix->cfg, d_seqs, d_off, N, total, wsize, max_range, ftab_k, d_mk_off, d_tmp, tmp_bytes, stream)
+               ? RBG_ENODEV : RBG_OK;
+    });
+}
+
+int rbg_marker_lmems_fill_dev(rbg_index *ix, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t total, uint64_t wsize,
+                              uint64_t max_range, uint64_t ftab_k, const void *d_tmp, rbg_marker_seed_t *d_seeds, uint64_t *d_mk, void *stream) {
+    return guarded([&]() -> int {
+    if (!queryable(ix)) return RBG_ENODEV;
+    if (N && total && (!d_seqs || !d_off || !d_tmp || !d_seeds)) return RBG_EARG;
+    if (reinterpret_cast<uintptr_t>(d_seqs) & 15 || reinterpret_cast<uintptr_t>(d_tmp) & 7) return RBG_EARG;
+    return launch_marker_lmems_fill(ix->dev, ix->cfg, d_seqs, d_off, N, total, wsize, max_range, ftab_k, d_tmp,
+                                    reinterpret_cast<uint64_t *>(d_seeds), d_mk, stream) ? RBG_ENODEV : RBG_OK;
+    });
+}
+
+// records per device pass of rbg_get_markers_lmems: 48 bytes each, 4 Mi records = 192 MiB of records plus 32 MiB of offsets
+// (RBG_LMEM_CHUNK=<records> overrides; a sequence longer than a chunk gets a pass of its own)
+static uint64_t lmem_chunk_records() {
+    const char *e = std::getenv("RBG_LMEM_CHUNK");
+    const uint64_t v = e ? std::strtoull(e, nullptr, 10) : 0;
+    return v ? v : (uint64_t(1) << 22);
+}
+
+int rbg_get_markers_lmems(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t wsize, uint64_t max_range,
+                          uint64_t ftab_k, uint64_t *seed_off, rbg_marker_seed_t **seeds, uint64_t **mk) {
+    return guarded([&]() -> int {
+    if (!queryable(ix)) return RBG_ENODEV;
+    if (!seed_off || !seeds || !mk || (N && !off)) return RBG_EARG;
+    *seeds = nullptr;
+    *mk = nullptr;
+    int rc = check_offsets(off, N);
+    if (rc) return rc;
+    const uint64_t total = N ? off[N] : 0;
+    for (uint64_t i = 0; i <= N; ++i) seed_off[i] = N ? off[i] : 0;   // exactly len(sequence) records each
+    DeviceScope scope(ix->device);
+    if (scope.rc) return scope.rc;
+    hipStream_t st = hipStreamPerThread;
+    auto *h_seeds = static_cast<rbg_marker_seed_t *>(alloc_result(total * sizeof(rbg_marker_seed_t)));
+    if (!h_seeds) return RBG_ENOMEM;
+    std::vector<uint64_t> h_mk;
+    const uint64_t chunk = lmem_chunk_records();
+    for (uint64_t a = 0; a < N && !rc;) {
+        uint64_t b = a + 1;   // sequences [a, b): at least one, and as many whole ones as fit the chunk
+        while (b < N && off[b + 1] - off[a] <= chunk) ++b;
+        const uint64_t n = b - a, recs = off[b] - off[a];
+        std::vector<uint64_t> roff(n + 1);
+        for (uint64_t i = 0; i <= n; ++i) roff[i] = off[a + i] - off[a];
+        ReadBatch rb;
+        DevBuf dmoff, dtmp, dseeds, dmk;
+        const size_t tmp_bytes = marker_lmems_tmp_bytes(recs);
+        if ((rc = rb.stage(seqs + off[a], roff.data(), n, st)) || (rc = dmoff.alloc((n + 1) * 8)) || (rc = dtmp.alloc(tmp_bytes))) break;
+        if (launch_marker_lmems_plan(ix->dev, ix->cfg, rb.seqs.as<uint8_t>(), rb.off.as<uint64_t>(), n, recs, wsize, max_range, ftab_k,
+                                     dmoff.as<uint64_t>(), dtmp.p, tmp_bytes, st)) { rc = RBG_ENODEV; break; }
+        uint64_t nmk = 0;
+        if (hipMemcpyAsync(&nmk, dmoff.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+            rc = RBG_ENODEV;
+            break;
+        }
+        if ((rc = dseeds.alloc(recs * sizeof(rbg_marker_seed_t))) || (rc = dmk.alloc(nmk * 8))) break;
+        if (launch_marker_lmems_fill(ix->dev, ix->cfg, rb.seqs.as<uint8_t>(), rb.off.as<uint64_t>(), n, recs, wsize, max_range, ftab_k, dtmp.p,
+                                     dseeds.as<uint64_t>(), dmk.as<uint64_t>(), st)) { rc = RBG_ENODEV; break; }
+        rbg_marker_seed_t *dst = h_seeds + off[a];
+        if ((rc = d2h_result(dst, dseeds.p, recs * sizeof(rbg_marker_seed_t), st))) break;
+        const uint64_t mbase = h_mk.size();
+        h_mk.resize(mbase + nmk);
+        if (nmk && (rc = d2h_result(h_mk.data() + mbase, dmk.p, nmk * 8, st))) break;
+        if (hipStreamSynchronize(st) != hipSuccess) { rc = RBG_ENODEV; break; }
+        if (mbase)
+            for (uint64_t r = 0; r < recs; ++r) { dst[r].mk_begin += mbase; dst[r].mk_end += mbase; }
+        a = b;
+    }
+    if (!rc) {
+        *mk = static_cast<uint64_t *>(alloc_result(h_mk.size() * 8));
+        if (!*mk) rc = RBG_ENOMEM;
+        else if (!h_mk.empty()) std::memcpy(*mk, h_mk.data(), h_mk.size() * 8);
+    }
+    if (rc) { rbg_free_buffer(h_seeds); return rc; }
+    *seeds = h_seeds;
+    return RBG_OK;
+    });
+}
+
 // ---- greedy seeding (next-row f4) -----------------------------------------------------------------
 
 int rbg_greedy_longest_seed_dev(rbg_index *ix, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t min_length,

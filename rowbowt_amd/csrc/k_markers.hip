@@ -587,6 +587,165 @@ __global__ __launch_bounds__(256) void k_count(const uint64_t *__restrict__ lo, 
         out[i] = hi[i] >= lo[i] ? hi[i] - lo[i] + 1 : 0;  // RowBowt::count, rowbowt.hpp:266-269
 }
 
+// ---- lmem marker seeds on the slot tables: RowBowt::get_markers_lmems (rowbowt.hpp:341-404), one lane per (sequence, end
+// position) -- the walk of k_runs_seeds.hip k_marker_lmems_runs (same records, same rec_off contract) with k_marker_seeds'
+// steps: k-mer gathers where no window query falls inside them, halved down to the failing symbol when they come back empty;
+// the ftab word (K = ftab_k > 0) as K steps from the full range, any miss continuing from the full range with K symbols counted.
+template <typename P>
+__device__ __forceinline__ bool slot_lf1(const DevIndex &ix, const DevSym *s_tab, const uint8_t *s_lut, uint32_t c, uint64_t &lo, uint64_t &hi) {
+    const uint32_t slot = s_lut[c];
+    if (slot == 0xFFu) return false;
+    const DevSym S = slot < static_cast<uint32_t>(kLdsSyms) ? s_tab[slot] : ix.syms[slot];
+    RankAux q;
+    uint64_t c_before, c_upto, bh;
+    rank_pair<P>(S, ix.dense, lo, hi + 1, &c_before, &c_upto, &bh, &q);
+    if (c_upto <= c_before) return false;
+    lo = S.F + c_before;
+    hi = lo + (c_upto - c_before) - 1;
+    return true;
+}
+// the longest k-mer (2..min(cap, ksteps) symbols, all with k-mer tables) ending at byte p: *len = its length (0: none applies)
+template <typename P>
+__device__ __forceinline__ bool slot_lfk(const DevIndex &ix, const DevSym *s_tab, const uint8_t *s_lut2, ByteCursor &rd, uint32_t ksteps, uint32_t M,
+                                         uint64_t p, uint64_t cap, uint32_t *len, uint64_t &lo, uint64_t &hi) {
+    *len = 0;
+    const uint32_t m0 = s_lut2[rd.at(p)];
+    if (m0 == 0xFFu || cap < 2 || ksteps < 2) return false;
+    uint32_t adv = 1, idx = m0, pw = M;
+    const uint32_t lim = static_cast<uint32_t>(cap < ksteps ? cap : ksteps);
+    for (uint32_t t = 1; t < lim; ++t) {
+        const uint32_t mm = s_lut2[rd.at(p - t)];
+        if (mm == 0xFFu) break;
+        idx += mm * pw;
+        pw *= M;
+        adv = t + 1;
+    }
+    if (adv < 2) return false;
+    *len = adv;
+    const uint32_t base = adv == 2 ? kOff2 : adv == 3 ? kOff3 : adv == 4 ? kOff4 : kOff5;
+    const DevSym S = s_tab[base + idx];
+    RankAux q;
+    uint64_t c_before, c_upto, bh;
+    rank_pair<P>(S, ix.dense, lo, hi + 1, &c_before, &c_upto, &bh, &q);
+    if (c_upto <= c_before) return false;
+    lo = S.F + c_before;
+    hi = lo + (c_upto - c_before) - 1;
+    return true;
+}
+
+template <typename P, bool FILL>
+__global__ __launch_bounds__(1024) void k_marker_lmems(const DevIndex ix, const uint8_t *__restrict__ seqs, const uint64_t *__restrict__ off,
+                                                       const uint64_t N, const uint64_t total, const uint64_t wsize, const uint64_t max_range,
+                                                       const uint64_t K, uint64_t *__restrict__ rec_off, uint64_t *__restrict__ seeds,
+                                                       uint64_t *__restrict__ mk, const uint32_t max_k) {
+    __shared__ uint8_t s_lut[256];
+    __shared__ uint8_t s_lut2[256];
+    extern __shared__ __align__(16) unsigned char s_dyn[];
+    DevSym *s_tab = reinterpret_cast<DevSym *>(s_dyn);
+    const uint32_t ksteps = ix.kmer_steps < max_k ? ix.kmer_steps : max_k;
+    stage_tables(ix, s_tab, s_lut, s_lut2, ksteps >= 5);
+    const uint32_t M = ix.nmajor;
+    const bool have_ma = ix.mk_nruns != 0;
+    const uint64_t fhi = ix.n - 1, off0 = off[0], nrec = off[N] - off0;
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    if (!FILL && blockIdx.x == 0 && threadIdx.x == 0) rec_off[0] = 0;
+    for (uint64_t t = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < total; t += stride) {
+        if (t >= nrec) {
+            if (!FILL) rec_off[t + 1] = 0;
+            continue;
+        }
+        uint64_t a = 0, b = N;                            // off[a] - off0 <= t < off[a + 1] - off0
+        while (b - a > 1) {
+            const uint64_t c = (a + b) >> 1;
+            if (off[c] - off0 <= t) a = c; else b = c;
+        }
+        const uint64_t beg = off[a], e = off[a + 1] - beg - (t - (beg - off0));
+        uint64_t lo = 0, hi = fhi, plo = 0, phi = fhi;    // range, prev_range (:343-344, :367-368)
+        uint64_t j = e, window_ei = e, tot = 0;           // the next symbol consumed is q[j-1]
+        const uint64_t mbase = FILL ? rec_off[t] : 0;
+        ByteCursor rd{reinterpret_cast<const uint4 *>(seqs), ~uint64_t(0), make_uint4(0, 0, 0, 0)};
+        auto update_mbuf = [&](uint64_t l, uint64_t h) {  // :356-360
+            if (!have_ma || h - l + 1 > max_range) return;
+            uint64_t src, cnt;
+            if (!marker_query(ix, l, h, &src, &cnt)) return;
+            if (FILL) {
+                uint64_t *d = mk + mbase + tot;
+                for (uint64_t u = 0; u < cnt; ++u) d[u] = ix.mk_vals[src + u];
+            }
+            tot += cnt;
+        };
+        auto on_ok = [&](uint32_t adv) {                  // :392-397
+            j -= adv;
+            if (window_ei - j >= wsize) {
+                update_mbuf(lo, hi);
+                window_ei = j;
+            }
+            plo = lo; phi = hi;
+        };
+        if (K && e >= K) {                                // :369-377: the word q[e-K, e) through search_ftab
+            bool hit = true;
+            for (uint64_t u = e - K; u < e && hit; ++u) {
+                const uint32_t c = rd.at(beg + u);
+                hit = c == 'A' || c == 'C' || c == 'G' || c == 'T';
+            }
+            uint64_t e2 = e;
+            while (hit && e2 > e - K) {
+                const uint64_t p = beg + e2 - 1;
+                uint32_t adv;
+                if (!slot_lfk<P>(ix, s_tab, s_lut2, rd, ksteps, M, p, e2 - (e - K), &adv, lo, hi)) {
+                    if (adv || !slot_lf1<P>(ix, s_tab, s_lut, rd.at(p), lo, hi)) hit = false;
+                    adv = 1;
+                }
+                e2 -= adv;
+            }
+            if (!hit) { lo = 0; hi = fhi; }               // a miss: the full range, the K symbols counted all the same
+            plo = lo; phi = hi;
+            j = e - K;
+        }
+        bool failed = false;
+        while (j > 0 && !failed) {                        // :380-398
+            const uint64_t p = beg + j - 1;
+            const uint64_t dist = j + wsize > window_ei ? j + wsize - window_ei : 1;
+            const uint64_t cap = dist < j ? dist : j;
+            uint32_t len;
+            if (slot_lfk<P>(ix, s_tab, s_lut2, rd, ksteps, M, p, cap, &len, lo, hi)) { on_ok(len); continue; }
+            if (len == 0) {
+                if (slot_lf1<P>(ix, s_tab, s_lut, rd.at(p), lo, hi)) on_ok(1u); else failed = true;
+                continue;
+            }
+            while (len > 1) {                             // the range died inside q[j-len, j): halve until one symbol is left
+                const uint32_t half = len / 2;
+                const uint64_t p2 = beg + j - 1;
+                uint32_t l2;
+                const bool ok2 = half >= 2 ? slot_lfk<P>(ix, s_tab, s_lut2, rd, ksteps, M, p2, half, &l2, lo, hi)
+                                           : slot_lf1<P>(ix, s_tab, s_lut, rd.at(p2), lo, hi);
+                if (ok2) { on_ok(half); len -= half; } else len = half;
+            }
+            failed = true;
+        }
+        uint64_t qs = 0;
+        if (failed) {                                     // q[j-1] empties the range: :384-391
+            if (e - j >= wsize) update_mbuf(plo, phi);
+            lo = plo; hi = phi; qs = j;
+        } else if (e >= wsize) {                          // the whole prefix q[0, e) occurs: :399-402
+            update_mbuf(lo, hi);
+        }
+        if (FILL) {
+            uint64_t *d = seeds + 6 * t;
+            d[0] = lo; d[1] = hi; d[2] = qs; d[3] = e; d[4] = mbase; d[5] = mbase + tot;
+        } else {
+            rec_off[t + 1] = tot;
+        }
+    }
+}
+
+// mk_off[i] = rec_off[off[i] - off[0]], i = 0..N: the markers before sequence i
+__global__ __launch_bounds__(256) void k_lmem_seq_off(const uint64_t *__restrict__ off, const uint64_t N, const uint64_t *__restrict__ rec_off,
+                                                      uint64_t *__restrict__ mk_off) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i <= N; i += stride) mk_off[i] = rec_off[off[i] - off[0]];
+}
+
 }  // namespace
 
 int launch_markers_plan(const DevIndex &ix, const LaunchCfg &cfg, const uint64_t *lo, const uint64_t *hi, uint64_t N,
@@ -722,6 +881,49 @@ int launch_greedy_seed(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *
     if (ix.pos_bytes == 4) RBG_GS(uint32_t); else RBG_GS(uint64_t);
 #undef RBG_GS
     return static_cast<int>(hipGetLastError());
+}
+
+size_t marker_lmems_tmp_bytes(uint64_t total) { return (((total + 1) * 8 + 255) & ~size_t(255)) + scan_tmp_bytes(total); }
+
+static int marker_lmems_walk(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t total, uint64_t wsize,
+                             uint64_t max_range, uint64_t K, uint64_t *rec_off, uint64_t *seeds, uint64_t *mk, bool fill, hipStream_t st) {
+    if (ix.layout == 2) return launch_marker_lmems_runs(ix, cfg, seqs, off, N, total, wsize, max_range, K, rec_off, seeds, mk, fill, st);
+#define RBG_LMS(PT, F)                                                                                                                    \
+    do {                                                                                                                                  \
+        auto kern = k_marker_lmems<PT, F>;                                                                                                \
+        const KmerLaunch L = kmer_launch(ix, cfg, total, kern, 0, kSeedKmerLevel);                                                        \
+        hipLaunchKernelGGL(kern, L.grid, L.block, L.lds, st, ix, seqs, off, N, total, wsize, max_range, K, rec_off, seeds, mk, kSeedKmerLevel); \
+    } while (0)
+    if (ix.pos_bytes == 4) { if (fill) RBG_LMS(uint32_t, true); else RBG_LMS(uint32_t, false); }
+    else { if (fill) RBG_LMS(uint64_t, true); else RBG_LMS(uint64_t, false); }
+#undef RBG_LMS
+    return static_cast<int>(hipGetLastError());
+}
+
+int launch_marker_lmems_plan(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t total,
+                             uint64_t wsize, uint64_t max_range, uint64_t ftab_k, uint64_t *mk_off, void *tmp, size_t tmp_bytes, void *stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (N == 0) return static_cast<int>(hipMemsetAsync(mk_off, 0, 8, st));
+    uint64_t *rec_off = static_cast<uint64_t *>(tmp);
+    const size_t head = ((total + 1) * 8 + 255) & ~size_t(255);
+    int rc;
+    if (total == 0 || ix.mk_nruns == 0) {   // no marker anywhere: no walk needed to know every record's count
+        rc = static_cast<int>(hipMemsetAsync(rec_off, 0, (total + 1) * 8, st));
+    } else {
+        rc = marker_lmems_walk(ix, cfg, seqs, off, N, total, wsize, max_range, ftab_k, rec_off, nullptr, nullptr, false, st);
+        if (!rc) rc = scan_in_place(rec_off + 1, total, static_cast<char *>(tmp) + head, tmp_bytes - head, st);
+    }
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_lmem_seq_off, dim3(grid_for(cfg, N + 1)), dim3(256), 0, st, off, N, rec_off, mk_off);
+    return static_cast<int>(hipGetLastError());
+}
+
+int launch_marker_lmems_fill(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t total,
+                             uint64_t wsize, uint64_t max_range, uint64_t ftab_k, const void *tmp, uint64_t *seeds, uint64_t *mk, void *stream) {
+    if (N == 0 || total == 0) return 0;
+    // (the fill only reads the records' marker offsets the plan left in tmp)
+    return marker_lmems_walk(ix, cfg, seqs, off, N, total, wsize, max_range, ftab_k, static_cast<uint64_t *>(const_cast<void *>(tmp)), seeds, mk, true,
+                             static_cast<hipStream_t>(stream));
 }
 
 int launch_lf(const DevIndex &ix, const LaunchCfg &cfg, const uint64_t *lo, const uint64_t *hi, const uint8_t *sym,

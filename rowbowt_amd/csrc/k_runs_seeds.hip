@@ -657,6 +657,180 @@ __global__ __launch_bounds__(512, sizeof(P) == 8 ? 3 : 4) void k_marker_seeds_ft
     }
 }
 
+// ---- lmem marker seeds: RowBowt::get_markers_lmems (rowbowt.hpp:341-404; rb_markers --ftab --lmem, rb_markers.cpp:402-405) ----------
+// A fresh backward search from every end position e = m, m-1, ..., 1 of a sequence, each leaving exactly one non-empty record
+// (the reference's second call with an empty range after a failed extension carries nothing: rb_markers drops it, the shim
+// replays it).  The work item is (sequence, end position): record t of the batch is end position e = m - k of the sequence i
+// with off[i] - off[0] + k == t.  A wave takes 64 consecutive records -- consecutive end positions of one or a few sequences,
+// whose match lengths differ by about a symbol (without an ftab miss L(e - 1) >= L(e) - 1) -- so its lanes finish together.
+// The first lane of each sequence in the wave stages it (rbg_runs_device.hpp stage_read) and every lane that walks it reads
+// that lane's column.  The K = ftab_k symbols of the ftab word (the tool's ftab, 0 = none) are stepped from the full range
+// without window queries (the ftab part leaves window_ei at e); an absent or non-ACGT word goes on from the FULL range with K
+// symbols counted (search_ftab's miss is {full_range(), 0}, :746-758, so :371-373 is never taken).  The rest of the walk is
+// k_marker_seeds_runs': steps capped at the next window end, an empty k-mer step halved down to the failing symbol.
+// FILL = false: rec_off[t + 1] = markers of record t; FILL = true: record t at seeds + 6 t, its markers at mk + rec_off[t].
+// total: any upper bound on off[N] - off[0] (the grid's size); N >= 1.
+template <typename P, bool FILL>
+__global__ __launch_bounds__(512, 4) void k_marker_lmems_runs(const DevIndex ix, const uint8_t *__restrict__ seqs, const uint64_t *__restrict__ off,
+                                                              const uint64_t N, const uint64_t total, const uint64_t wsize, const uint64_t max_range,
+                                                              const uint64_t K, uint64_t *__restrict__ rec_off, uint64_t *__restrict__ seeds,
+                                                              uint64_t *__restrict__ mk) {
+    RBG_SEED_KERNEL_PROLOGUE(P);
+    RBG_SEED_STAGE_SHARED;
+    const bool have_ma = ix.mk_nruns != 0;
+    const uint64_t fhi = ix.n - 1;
+    const uint64_t off0 = off[0], nrec = off[N] - off0;
+    // the four k-mer symbols are A, C, G, T: a staged word is then ACGT-only, and the device ftab (when its k is K) answers search_ftab
+    const bool acgt = M == 4 && s_lut2['A'] != 0xFFu && s_lut2['C'] != 0xFFu && s_lut2['G'] != 0xFFu && s_lut2['T'] != 0xFFu;
+    lds_u32 *const wave_codes = codes - lane;
+    if (!FILL && blockIdx.x == 0 && threadIdx.x == 0) rec_off[0] = 0;
+    for (uint64_t base = wave_first; base < total; base += stride) {
+        const uint64_t t = base + lane;
+        const bool valid = t < nrec;
+        uint64_t beg = 0, m = 0, k = 0;
+        if (valid) {   // the sequence of record t: off[a] - off0 <= t < off[a + 1] - off0 (an empty sequence is never it)
+            uint64_t a = 0, b = N;
+            while (b - a > 1) {
+                const uint64_t c = (a + b) >> 1;
+                if (off[c] - off0 <= t) a = c; else b = c;
+            }
+            beg = off[a];
+            m = off[a + 1] - beg;
+            k = t - (beg - off0);
+        }
+        const uint64_t e = m - k;
+        bool staged = false;
+        const lds_u32 *col = codes;
+        if (stage_on && __ballot(valid && m > kStageCap) == 0) {
+            // one lane per sequence stages it: lane 0, or the lane of its end position m (k == 0)
+            const bool lead = valid && (lane == 0 || k == 0);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (the previous records' reads of the columns come first)
+            __builtin_amdgcn_wave_barrier();
+            uint32_t nch = 0;
+            const bool bad = lead && stage_read(reinterpret_cast<const uint4 *>(seqs), beg, beg + m, stage_tab, codes, nch);
+            staged = __ballot(bad) == 0;
+            const unsigned long long leads = __ballot(lead) & ((2ull << lane) - 1ull);
+            if (leads) col = wave_codes + (63 - __clzll(leads));
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (other lanes' columns are read from here on)
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+        auto walk = [&](auto staged_tag) __attribute__((always_inline)) {
+        constexpr bool STAGED = decltype(staged_tag)::value;
+        uint64_t lo = 0, hi = fhi, plo = 0, phi = fhi;    // range, prev_range (:343-344, :367-368)
+        uint64_t j = e, window_ei = e, tot = 0;           // the next symbol consumed is q[j-1] (i = e - j of the reference)
+        const uint64_t mbase = (FILL && valid) ? rec_off[t] : 0;
+        bool in_ftab = valid && K && e >= K;              // :369: stepping through the word q[jf, e)
+        const uint64_t jf = in_ftab ? e - K : 0;
+        bool live = valid;
+        uint32_t nlen = 0;
+        uint64_t unused_k = 0;
+        ByteCursor rd{reinterpret_cast<const uint4 *>(seqs), ~uint64_t(0), make_uint4(0, 0, 0, 0)};
+        auto update_mbuf = [&](uint64_t l, uint64_t h) {  // :356-360
+            if (!have_ma || h - l + 1 > max_range) return;
+            uint64_t src, cnt;
+            if (!marker_query(ix, l, h, &src, &cnt)) return;
+            if (FILL) {
+                uint64_t *d = mk + mbase + tot;
+                for (uint64_t u = 0; u < cnt; ++u) d[u] = ix.mk_vals[src + u];
+            }
+            tot += cnt;
+        };
+        auto emit = [&](uint64_t l, uint64_t h, uint64_t qs) {   // fn(range, (qs, e-1), mbuf), :389 / :402
+            if (FILL) {
+                uint64_t *d = seeds + 6 * t;
+                d[0] = l; d[1] = h; d[2] = qs; d[3] = e; d[4] = mbase; d[5] = mbase + tot;
+            } else {
+                rec_off[t + 1] = tot;
+            }
+            live = false;
+        };
+        auto ftab_done = [&](bool hit) {                  // :370-377 (a miss: the full range, K symbols counted)
+            if (!hit) { lo = 0; hi = fhi; }
+            plo = lo; phi = hi;
+            j = jf;
+            in_ftab = false;
+        };
+        auto on_ok = [&](uint32_t adv) {                  // :392-397
+            j -= adv;
+            if (window_ei - j >= wsize) {
+                update_mbuf(lo, hi);
+                window_ei = j;
+            }
+            plo = lo; phi = hi;                           // :382 of the next step
+        };
+        auto on_fail = [&]() {                            // q[j-1] empties the range: :384-391
+            if (e - j >= wsize) update_mbuf(plo, phi);
+            emit(plo, phi, j);
+        };
+        if (in_ftab) {
+            bool word = STAGED && acgt;                   // (staged: every symbol is one of the four)
+            if (!word) {
+                word = true;
+                for (uint64_t u = e - K; u < e; ++u) {
+                    const uint32_t c = rd.at(beg + u);
+                    word = word && (c == 'A' || c == 'C' || c == 'G' || c == 'T');
+                }
+            }
+            if (!word) ftab_done(false);
+            else if (acgt && ix.ftab_k == K &&
+                     (STAGED ? ftab_state_staged<P>(ix, col, static_cast<uint32_t>(m - e), lo, hi, unused_k)
+                             : ftab_state<P>(ix, rd, s_lut2, beg + e - 1, M, lo, hi, unused_k)))
+                ftab_done(true);                          // one gather in the device table (false: not answered there, step it)
+        }
+        while (__ballot(live)) {
+            bool stepping = false;
+            StepPick pick{1u, 0u, 0u, true};
+            while (live && !stepping) {
+                if (!in_ftab && j == 0) {                 // the whole prefix q[0, e) occurs: :399-402
+                    if (e >= wsize) update_mbuf(lo, hi);
+                    emit(lo, hi, 0);
+                    break;
+                }
+                uint64_t cap;
+                if (in_ftab) cap = j - jf;
+                else if (nlen) cap = nlen / 2;
+                else {                                    // symbols that may be consumed before the next window query fires (:393)
+                    const uint64_t dist = j + wsize > window_ei ? j + wsize - window_ei : 1;
+                    cap = dist < j ? dist : j;
+                }
+                pick = STAGED ? pick_step_staged(col, s_mslot, tab_first, static_cast<uint32_t>(m - j), cap, D, DMASK)
+                              : pick_step(rd, s_lut, s_lut2, tab_first, beg + j - 1, cap, D, DMASK, M);
+                if (!pick.ok) {                           // the symbol does not occur in the index
+                    if (in_ftab) ftab_done(false); else on_fail();
+                    nlen = 0;
+                    continue;
+                }
+                stepping = true;
+            }
+            RunStep r;
+            seeds_lf2<P, true, true>(S2, stepping, pick.d, pick.rec, lo, hi + 1, r);
+            if (stepping) {
+                const uint64_t c_inside = r.c_upto - r.c_before;
+                const bool ok = c_inside != 0;
+                if (ok) {
+                    lo = r.F + r.c_before;
+                    hi = lo + c_inside - 1;
+                }
+                if (in_ftab) {
+                    if (!ok) ftab_done(false);
+                    else if ((j -= pick.adv) == jf) ftab_done(true);
+                } else if (nlen == 0) {
+                    if (ok) on_ok(pick.adv);
+                    else if (pick.adv == 1) on_fail();
+                    else nlen = pick.adv;                 // the range died inside q[j-adv, j): halve until one symbol is left
+                } else {
+                    if (ok) { on_ok(pick.adv); nlen -= pick.adv; } else nlen = pick.adv;
+                    if (nlen == 1) { on_fail(); nlen = 0; }   // that symbol is the failing one
+                }
+            }
+        }
+        if (!FILL && !valid && t < total) rec_off[t + 1] = 0;
+        };
+        if (staged) walk(std::true_type{}); else walk(std::false_type{});
+    }
+}
+
 struct SeedLaunch {
     dim3 grid, block;
     size_t lds;
@@ -761,6 +935,22 @@ int launch_marker_seeds_runs(const DevIndex &ix, const LaunchCfg &cfg, const uin
     } while (0)
     if (ix.pos_bytes == 4) RBG_MSR(uint32_t); else RBG_MSR(uint64_t);
 #undef RBG_MSR
+    return static_cast<int>(hipGetLastError());
+}
+
+int launch_marker_lmems_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t total,
+                             uint64_t wsize, uint64_t max_range, uint64_t ftab_k, uint64_t *rec_off, uint64_t *seeds, uint64_t *mk, bool fill,
+                             void *stream) {
+    if (N == 0 || total == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const SeedLaunch L = seed_launch(ix, cfg, total);
+#define RBG_LMR(PT)                                                                                                                          \
+    do {                                                                                                                                     \
+        if (fill) RBG_LAUNCH_SEEDK((k_marker_lmems_runs<PT, true>), seqs, off, N, total, wsize, max_range, ftab_k, rec_off, seeds, mk);     \
+        else RBG_LAUNCH_SEEDK((k_marker_lmems_runs<PT, false>), seqs, off, N, total, wsize, max_range, ftab_k, rec_off, seeds, mk);         \
+    } while (0)
+    if (ix.pos_bytes == 4) RBG_LMR(uint32_t); else RBG_LMR(uint64_t);
+#undef RBG_LMR
     return static_cast<int>(hipGetLastError());
 }
 #undef RBG_LAUNCH_SEEDK

@@ -14,8 +14,11 @@
 // `rb_build -f` makes for this index (checked), and seeding then goes through search_ftab
 // (rowbowt.hpp:430-433, :454-464).
 //
+// --ftab --lmem seeds through get_markers_lmems (rowbowt.hpp:341-404; rbg_get_markers_lmems): one line per end position of
+// each strand, m per strand.  Parity is stdout only: the reference's per-step debug text on stderr is not reproduced.
+// --lmem without --ftab exits 1 with the reference's "ftab must be enabled!" (:346-349).
+//
 // Not carried over (each exits 1 with a message, like the reference does for --overlap):
-//   --lmem      get_markers_lmems (rowbowt.hpp:341-404) prints debugging text per step and is O(m^2)
 //   --fbb/-x    other string type, other index file
 #include <getopt.h>
 #include <zlib.h>
@@ -73,6 +76,8 @@ void print_help() {  // rb_markers.cpp:44-54
     fprintf(stderr, "    --threads          <int>         host threads formatting the output\n");
     fprintf(stderr, "    --heuristic [--best-strand-only] [--min-seed-length <int>] [--read-len <int>]\n");
     fprintf(stderr, "                [--clear-conflicting] [--clear-identical]\n");
+    fprintf(stderr, "    --ftab [--lmem]                  seed through the index's .ftab; --lmem: a longest match from every end position\n");
+    fprintf(stderr, "                                     (stdout as the reference's; its per-step debug text on stderr is not printed)\n");
     fprintf(stderr, "    --gpu <n>                        HIP device ordinal (default 0)\n");
     fprintf(stderr, "    --batch <n>                      reads per GPU batch (default 262144)\n");
     fprintf(stderr, "    <input_prefix>                   index prefix\n");
@@ -123,8 +128,8 @@ RbMarkersArgs parse_args(int argc, char **argv) {  // rb_markers.cpp:56-134
         fprintf(stderr, "overlapped seeds currently broken\n");
         exit(1);
     }
-    if (args.lmem) {  // without an ftab the reference stops at rowbowt.hpp:346-349
-        fprintf(stderr, args.ftab ? "rb_markers: --lmem is not built in this engine\n" : "ftab must be enabled!\n");
+    if (args.lmem && !args.ftab) {  // without an ftab the reference stops at rowbowt.hpp:346-349
+        fprintf(stderr, "ftab must be enabled!\n");
         exit(1);
     }
     if (args.fbb) {
@@ -138,6 +143,7 @@ RbMarkersArgs parse_args(int argc, char **argv) {  // rb_markers.cpp:56-134
     args.inpre = argv[optind++];
     args.fastq_fname = argv[optind++];
     if (args.batch == 0) args.batch = 1;
+    if (args.lmem) args.batch = std::min<uint64_t>(args.batch, 16384);   // 2 x 16384 strands of 150 bp: 236 MB of records per batch
     if (args.threads == 0) args.threads = 1;
     return args;
 }
@@ -374,8 +380,10 @@ void query_batch(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args, const Bat
     slot.r.seeds = nullptr;
     slot.r.mk = nullptr;
     slot.r.seed_off.resize(2 * N + 1);
-    slot.rc = rbg_get_markers_greedy_seeding(rb.handle(), reinterpret_cast<const uint8_t *>(slot.seqs.data()), slot.off.data(), 2 * N, args.wsize,
-                                             args.max_range, ft_k, slot.r.seed_off.data(), &slot.r.seeds, &slot.r.mk);
+    // (--lmem: one record per end position of every strand, the same records and the same callback logic afterwards)
+    auto *call = args.lmem ? rbg_get_markers_lmems : rbg_get_markers_greedy_seeding;
+    slot.rc = call(rb.handle(), reinterpret_cast<const uint8_t *>(slot.seqs.data()), slot.off.data(), 2 * N, args.wsize, args.max_range, ft_k,
+                   slot.r.seed_off.data(), &slot.r.seeds, &slot.r.mk);
     slot.t_strands = std::chrono::duration<double>(t1 - t0).count();
     slot.t_query = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
 }
@@ -384,7 +392,7 @@ void query_batch(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args, const Bat
 void format_batch(const RbMarkersArgs &args, const BatchView &b, SeedSlot &slot, RandomBoolGenerator &booler, std::vector<rbg_cli::TextBuf> &pieces,
                   size_t &used) {
     const size_t N = b.size();
-    rbwt::detail::check(slot.rc, "rbg_get_markers_greedy_seeding");
+    rbwt::detail::check(slot.rc, args.lmem ? "rbg_get_markers_lmems" : "rbg_get_markers_greedy_seeding");
     const BatchSeeds &r = slot.r;
     const auto t2 = std::chrono::steady_clock::now();
     std::vector<uint8_t> first_fwd(N, 1);
@@ -428,7 +436,9 @@ int main(int argc, char **argv) {
 
     start = std::chrono::high_resolution_clock::now();
     InputSource input;  // :568-572 (the file is scanned in place, window by window: cli_input.hpp)
-    if (!input.open(args.fastq_fname, static_cast<unsigned>(std::max<uint64_t>(1, args.threads)), uint64_t(256) << 20)) {
+    // --lmem prints m lines per strand (about 60 times the greedy text per read): 8 MB windows keep a window's text near 0.5 GB
+    const uint64_t window = args.lmem ? uint64_t(8) << 20 : uint64_t(256) << 20;
+    if (!input.open(args.fastq_fname, static_cast<unsigned>(std::max<uint64_t>(1, args.threads)), window)) {
         fprintf(stderr, "invalid file\n");
         exit(1);
     }
@@ -448,7 +458,7 @@ int main(int argc, char **argv) {
         used = 0;
         {   // two stages over the window's batches: batch j + 1 is searched while batch j's seeds are sorted and printed
             const uint64_t ft_k = rb.ftab_k();
-            if (ft_k)
+            if (ft_k && !args.lmem)   // (lmem starts a suffix shorter than k from the full range: no substr past the end, :369)
                 for (size_t i = 0; i < cur.size(); ++i)
                     if (cur.recs.seq_len[i] < ft_k) {  // the reference dies in std::string::substr (rowbowt.hpp:431)
                         fprintf(stderr, "ERROR: read shorter than the ftab k-mer size (%llu)\n", static_cast<unsigned long long>(ft_k));

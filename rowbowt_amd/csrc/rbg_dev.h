@@ -486,6 +486,10 @@ int launch_greedy_seed_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint
 int launch_marker_seeds_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t wsize,
                              uint64_t max_range, uint64_t *seed_cnt, uint64_t *mk_cnt, const uint64_t *seed_off, const uint64_t *mk_off,
                              uint64_t *seeds, uint64_t *mk, bool fill, void *stream, const SeedLog &lg, uint64_t ftab_k = 0 /*format 2: rb_markers --ftab*/);
+// lmem marker seeds (get_markers_lmems): one record per (sequence, end position); fill == false writes rec_off[t + 1] = markers of record t
+int launch_marker_lmems_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t total,
+                             uint64_t wsize, uint64_t max_range, uint64_t ftab_k, uint64_t *rec_off, uint64_t *seeds, uint64_t *mk, bool fill,
+                             void *stream);
 int launch_find_range_stats(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N,
                             uint64_t *lo, uint64_t *hi, uint64_t *ssamp /*nullable*/, unsigned long long *stats /*kStatSearchN*/,
                             void *stream);
@@ -554,6 +558,13 @@ int launch_marker_seeds_plan(const DevIndex &ix, const LaunchCfg &cfg, const uin
 int launch_marker_seeds_fill(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N,
                              uint64_t wsize, uint64_t max_range, uint64_t ftab_k, const uint64_t *seed_off, const uint64_t *mk_off,
                              uint64_t *seeds, uint64_t *mk, void *stream, void *log = nullptr, size_t log_bytes = 0, unsigned long long *stats = nullptr);
+// lmem marker seeds, two phases (total: any upper bound on off[N] - off[0]).  tmp (marker_lmems_tmp_bytes(total)) holds the
+// records' marker offsets from the plan to the fill: the fill needs the plan's tmp untouched
+size_t marker_lmems_tmp_bytes(uint64_t total);
+int launch_marker_lmems_plan(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t total,
+                             uint64_t wsize, uint64_t max_range, uint64_t ftab_k, uint64_t *mk_off, void *tmp, size_t tmp_bytes, void *stream);
+int launch_marker_lmems_fill(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t total,
+                             uint64_t wsize, uint64_t max_range, uint64_t ftab_k, const void *tmp, uint64_t *seeds, uint64_t *mk, void *stream);
 int launch_greedy_seed(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N,
                        uint64_t min_length, uint64_t *lo, uint64_t *hi, uint64_t *qs, uint64_t *qe, uint64_t *ss, void *stream, unsigned long long *stats = nullptr);
 int launch_markers_plan(const DevIndex &ix, const LaunchCfg &cfg, const uint64_t *lo, const uint64_t *hi, uint64_t N,

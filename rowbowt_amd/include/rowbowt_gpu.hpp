@@ -14,7 +14,8 @@
 // would not survive (no GPU, HIP failure) also goes to stderr + exit(1).
 //
 // Also offered (next-row f4): find_locs_greedy_seeding, get_markers_greedy_seeding (with and without
-// a loaded ftab).  Not implemented here: lmem and overlap seeding.
+// a loaded ftab), get_markers_lmems (with a loaded ftab, as in the reference).  Not implemented here: overlap seeding
+// (the reference refuses it itself).
 #pragma once
 
 #include <cstdint>
@@ -223,6 +224,36 @@ class RowBowt {
             const rbg_marker_seed_t &d = seeds[s];
             fn(range_t(d.lo, d.hi), std::make_pair(static_cast<size_t>(d.qstart), static_cast<size_t>(d.qend - 1)),
                std::vector<MarkerT>(mk.p + d.mk_begin, mk.p + d.mk_end));
+        }
+    }
+
+    // rowbowt.hpp:341-404: fn(range, (q.first, q.second), mbuf) for every end position m, m-1, ..., 1 of the query, exactly as
+    // the reference calls it.  A failed extension is reported twice there: fn(prev_range, q, mbuf) (:389), then, after the
+    // break, fn(range, q, mbuf) (:402) with LF's empty range and the cleared mbuf.  The second call is replayed here with the
+    // library's in-band empty range {1, 0} (LF's own empty pair depends on the ranks where the search died).  The per-step
+    // debug text the reference prints to stderr is not reproduced.
+    template <typename F>
+    void get_markers_lmems(const std::string query, uint64_t wsize, uint64_t max_range, F fn) const {
+        if (disable_ft_ || !ft_k_) {  // :346-349
+            std::cerr << "ftab must be enabled!" << std::endl;
+            std::exit(1);
+        }
+        if (ft_k_ - 1 > wsize) {  // :350-353
+            std::cerr << "ERROR: wsize cannot be greater than or equal to ftab k size. please rebuild ftab with smaller k\n";
+            std::exit(1);
+        }
+        const uint64_t off[2] = {0, query.size()};
+        uint64_t seed_off[2];
+        rbg_marker_seed_t *seeds = nullptr;
+        detail::LibBuf mk;
+        detail::check(rbg_get_markers_lmems(ix_.get(), reinterpret_cast<const uint8_t *>(query.data()), off, 1, wsize, max_range, ft_k_,
+                                            seed_off, &seeds, &mk.p), "rbg_get_markers_lmems");
+        std::unique_ptr<rbg_marker_seed_t, void (*)(void *)> hold(seeds, rbg_free_buffer);
+        for (uint64_t s = 0; s < seed_off[1]; ++s) {
+            const rbg_marker_seed_t &d = seeds[s];
+            const auto q = std::make_pair(static_cast<size_t>(d.qstart), static_cast<size_t>(d.qend - 1));
+            fn(range_t(d.lo, d.hi), q, std::vector<MarkerT>(mk.p + d.mk_begin, mk.p + d.mk_end));
+            if (d.qstart > 0) fn(range_t(1, 0), q, std::vector<MarkerT>());   // the failed extension's second call (:402)
         }
     }
 
