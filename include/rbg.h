@@ -303,6 +303,38 @@ int rbg_get_markers_lmems(rbg_index *, const uint8_t *seqs, const uint64_t *off,
  * with no seed of at least min_length gets rn={1,0}, qstart=qend=ssamp=0. */
 int rbg_greedy_longest_seed(rbg_index *, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t min_length,
                             uint64_t *lo, uint64_t *hi, uint64_t *qstart, uint64_t *qend, uint64_t *ssamp);
+/* The whole seed list of RowBowt::get_seeds_greedy_w_sample(query, min_length) (rowbowt.hpp:222-256; flags = RBG_SEEDS_W_SAMPLE) or
+ * RowBowt::get_seeds_greedy(query, min_length, lfdata) (:191-215; flags = 0): every greedy seed of every read as LFData {rn, qstart,
+ * qend, ssamp}, where rbg_greedy_longest_seed keeps one.  seed_off[N+1]: read i owns records [seed_off[i], seed_off[i+1]), in the
+ * reference's order (the first record is the rightmost seed).  *seeds is ONE block of 5 * seed_off[N] u64, five arrays back to back:
+ * lo | hi | qstart | qend | ssamp (release with rbg_free_buffer) -- arrays and not records, because lo / hi / ssamp are what
+ * rbg_locate_plan_dev / rbg_locate_order_dev take and qstart is the d_sub of rbg_locate_fill_offset_dev (locate_from_longest_seed's
+ * "minus qstart", :684-686).  Quirks kept:
+ *   1. with the sample the last record (qstart = 0) is pushed only if ei >= min_length (:252); without it, always, whatever its
+ *      length (:211).
+ *   2. without the sample the reference leaves ssamp uninitialised (LFData's three-argument constructor, :148-152, :163): here it is
+ *      0.  flags = 0 works on an index loaded without a toehold SA.
+ *   3. with the sample and no toehold SA every list is empty (:225) -- RBG_OK, not RBG_ENOTLOADED.
+ *   4. pk is not reset when a seed fails (:241-244): a zero-length seed (recorded only when min_length == 0, e.g. at the second of
+ *      two N) carries the toehold of the last successful step anywhere earlier in that read, or 2^64 - 1 if there was none; its
+ *      range is the full range.
+ *   5. an empty read gives one record {full range, 0, 0, 2^64 - 1} when min_length == 0 (without the sample: always, ssamp 0), and
+ *      no record otherwise.
+ *   6. any byte that does not occur in the BWT (N, lower case) ends a seed and is skipped. */
+#define RBG_SEEDS_W_SAMPLE 1u
+int rbg_get_seeds_greedy(rbg_index *, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t min_length, uint32_t flags,
+                         uint64_t *seed_off, uint64_t **seeds);
+/* RowBowt::find_range_w_toehold_chkpnts(query, wsize), rowbowt.hpp:575-606: one backward search per read with a record {rn, qstart,
+ * qend, ssamp} after step i = wsize, 2 wsize, ... <= m - 1 (step i consumes q[m-i-1]; the test of :592).  Such a record is labelled
+ * qstart = m - i, qend = the previous label (m at first), but its range and toehold are those of q[m-i-1, m): one symbol more than
+ * the label says -- {rn, ssamp} of a record with qstart = s > 0 is rbg_find_range_w_toehold(q[s-1:]).  A final record {qstart 0,
+ * qend m} with the whole read's range follows when (m - 1) % wsize != 0.  A read that occurs therefore has floor((m - 1) / wsize)
+ * records, plus one if (m - 1) % wsize != 0 (m >= 1; a one-symbol read has none); a read that does not occur has none (:588-590).
+ * An empty read: no step, m - 1 wraps -- one record {full range, 0, 0, last run sample} if (2^64 - 1) % wsize != 0, none otherwise
+ * (wsize 1, 3, 5, 15, 17, ...).  wsize == 0 is RBG_EARG (the reference computes % 0).  Without a toehold SA every list is empty
+ * (:579).  Output as rbg_get_seeds_greedy: seed_off[N+1] and one block of 5 * seed_off[N] u64 (lo | hi | qstart | qend | ssamp). */
+int rbg_find_range_w_toehold_chkpnts(rbg_index *, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t wsize,
+                                     uint64_t *seed_off, uint64_t **seeds);
 /* RowBowt::find_locs_greedy_seeding(s, min_length, max_hits), rowbowt.hpp:633-657 (== get_seeds +
  * locate_from_longest_seed :664-685): locations of the longest seed, each minus the seed's qstart. */
 int rbg_find_locs_greedy_seeding(rbg_index *, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t min_length,
@@ -429,6 +461,30 @@ int rbg_marker_lmems_plan_dev(rbg_index *, const uint8_t *d_seqs, const uint64_t
                               uint64_t max_range, uint64_t ftab_k, uint64_t *d_mk_off, void *d_tmp, size_t tmp_bytes, void *stream);
 int rbg_marker_lmems_fill_dev(rbg_index *, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t total, uint64_t wsize,
                               uint64_t max_range, uint64_t ftab_k, const void *d_tmp, rbg_marker_seed_t *d_seeds, uint64_t *d_mk, void *stream);
+/* greedy seed lists (rbg_get_seeds_greedy), two-phase.  The plan walks the reads without any toehold state and writes
+ * d_seed_off[N+1], the exclusive scan of the seeds per read (d_tmp: rbg_greedy_seeds_tmp_bytes(N) bytes); the fill walks them again
+ * (same min_length and flags) and writes record r of read i at index d_seed_off[i] + r of five arrays of d_seed_off[N] entries
+ * each; d_ssamp may be NULL without RBG_SEEDS_W_SAMPLE (else it is written 0).  The arrays go unchanged into rbg_locate_plan_dev
+ * (d_lo, d_hi), rbg_locate_order_dev (d_ssamp) and rbg_locate_fill_offset_dev (d_sub = d_qstart): "locate every seed of every
+ * read" is these two calls and those.  A zero-length seed (min_length == 0) has the full range: give it to K3 with care. */
+size_t rbg_greedy_seeds_tmp_bytes(uint64_t N);
+int rbg_greedy_seeds_plan_dev(rbg_index *, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t min_length, uint32_t flags,
+                              uint64_t *d_seed_off, void *d_tmp, size_t tmp_bytes, void *stream);
+int rbg_greedy_seeds_fill_dev(rbg_index *, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t min_length, uint32_t flags,
+                              const uint64_t *d_seed_off, uint64_t *d_lo, uint64_t *d_hi, uint64_t *d_qstart, uint64_t *d_qend,
+                              uint64_t *d_ssamp, void *stream);
+/* toehold checkpoints (rbg_find_range_w_toehold_chkpnts) on the device.  The records a read can have are a function of its length
+ * and wsize alone, so there is no count walk: rbg_toehold_chkpnts_slots_dev writes d_slot_off[N+1], the exclusive scan of those
+ * fixed slots (from d_off alone; d_tmp: rbg_toehold_chkpnts_tmp_bytes(N) bytes), and the one walk writes record r of read i at index
+ * d_slot_off[i] + r of five arrays of d_slot_off[N] entries each, and d_cnt[i] = 0 (the read does not occur: its slots hold nothing
+ * of use) or d_slot_off[i+1] - d_slot_off[i].  The host call compacts; a device caller skips the slots of reads with d_cnt[i] == 0.
+ * RBG_ENOTLOADED without a toehold SA (the host call answers empty lists there); wsize == 0: RBG_EARG. */
+size_t rbg_toehold_chkpnts_tmp_bytes(uint64_t N);
+int rbg_toehold_chkpnts_slots_dev(rbg_index *, const uint64_t *d_off, uint64_t N, uint64_t wsize, uint64_t *d_slot_off, void *d_tmp,
+                                  size_t tmp_bytes, void *stream);
+int rbg_find_range_w_toehold_chkpnts_dev(rbg_index *, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t wsize,
+                                         const uint64_t *d_slot_off, uint64_t *d_cnt, uint64_t *d_lo, uint64_t *d_hi,
+                                         uint64_t *d_qstart, uint64_t *d_qend, uint64_t *d_ssamp, void *stream);
 /* markers, same two-phase shape */
 int rbg_markers_plan_dev(rbg_index *, const uint64_t *d_lo, const uint64_t *d_hi, uint64_t N,
                          uint64_t *d_mk_off, void *d_tmp, size_t tmp_bytes, void *stream);

@@ -26,6 +26,7 @@ OPT_JUMP_K = 19          # the jump table (rbg_jump_info): 0 = off, -1 = automat
 ABI_VERSION = 3          # include/rbg.h RBG_ABI_VERSION this binding is written against
 MAX_KMER_DEPTH = 8       # RBG_OPT_KMER_STEPS / the depth arrays of Info and LayoutInfo
 LAYOUT_AUTO, LAYOUT_SLOTS, LAYOUT_RUNS, LAYOUT_PREFER_SLOTS = 0, 1, 2, 3
+SEEDS_W_SAMPLE = 1   # RBG_SEEDS_W_SAMPLE: get_seeds_greedy_w_sample (0: get_seeds_greedy)
 (ARR_RUN_HEADS, ARR_RUN_START, ARR_SAMPLES_LAST, ARR_PRED_POS, ARR_PHI_BASE,
  ARR_MARKER_START, ARR_MARKER_END, ARR_MARKER_OFF, ARR_MARKER_VALS) = range(9)
 
@@ -154,6 +155,14 @@ _PROTOS = [
     ("rbg_marker_lmems_tmp_bytes", C.c_size_t, [U64, U64]),
     ("rbg_marker_lmems_plan_dev", C.c_int, [VP, VP, VP, U64, U64, U64, U64, U64, VP, VP, C.c_size_t, VP]),
     ("rbg_marker_lmems_fill_dev", C.c_int, [VP, VP, VP, U64, U64, U64, U64, U64, VP, VP, VP, VP]),
+    ("rbg_get_seeds_greedy", C.c_int, [VP, VP, VP, U64, U64, C.c_uint32, VP, C.POINTER(VP)]),
+    ("rbg_greedy_seeds_tmp_bytes", C.c_size_t, [U64]),
+    ("rbg_greedy_seeds_plan_dev", C.c_int, [VP, VP, VP, U64, U64, C.c_uint32, VP, VP, C.c_size_t, VP]),
+    ("rbg_greedy_seeds_fill_dev", C.c_int, [VP, VP, VP, U64, U64, C.c_uint32, VP, VP, VP, VP, VP, VP, VP]),
+    ("rbg_find_range_w_toehold_chkpnts", C.c_int, [VP, VP, VP, U64, U64, VP, C.POINTER(VP)]),
+    ("rbg_toehold_chkpnts_tmp_bytes", C.c_size_t, [U64]),
+    ("rbg_toehold_chkpnts_slots_dev", C.c_int, [VP, VP, U64, U64, VP, VP, C.c_size_t, VP]),
+    ("rbg_find_range_w_toehold_chkpnts_dev", C.c_int, [VP, VP, VP, U64, U64, VP, VP, VP, VP, VP, VP, VP, VP]),
     ("rbg_set_default_option", C.c_int, [C.c_int, C.c_int64]),
     ("rbg_get_default_option", C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
 ]
@@ -474,6 +483,31 @@ class RowBowt:
         seeds = _take(ps, 6 * S).reshape(S, 6)
         nmk = int(seeds[-1, 5]) if S else 0
         return seed_off, seeds, _take(pm, nmk)
+
+    def _seed_arrays(self, seed_off, ptr):
+        S = int(seed_off[-1])
+        a = _take(ptr, 5 * S).reshape(5, S)
+        return (seed_off,) + tuple(a[t] for t in range(5))
+
+    def get_seeds_greedy(self, seqs, off, min_length, w_sample=True):
+        """RowBowt::get_seeds_greedy_w_sample (rowbowt.hpp:222-256) or, w_sample=False, get_seeds_greedy (:191-215): every greedy
+        seed of every read, the rightmost first -> (seed_off[N+1], lo, hi, qstart, qend, ssamp), five arrays of seed_off[N]"""
+        N = len(off) - 1
+        seed_off = np.zeros(N + 1, np.uint64)
+        ptr = VP()
+        _check(self.L.rbg_get_seeds_greedy(self.h, _p(seqs), _p(off), N, min_length, SEEDS_W_SAMPLE if w_sample else 0, _p(seed_off),
+                                           C.byref(ptr)), "rbg_get_seeds_greedy")
+        return self._seed_arrays(seed_off, ptr)
+
+    def find_range_w_toehold_chkpnts(self, seqs, off, wsize):
+        """RowBowt::find_range_w_toehold_chkpnts (rowbowt.hpp:575-606): a record every wsize steps of each read's backward search
+        and the whole read's at the end -> (seed_off[N+1], lo, hi, qstart, qend, ssamp); a read that does not occur has none"""
+        N = len(off) - 1
+        seed_off = np.zeros(N + 1, np.uint64)
+        ptr = VP()
+        _check(self.L.rbg_find_range_w_toehold_chkpnts(self.h, _p(seqs), _p(off), N, wsize, _p(seed_off), C.byref(ptr)),
+               "rbg_find_range_w_toehold_chkpnts")
+        return self._seed_arrays(seed_off, ptr)
 
     def greedy_longest_seed(self, seqs, off, min_length):
         """get_seeds_greedy_w_sample (rowbowt.hpp:222-256) -> the seed locate_from_longest_seed picks (:669-677)"""

@@ -349,6 +349,163 @@ int rbg_get_markers_lmems(rbg_index *ix, const uint8_t *seqs, const uint64_t *of
     });
 }
 
+// ---- greedy seed lists (get_seeds_greedy :191-215, get_seeds_greedy_w_sample :222-256) and toehold checkpoints (:575-606) -------
+
+size_t rbg_greedy_seeds_tmp_bytes(uint64_t N) { return scan_tmp_bytes(N); }
+
+int rbg_greedy_seeds_plan_dev(rbg_index *ix, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t min_length, uint32_t flags,
+                              uint64_t *d_seed_off, void *d_tmp, size_t tmp_bytes, void *stream) {
+    return guarded([&]() -> int {
+    if (!queryable(ix)) return RBG_ENODEV;
+    if ((flags & ~RBG_SEEDS_W_SAMPLE) || !d_seed_off || (N && (!d_seqs || !d_off))) return RBG_EARG;
+    if (reinterpret_cast<uintptr_t>(d_seqs) & 15) return RBG_EARG;
+    if (tmp_bytes < scan_tmp_bytes(N) || (N && !d_tmp)) return RBG_EARG;
+    const bool w_sample = (flags & RBG_SEEDS_W_SAMPLE) != 0;
+    if (w_sample && !ix->H().has_tsa)   // rowbowt.hpp:225: every list is empty
+        return hipMemsetAsync(d_seed_off, 0, (N + 1) * 8, static_cast<hipStream_t>(stream)) == hipSuccess ? RBG_OK : RBG_ENODEV;
+    return launch_greedy_seeds_plan(ix->dev, ix->cfg, d_seqs, d_off, N, min_length, w_sample, d_seed_off, d_tmp, tmp_bytes, stream) ? RBG_ENODEV : RBG_OK;
+    });
+}
+
+int rbg_greedy_seeds_fill_dev(rbg_index *ix, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t min_length, uint32_t flags,
+                              const uint64_t *d_seed_off, uint64_t *d_lo, uint64_t *d_hi, uint64_t *d_qstart, uint64_t *d_qend,
+                              uint64_t *d_ssamp, void *stream) {
+    return guarded([&]() -> int {
+    if (!queryable(ix)) return RBG_ENODEV;
+    const bool w_sample = (flags & RBG_SEEDS_W_SAMPLE) != 0;
+    if ((flags & ~RBG_SEEDS_W_SAMPLE) || !d_seed_off || (N && (!d_seqs || !d_off))) return RBG_EARG;
+    if (reinterpret_cast<uintptr_t>(d_seqs) & 15) return RBG_EARG;
+    if (w_sample && !ix->H().has_tsa) return RBG_OK;   // (the plan left every list empty)
+    if (N && (!d_lo || !d_hi || !d_qstart || !d_qend || (w_sample && !d_ssamp))) return RBG_EARG;
+    return launch_greedy_seeds_fill(ix->dev, ix->cfg, d_seqs, d_off, N, min_length, w_sample, d_seed_off, d_lo, d_hi, d_qstart, d_qend, d_ssamp, stream)
+               ? RBG_ENODEV : RBG_OK;
+    });
+}
+
+int rbg_get_seeds_greedy(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t min_length, uint32_t flags,
+                         uint64_t *seed_off, uint64_t **seeds) {
+    return guarded([&]() -> int {
+    if (!seed_off || !seeds) return RBG_EARG;
+    *seeds = nullptr;
+    if (!queryable(ix)) return RBG_ENODEV;
+    if ((flags & ~RBG_SEEDS_W_SAMPLE) || (N && !off)) return RBG_EARG;
+    int rc = check_offsets(off, N);
+    if (rc) return rc;
+    const bool w_sample = (flags & RBG_SEEDS_W_SAMPLE) != 0;
+    if (w_sample && !ix->H().has_tsa) {   // rowbowt.hpp:225
+        std::fill(seed_off, seed_off + N + 1, uint64_t(0));
+        *seeds = static_cast<uint64_t *>(alloc_result(0));
+        return *seeds ? RBG_OK : RBG_ENOMEM;
+    }
+    DeviceScope scope(ix->device);
+    if (scope.rc) return scope.rc;
+    hipStream_t st = hipStreamPerThread;
+    ReadBatch rb;
+    if ((rc = rb.stage(seqs, off, N, st))) return rc;
+    DevBuf dsoff, dtmp, dout;
+    const size_t tmp_bytes = scan_tmp_bytes(N);
+    if ((rc = dsoff.alloc((N + 1) * 8)) || (rc = dtmp.alloc(tmp_bytes))) return rc;
+    if (launch_greedy_seeds_plan(ix->dev, ix->cfg, rb.seqs.as<uint8_t>(), rb.off.as<uint64_t>(), N, min_length, w_sample, dsoff.as<uint64_t>(), dtmp.p,
+                                 tmp_bytes, st))
+        return RBG_ENODEV;
+    HIP_TRY(hipMemcpyAsync(seed_off, dsoff.p, (N + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t total = seed_off[N];
+    auto *h = static_cast<uint64_t *>(alloc_result(total * 40));
+    if (!h) return RBG_ENOMEM;
+    if (total) {
+        if (!(rc = dout.alloc(total * 40))) {
+            uint64_t *d = dout.as<uint64_t>();
+            if (launch_greedy_seeds_fill(ix->dev, ix->cfg, rb.seqs.as<uint8_t>(), rb.off.as<uint64_t>(), N, min_length, w_sample, dsoff.as<uint64_t>(), d,
+                                         d + total, d + 2 * total, d + 3 * total, d + 4 * total, st))
+                rc = RBG_ENODEV;
+            if (!rc) rc = d2h_result(h, dout.p, total * 40, st);
+        }
+    }
+    if (rc) { rbg_free_buffer(h); return rc; }
+    *seeds = h;
+    return RBG_OK;
+    });
+}
+
+size_t rbg_toehold_chkpnts_tmp_bytes(uint64_t N) { return scan_tmp_bytes(N); }
+
+int rbg_toehold_chkpnts_slots_dev(rbg_index *ix, const uint64_t *d_off, uint64_t N, uint64_t wsize, uint64_t *d_slot_off, void *d_tmp,
+                                  size_t tmp_bytes, void *stream) {
+    return guarded([&]() -> int {
+    if (!queryable(ix)) return RBG_ENODEV;
+    if (wsize == 0 || !d_slot_off || (N && !d_off)) return RBG_EARG;
+    if (tmp_bytes < scan_tmp_bytes(N) || (N && !d_tmp)) return RBG_EARG;
+    return launch_toehold_chkpnts_slots(ix->cfg, d_off, N, wsize, d_slot_off, d_tmp, tmp_bytes, stream) ? RBG_ENODEV : RBG_OK;
+    });
+}
+
+int rbg_find_range_w_toehold_chkpnts_dev(rbg_index *ix, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t wsize,
+                                         const uint64_t *d_slot_off, uint64_t *d_cnt, uint64_t *d_lo, uint64_t *d_hi, uint64_t *d_qstart,
+                                         uint64_t *d_qend, uint64_t *d_ssamp, void *stream) {
+    return guarded([&]() -> int {
+    if (!queryable(ix)) return RBG_ENODEV;
+    if (!ix->H().has_tsa) return RBG_ENOTLOADED;
+    if (wsize == 0) return RBG_EARG;
+    if (N && (!d_seqs || !d_off || !d_slot_off || !d_cnt || !d_lo || !d_hi || !d_qstart || !d_qend || !d_ssamp)) return RBG_EARG;
+    if (reinterpret_cast<uintptr_t>(d_seqs) & 15) return RBG_EARG;
+    return launch_toehold_chkpnts(ix->dev, ix->cfg, d_seqs, d_off, N, wsize, d_slot_off, d_cnt, d_lo, d_hi, d_qstart, d_qend, d_ssamp, stream)
+               ? RBG_ENODEV : RBG_OK;
+    });
+}
+
+int rbg_find_range_w_toehold_chkpnts(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t wsize, uint64_t *seed_off,
+                                     uint64_t **seeds) {
+    return guarded([&]() -> int {
+    if (!seed_off || !seeds) return RBG_EARG;
+    *seeds = nullptr;
+    if (!queryable(ix)) return RBG_ENODEV;
+    if (wsize == 0 || (N && !off)) return RBG_EARG;
+    int rc = check_offsets(off, N);
+    if (rc) return rc;
+    std::fill(seed_off, seed_off + N + 1, uint64_t(0));
+    if (!ix->H().has_tsa || N == 0) {   // rowbowt.hpp:579
+        *seeds = static_cast<uint64_t *>(alloc_result(0));
+        return *seeds ? RBG_OK : RBG_ENOMEM;
+    }
+    DeviceScope scope(ix->device);
+    if (scope.rc) return scope.rc;
+    hipStream_t st = hipStreamPerThread;
+    ReadBatch rb;
+    if ((rc = rb.stage(seqs, off, N, st))) return rc;
+    DevBuf dsoff, dcnt, dtmp, dout;
+    const size_t tmp_bytes = scan_tmp_bytes(N);
+    if ((rc = dsoff.alloc((N + 1) * 8)) || (rc = dcnt.alloc(N * 8)) || (rc = dtmp.alloc(tmp_bytes))) return rc;
+    if (launch_toehold_chkpnts_slots(ix->cfg, rb.off.as<uint64_t>(), N, wsize, dsoff.as<uint64_t>(), dtmp.p, tmp_bytes, st)) return RBG_ENODEV;
+    std::vector<uint64_t> slot_off(N + 1), cnt(N);
+    HIP_TRY(hipMemcpyAsync(slot_off.data(), dsoff.p, (N + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t slots = slot_off[N];
+    std::vector<uint64_t> fixed(slots * 5);
+    if (slots) {
+        if ((rc = dout.alloc(slots * 40))) return rc;
+        uint64_t *d = dout.as<uint64_t>();
+        if (launch_toehold_chkpnts(ix->dev, ix->cfg, rb.seqs.as<uint8_t>(), rb.off.as<uint64_t>(), N, wsize, dsoff.as<uint64_t>(), dcnt.as<uint64_t>(), d,
+                                   d + slots, d + 2 * slots, d + 3 * slots, d + 4 * slots, st))
+            return RBG_ENODEV;
+        HIP_TRY(hipMemcpyAsync(cnt.data(), dcnt.p, N * 8, hipMemcpyDeviceToHost, st));
+        if ((rc = d2h_result(fixed.data(), dout.p, slots * 40, st))) return rc;
+    }
+    // compact: the slots of the reads that occur, in read order
+    for (uint64_t i = 0; i < N; ++i) seed_off[i + 1] = seed_off[i] + (slots ? cnt[i] : 0);
+    const uint64_t total = seed_off[N];
+    auto *h = static_cast<uint64_t *>(alloc_result(total * 40));
+    if (!h) return RBG_ENOMEM;
+    for (uint64_t i = 0; i < N; ++i) {
+        const uint64_t c = seed_off[i + 1] - seed_off[i];
+        for (int a = 0; a < 5; ++a)
+            std::copy_n(fixed.data() + a * slots + slot_off[i], c, h + a * total + seed_off[i]);
+    }
+    *seeds = h;
+    return RBG_OK;
+    });
+}
+
 // ---- greedy seeding (next-row f4) -----------------------------------------------------------------
 
 int rbg_greedy_longest_seed_dev(rbg_index *ix, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t min_length,

@@ -255,6 +255,221 @@ __global__ __launch_bounds__(1024) void k_greedy_seed(const DevIndex ix, const u
     }
 }
 
+// ---- greedy seed LISTS: RowBowt::get_seeds_greedy (rowbowt.hpp:191-215) and get_seeds_greedy_w_sample (:222-256), every
+// record kept.  k_greedy_seed's walk with a record where that kernel only compares lengths.  FILL = false counts the records
+// of a read into seed_cnt[i + 1]; FILL = true writes record r of read i at seed_off[i] + r of the five arrays (the
+// rightmost seed first, as the reference pushes them).  TOE = false carries no toehold and reads no sample: the count pass,
+// and get_seeds_greedy (ssamp 0; it works on an index without a toehold SA).  pk is not reset when a seed ends (:239-246),
+// so a zero-length seed (min_length == 0) carries the toehold of the last successful step before it.  w_sample picks the
+// tail's rule: pushed only if ei >= min_length (:252), or always (:211).
+template <typename P, bool TOE>
+__device__ __forceinline__ bool lf_seed_step(const DevSym &S, const uint8_t *__restrict__ dense, uint32_t adv, uint64_t &lo, uint64_t &hi,
+                                             uint64_t &k) {
+    if constexpr (TOE) return lf_w_loc<P>(S, dense, adv, lo, hi, k);
+    RankAux q;
+    uint64_t c_before, c_upto, bh;
+    rank_pair<P>(S, dense, lo, hi + 1, &c_before, &c_upto, &bh, &q);
+    const uint64_t c_inside = c_upto - c_before;
+    if (c_inside == 0) return false;
+    lo = S.F + c_before;
+    hi = lo + c_inside - 1;
+    return true;
+}
+
+template <typename P, bool FILL, bool TOE>
+__global__ __launch_bounds__(1024) void k_greedy_seeds_list(const DevIndex ix, const uint8_t *__restrict__ seqs,
+                                                     const uint64_t *__restrict__ off, const uint64_t N,
+                                                     const uint64_t min_length, const bool w_sample, uint64_t *__restrict__ seed_cnt,
+                                                     const uint64_t *__restrict__ seed_off, uint64_t *__restrict__ lo_out,
+                                                     uint64_t *__restrict__ hi_out, uint64_t *__restrict__ qs_out,
+                                                     uint64_t *__restrict__ qe_out, uint64_t *__restrict__ ss_out,
+                                                     const uint32_t max_k) {
+    __shared__ uint8_t s_lut[256];
+    __shared__ uint8_t s_lut2[256];
+    extern __shared__ __align__(16) unsigned char s_dyn[];
+    DevSym *s_tab = reinterpret_cast<DevSym *>(s_dyn);
+    const uint32_t ksteps = ix.kmer_steps < max_k ? ix.kmer_steps : max_k;  // deepest level staged (the launcher sized the LDS for it)
+    stage_tables(ix, s_tab, s_lut, s_lut2, ksteps >= 5);
+    static_assert(FILL || !TOE, "the count pass carries no toehold");
+    const uint32_t M = ix.nmajor;
+    if (!FILL && blockIdx.x == 0 && threadIdx.x == 0) seed_cnt[0] = 0;
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < N; i += stride) {
+        const uint64_t beg = off[i], m = off[i + 1] - beg;
+        const uint64_t first_k = TOE ? ix.last_run_sample : 0;  // rowbowt.hpp:230
+        const uint64_t fhi = ix.n - 1;
+        uint64_t lo = 0, hi = fhi, plo = 0, phi = fhi;
+        uint64_t k = first_k, pk = ~uint64_t(0), ei = m;
+        uint64_t ns = 0;  // records of this read so far
+        const uint64_t dst = FILL ? seed_off[i] : 0;
+        const uint64_t room = FILL ? seed_off[i + 1] - dst : 0;  // (a fill never writes past what the plan counted)
+        ByteCursor rd{reinterpret_cast<const uint4 *>(seqs), ~uint64_t(0), make_uint4(0, 0, 0, 0)};
+        uint64_t j = m;  // next symbol to consume is q[j-1]
+        auto lf1 = [&](uint32_t c) -> bool {  // one reference step (:197 / :235); an absent symbol is an empty range (:76)
+            const uint32_t slot = s_lut[c];
+            if (slot == 0xFFu) return false;
+            if (slot < static_cast<uint32_t>(kLdsSyms)) { const DevSym S = s_tab[slot]; return lf_seed_step<P, TOE>(S, ix.dense, 1u, lo, hi, k); }
+            return lf_seed_step<P, TOE>(ix.syms[slot], ix.dense, 1u, lo, hi, k);
+        };
+        // the longest k-mer (2..min(cap, kmer_steps) symbols, all with k-mer tables) ending at byte p (k_greedy_seed)
+        auto lfk = [&](uint64_t p, uint32_t c, uint64_t cap, uint32_t *len) -> bool {
+            *len = 0;
+            const uint32_t m0 = s_lut2[c];
+            if (m0 == 0xFFu || cap < 2 || ksteps < 2) return false;
+            const uint32_t m1 = s_lut2[rd.at(p - 1)];
+            if (m1 == 0xFFu) return false;
+            uint32_t adv = 2, idx = kOff2 + m1 * M + m0;
+            if (ksteps >= 3 && cap >= 3) {
+                const uint32_t m2 = s_lut2[rd.at(p - 2)];
+                if (m2 != 0xFFu) {
+                    adv = 3;
+                    idx = kOff3 + (m2 * M + m1) * M + m0;
+                    if (ksteps >= 4 && cap >= 4) {
+                        const uint32_t m3 = s_lut2[rd.at(p - 3)];
+                        if (m3 != 0xFFu) {
+                            adv = 4;
+                            idx = kOff4 + ((m3 * M + m2) * M + m1) * M + m0;
+                            if (ksteps >= 5 && cap >= 5) {
+                                const uint32_t m4 = s_lut2[rd.at(p - 4)];
+                                if (m4 != 0xFFu) { adv = 5; idx = kOff5 + (((m4 * M + m3) * M + m2) * M + m1) * M + m0; }
+                            }
+                        }
+                    }
+                }
+            }
+            *len = adv;
+            const DevSym S = s_tab[idx];
+            return lf_seed_step<P, TOE>(S, ix.dense, adv, lo, hi, k);
+        };
+        auto emit = [&](uint64_t qs) {  // LFData(prev_range, qs, ei[, pk]), :203 / :211 / :239 / :253
+            if (FILL && ns < room) {
+                const uint64_t at = dst + ns;
+                lo_out[at] = plo;
+                hi_out[at] = phi;
+                qs_out[at] = qs;
+                qe_out[at] = ei;
+                if (TOE) ss_out[at] = pk;
+                else if (ss_out) ss_out[at] = 0;
+            }
+            ++ns;
+        };
+        auto on_ok = [&](uint32_t adv) {
+            j -= adv;
+            plo = lo; phi = hi; pk = k;  // rowbowt.hpp:208 / :248-249
+        };
+        auto on_fail = [&]() {  // q[j-1] ends the seed q[j, ei)  (rowbowt.hpp:199-207, :236-246; m-i == j here)
+            if (ei - j >= min_length) emit(j);
+            k = first_k;  // (pk stays: :241-244)
+            lo = 0; hi = fhi; plo = 0; phi = fhi;
+            j -= 1;      // skip the base that failed
+            ei = j;
+        };
+        while (j > 0) {
+            const uint64_t p = beg + j - 1;
+            const uint32_t c = rd.at(p);
+            if (j == ei && ix.ftab_k && j >= ix.ftab_k) {  // a fresh seed: its first ftab_k symbols from the device table (k_greedy_seed)
+                uint64_t idx = 0, pw = 1;
+                bool all_major = true;
+                for (uint32_t t = 0; t < ix.ftab_k; ++t) {
+                    const uint32_t mm = s_lut2[rd.at(p - t)];
+                    all_major = all_major && mm != 0xFFu;
+                    idx += (mm & 3u) * pw;
+                    pw *= M;
+                }
+                uint64_t flo, fhi2, fk;
+                if (all_major && ftab_lookup<P>(ix, idx, flo, fhi2, fk) && flo <= fhi2) {
+                    lo = flo; hi = fhi2;
+                    if (TOE) k = fk;
+                    on_ok(ix.ftab_k);
+                    continue;
+                }
+            }
+            uint32_t len;
+            if (lfk(p, c, j, &len)) { on_ok(len); continue; }
+            if (len == 0) {
+                if (lf1(c)) on_ok(1u); else on_fail();
+                continue;
+            }
+            // the range died inside q[j-len, j) (lo/hi/k are untouched by a failed step): halve the window until one symbol is left
+            while (len > 1) {
+                const uint32_t half = len / 2;
+                const uint64_t p2 = beg + j - 1;
+                const uint32_t c2 = rd.at(p2);
+                uint32_t l2;
+                const bool ok2 = half >= 2 ? lfk(p2, c2, half, &l2) : lf1(c2);
+                if (ok2) { on_ok(half); len -= half; } else len = half;
+            }
+            on_fail();
+        }
+        if (!w_sample || ei >= min_length) emit(0);  // :211 (always) / :252-254
+        if (!FILL) seed_cnt[i + 1] = ns;
+    }
+}
+
+// ---- toehold checkpoints: RowBowt::find_range_w_toehold_chkpnts (rowbowt.hpp:575-606) ------------------------
+// k_find_range_markers' single steps with the toehold carried (LF_w_loc) and a record store in place of the marker
+// query: after step i = wsize, 2 wsize, ... a record labelled qstart = m - i with the range and toehold of q[m-i-1, m);
+// the final record {0, m} when (m - 1) % wsize != 0 (m - 1 wraps for an empty read).  Record r of read i is slot
+// slot_off[i] + r; cnt[i] = 0 for a read that does not occur (:588-590), else all of its slots.
+template <typename P>
+__global__ __launch_bounds__(256) void k_toehold_chkpnts(const DevIndex ix, const uint8_t *__restrict__ seqs,
+                                                         const uint64_t *__restrict__ off, const uint64_t N, const uint64_t wsize,
+                                                         const uint64_t *__restrict__ slot_off, uint64_t *__restrict__ cnt_out,
+                                                         uint64_t *__restrict__ lo_out, uint64_t *__restrict__ hi_out,
+                                                         uint64_t *__restrict__ qs_out, uint64_t *__restrict__ qe_out,
+                                                         uint64_t *__restrict__ ss_out) {
+    __shared__ uint8_t s_lut[256];
+    __shared__ DevSym s_sym[kLdsSyms];
+    for (int t = threadIdx.x; t < 256; t += blockDim.x) s_lut[t] = ix.lut[t];
+    const int nlds = ix.sigma < static_cast<uint32_t>(kLdsSyms) ? static_cast<int>(ix.sigma) : kLdsSyms;
+    for (int t = threadIdx.x; t < nlds; t += blockDim.x) s_sym[t] = ix.syms[t];
+    __syncthreads();
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < N; i += stride) {
+        const uint64_t beg = off[i], m = off[i + 1] - beg;
+        const uint64_t dst = slot_off[i], room = slot_off[i + 1] - dst;
+        uint64_t lo = 0, hi = ix.n - 1, k = ix.last_run_sample;  // :583-584
+        uint64_t window_ei = m, nrec = 0;
+        bool alive = true;
+        ByteCursor rd{reinterpret_cast<const uint4 *>(seqs), ~uint64_t(0), make_uint4(0, 0, 0, 0)};
+        auto record = [&](uint64_t qs, uint64_t qe) {  // :593-595 / :600-602
+            if (nrec < room) {
+                const uint64_t at = dst + nrec;
+                lo_out[at] = lo;
+                hi_out[at] = hi;
+                qs_out[at] = qs;
+                qe_out[at] = qe;
+                ss_out[at] = k;
+            }
+            ++nrec;
+        };
+        for (uint64_t s = 0; s < m; ++s) {
+            const uint32_t slot = s_lut[rd.at(beg + m - 1 - s)];
+            if (slot == 0xFFu) { alive = false; break; }
+            const DevSym S = slot < static_cast<uint32_t>(kLdsSyms) ? s_sym[slot] : ix.syms[slot];
+            if (!lf_w_loc<P>(S, ix.dense, 1u, lo, hi, k)) { alive = false; break; }  // :588-590
+            if (window_ei - (m - s) >= wsize) {         // :592
+                record(m - s, window_ei);
+                window_ei = m - s;                      // :596
+            }
+        }
+        if (alive && (m - 1) % wsize != 0) record(0, m);  // :599-603
+        cnt_out[i] = alive ? nrec : 0;
+    }
+}
+
+// the slots of a read's checkpoints, from its length alone: floor((m - 1) / wsize) records inside the loop and the final one when
+// (m - 1) % wsize != 0, m - 1 in wrapping arithmetic (an empty read: no step, the final record alone)
+__global__ __launch_bounds__(256) void k_chkpnt_slots(const uint64_t *__restrict__ off, const uint64_t N, const uint64_t wsize,
+                                                      uint64_t *__restrict__ slot_off) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < N; i += stride) {
+        const uint64_t m = off[i + 1] - off[i], m1 = m - 1;
+        slot_off[i + 1] = (m ? m1 / wsize : 0) + (m1 % wsize != 0 ? 1 : 0);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) slot_off[0] = 0;
+}
+
 // ---- marker seeds (next-row f4): RowBowt::get_markers_greedy_seeding without an ftab
 // (rowbowt.hpp:406-482; rb_markers' default path, rb_markers.cpp:411-413).  One record per call of
 // the reference's callback: {range lo, range hi, q.first, seed_ei (= q.second + 1), first marker,
@@ -880,6 +1095,62 @@ int launch_greedy_seed(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *
     } while (0)
     if (ix.pos_bytes == 4) RBG_GS(uint32_t); else RBG_GS(uint64_t);
 #undef RBG_GS
+    return static_cast<int>(hipGetLastError());
+}
+
+// greedy seed lists, two phases: the plan counts (no toehold) and scans, the fill walks again and writes
+int launch_greedy_seeds_plan(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t min_length,
+                             bool w_sample, uint64_t *seed_off, void *tmp, size_t tmp_bytes, void *stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (N == 0) return static_cast<int>(hipMemsetAsync(seed_off, 0, 8, st));
+    int rc;
+    if (ix.layout == 2) {
+        rc = launch_greedy_seeds_list_runs(ix, cfg, seqs, off, N, min_length, w_sample, seed_off, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, stream);
+    } else {
+        auto launch = [&](auto kern) {
+            const KmerLaunch L = kmer_launch(ix, cfg, N, kern, 0, kSeedKmerLevel);
+            hipLaunchKernelGGL(kern, L.grid, L.block, L.lds, st, ix, seqs, off, N, min_length, w_sample, seed_off, nullptr, nullptr, nullptr, nullptr, nullptr,
+                               nullptr, kSeedKmerLevel);
+        };
+        if (ix.pos_bytes == 4) launch(k_greedy_seeds_list<uint32_t, false, false>); else launch(k_greedy_seeds_list<uint64_t, false, false>);
+        rc = static_cast<int>(hipGetLastError());
+    }
+    if (rc) return rc;
+    return scan_in_place(seed_off + 1, N, tmp, tmp_bytes, st);
+}
+
+int launch_greedy_seeds_fill(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t min_length,
+                             bool w_sample, const uint64_t *seed_off, uint64_t *lo, uint64_t *hi, uint64_t *qs, uint64_t *qe, uint64_t *ss, void *stream) {
+    if (N == 0) return 0;
+    if (ix.layout == 2) return launch_greedy_seeds_list_runs(ix, cfg, seqs, off, N, min_length, w_sample, nullptr, seed_off, lo, hi, qs, qe, ss, true, stream);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    auto launch = [&](auto kern) {
+        const KmerLaunch L = kmer_launch(ix, cfg, N, kern, 0, kSeedKmerLevel);
+        hipLaunchKernelGGL(kern, L.grid, L.block, L.lds, st, ix, seqs, off, N, min_length, w_sample, nullptr, seed_off, lo, hi, qs, qe, ss, kSeedKmerLevel);
+    };
+    if (ix.pos_bytes == 4) { if (w_sample) launch(k_greedy_seeds_list<uint32_t, true, true>); else launch(k_greedy_seeds_list<uint32_t, true, false>); }
+    else { if (w_sample) launch(k_greedy_seeds_list<uint64_t, true, true>); else launch(k_greedy_seeds_list<uint64_t, true, false>); }
+    return static_cast<int>(hipGetLastError());
+}
+
+// toehold checkpoints: the slots of every read (from the offsets alone), then one walk
+int launch_toehold_chkpnts_slots(const LaunchCfg &cfg, const uint64_t *off, uint64_t N, uint64_t wsize, uint64_t *slot_off, void *tmp, size_t tmp_bytes,
+                                 void *stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_chkpnt_slots, dim3(grid_for(cfg, N)), dim3(256), 0, st, off, N, wsize, slot_off);
+    const int rc = static_cast<int>(hipGetLastError());
+    if (rc) return rc;
+    return scan_in_place(slot_off + 1, N, tmp, tmp_bytes, st);
+}
+
+int launch_toehold_chkpnts(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t wsize,
+                           const uint64_t *slot_off, uint64_t *cnt, uint64_t *lo, uint64_t *hi, uint64_t *qs, uint64_t *qe, uint64_t *ss, void *stream) {
+    if (N == 0) return 0;
+    if (ix.layout == 2) return launch_toehold_chkpnts_runs(ix, cfg, seqs, off, N, wsize, slot_off, cnt, lo, hi, qs, qe, ss, stream);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(grid_for(cfg, N)), block(cfg.block_threads);
+    if (ix.pos_bytes == 4) hipLaunchKernelGGL((k_toehold_chkpnts<uint32_t>), grid, block, 0, st, ix, seqs, off, N, wsize, slot_off, cnt, lo, hi, qs, qe, ss);
+    else hipLaunchKernelGGL((k_toehold_chkpnts<uint64_t>), grid, block, 0, st, ix, seqs, off, N, wsize, slot_off, cnt, lo, hi, qs, qe, ss);
     return static_cast<int>(hipGetLastError());
 }
 

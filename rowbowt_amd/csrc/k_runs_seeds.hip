@@ -831,6 +831,198 @@ __global__ __launch_bounds__(512, 4) void k_marker_lmems_runs(const DevIndex ix,
     }
 }
 
+// ---- greedy seed LISTS: RowBowt::get_seeds_greedy (rowbowt.hpp:191-215) and get_seeds_greedy_w_sample (:222-256), every record kept ----
+// k_greedy_seed_runs' walk (staged reads, k-mer steps, an empty step halved down to the failing symbol, the device ftab for a fresh seed's
+// first symbols) with a record where that kernel only compares lengths: on_fail and the tail.  Two passes: FILL = false counts the
+// records of a read into seed_cnt[i + 1]; FILL = true writes record r of read i at seed_off[i] + r of the five arrays, in the
+// reference's order (the rightmost seed first).  TOE = false carries no toehold at all: the count pass (which record exists does not
+// depend on one) and get_seeds_greedy, whose records have ssamp 0.  TOE = true: a deferred re-sample is resolved per record.
+// What differs from the longest-seed walk on purpose: pk -- and with it a deferred re-sample of pk -- survives a seed's end
+// (:239-246 reset k, not pk), so that a zero-length seed (min_length == 0) carries the toehold of the last successful step before it.
+// w_sample picks the tail's rule: pushed only if ei >= min_length (:252), or always (:211).
+template <typename P, bool FILL, bool TOE>
+__global__ __launch_bounds__(512, TOE ? 3 : 4) void k_greedy_seeds_list_runs(const DevIndex ix, const uint8_t *__restrict__ seqs,
+                                                     const uint64_t *__restrict__ off, const uint64_t N,
+                                                     const uint64_t min_length, const bool w_sample, uint64_t *__restrict__ seed_cnt,
+                                                     const uint64_t *__restrict__ seed_off, uint64_t *__restrict__ lo_out,
+                                                     uint64_t *__restrict__ hi_out, uint64_t *__restrict__ qs_out,
+                                                     uint64_t *__restrict__ qe_out, uint64_t *__restrict__ ss_out) {
+    RBG_SEED_KERNEL_PROLOGUE(P);
+    RBG_SEED_STAGE_SHARED;
+    static_assert(FILL || !TOE, "the count pass carries no toehold");
+    if (!FILL && blockIdx.x == 0 && threadIdx.x == 0) seed_cnt[0] = 0;
+    const uint64_t first_k = TOE ? ix.last_run_sample : 0;   // rowbowt.hpp:230
+    const uint64_t fhi = ix.n - 1;
+    for (uint64_t base = wave_first; base < N; base += stride) {
+        const uint64_t i = base + lane;
+        const bool valid = i < N;
+        uint64_t beg = 0, m = 0;
+        if (valid) { beg = off[i]; m = off[i + 1] - beg; }
+        bool staged = false;                            // the wave's reads as 2-bit codes in LDS (as in k_greedy_seed_runs)
+        if (stage_on && __ballot(valid && m > kStageCap) == 0) {
+            uint32_t nch = 0;
+            const bool bad = valid && stage_read(reinterpret_cast<const uint4 *>(seqs), beg, beg + m, stage_tab, codes, nch);
+            staged = __ballot(bad) == 0;
+        }
+        auto walk = [&](auto staged_tag) __attribute__((always_inline)) {
+        constexpr bool STAGED = decltype(staged_tag)::value;
+        uint64_t lo = 0, hi = fhi, plo = 0, phi = fhi;
+        uint64_t k = first_k, pk = ~uint64_t(0), ei = m;
+        bool pend = false, ppend = false;               // deferred re-samples of k and of pk (k_greedy_seed_runs)
+        uint32_t pend_d = 0, pend_rec = 0, ppend_d = 0, ppend_rec = 0;
+        uint64_t pend_e = 0, ppend_e = 0;
+        uint64_t ns = 0;                                // records of this read so far
+        const uint64_t dst = (FILL && valid) ? seed_off[i] : 0;
+        const uint64_t room = (FILL && valid) ? seed_off[i + 1] - dst : 0;   // (a fill never writes past what the plan counted)
+        uint64_t j = m;                                 // next symbol to consume is q[j-1]
+        uint32_t nlen = 0;                              // > 0: a k-mer step over q[j-nlen, j) came back empty and is being narrowed
+        ByteCursor rd{reinterpret_cast<const uint4 *>(seqs), ~uint64_t(0), make_uint4(0, 0, 0, 0)};
+        auto emit = [&](uint64_t qs) {                  // LFData(prev_range, qs, ei[, pk]), :203 / :211 / :239 / :253
+            if (FILL && ns < room) {
+                const uint64_t at = dst + ns;
+                lo_out[at] = plo;
+                hi_out[at] = phi;
+                qs_out[at] = qs;
+                qe_out[at] = ei;
+                if (TOE) ss_out[at] = ppend ? pk + run_step_sample2<P>(ix, S2, ppend_d, ppend_rec, ppend_e) : pk;
+                else if (ss_out) ss_out[at] = 0;
+            }
+            ++ns;
+        };
+        auto on_ok = [&](uint32_t adv) {
+            j -= adv;
+            plo = lo; phi = hi;                         // rowbowt.hpp:208 / :248-249
+            if (TOE) { pk = k; ppend = pend; ppend_d = pend_d; ppend_rec = pend_rec; ppend_e = pend_e; }
+        };
+        auto on_fail = [&]() {                          // q[j-1] ends the seed q[j, ei)  (rowbowt.hpp:199-207, :236-246; m-i == j here)
+            if (ei - j >= min_length) emit(j);
+            k = first_k;
+            pend = false;                               // (pk and its deferred re-sample stay: :241-244)
+            lo = 0; hi = fhi; plo = 0; phi = fhi;
+            j -= 1;                                     // skip the base that failed
+            ei = j;
+        };
+        while (__ballot(valid && j > 0)) {
+            bool stepping = false;
+            StepPick pick{1u, 0u, 0u, true};
+            while (valid && j > 0 && !stepping) {       // lane-local work until a rank is needed
+                const uint64_t p = beg + j - 1;
+                if (nlen == 0) {
+                    const uint32_t tc = static_cast<uint32_t>(m - j);   // STAGED: symbols between q[j-1] and the read's end
+                    if (j == ei && ix.ftab_k && j >= ix.ftab_k) {
+                        if (STAGED ? ftab_state_staged<P>(ix, codes, tc, lo, hi, k) : ftab_state<P>(ix, rd, s_lut2, p, M, lo, hi, k)) { pend = false; on_ok(ix.ftab_k); continue; }
+                    }
+                    pick = STAGED ? pick_step_staged(codes, s_mslot, tab_first, tc, j, D, DMASK) : pick_step(rd, s_lut, s_lut2, tab_first, p, j, D, DMASK, M);
+                    if (!pick.ok) { on_fail(); continue; }
+                } else {
+                    pick = STAGED ? pick_step_staged(codes, s_mslot, tab_first, static_cast<uint32_t>(m - j), nlen / 2, D, DMASK)
+                                  : pick_step(rd, s_lut, s_lut2, tab_first, p, nlen / 2, D, DMASK, M);
+                }
+                stepping = true;
+            }
+            RunStep r;
+            seeds_lf2<P, sizeof(P) == 8, false>(S2, stepping, pick.d, pick.rec, lo, hi + 1, r);
+            if (stepping) {
+                const uint64_t c_inside = r.c_upto - r.c_before;
+                const bool ok = c_inside != 0;
+                if (ok) {                               // LF_w_loc, rowbowt.hpp:555-573, pick.adv times nested
+                    if (TOE) {
+                        if (r.inside) k = k - pick.adv;
+                        else { pend = true; pend_d = pick.d; pend_rec = pick.rec; pend_e = r.samp_e; k = 0; }
+                    }
+                    lo = r.F + r.c_before;
+                    hi = lo + c_inside - 1;
+                }
+                if (nlen == 0) {
+                    if (ok) on_ok(pick.adv);
+                    else if (pick.adv == 1) on_fail();
+                    else nlen = pick.adv;               // the range died inside q[j-adv, j): halve until one symbol is left
+                } else {
+                    if (ok) { on_ok(pick.adv); nlen -= pick.adv; } else nlen = pick.adv;
+                }
+                if (nlen == 1) { on_fail(); nlen = 0; }  // that symbol is the failing base
+            }
+        }
+        if (valid) {
+            if (!w_sample || ei >= min_length) emit(0);   // :211 (always) / :252-254
+            if (!FILL) seed_cnt[i + 1] = ns;
+        }
+        };
+        if (staged) walk(std::true_type{}); else walk(std::false_type{});
+    }
+}
+
+// ---- toehold checkpoints: RowBowt::find_range_w_toehold_chkpnts (rowbowt.hpp:575-606) -------------------------------------------
+// k_find_range_markers_runs with the marker query replaced by a record store and the toehold carried.  The test of :592 passes after
+// step i = wsize, 2 wsize, ... (step i consumes q[m-i-1]): a record labelled qstart = m - i whose range and toehold are those of
+// q[m-i-1, m), one symbol more than the label says.  Steps take up to run_ksteps symbols and are capped at the next record's step; a
+// step that comes back empty needs no narrowing: the read does not occur and its list is empty (:588-590).  The final record
+// {0, m} follows when (m - 1) % wsize != 0 -- m - 1 wraps for an empty read, whose range is the full one.  Record r of read i is
+// slot slot_off[i] + r (the slots of a read are a function of its length: launch_toehold_chkpnts_slots); cnt[i] = 0 or all of them.
+template <typename P>
+__global__ __launch_bounds__(512, 3) void k_toehold_chkpnts_runs(const DevIndex ix, const uint8_t *__restrict__ seqs,
+                                                                  const uint64_t *__restrict__ off, const uint64_t N, const uint64_t wsize,
+                                                                  const uint64_t *__restrict__ slot_off, uint64_t *__restrict__ cnt_out,
+                                                                  uint64_t *__restrict__ lo_out, uint64_t *__restrict__ hi_out,
+                                                                  uint64_t *__restrict__ qs_out, uint64_t *__restrict__ qe_out,
+                                                                  uint64_t *__restrict__ ss_out) {
+    RBG_SEED_KERNEL_PROLOGUE(P);
+    for (uint64_t base = wave_first; base < N; base += stride) {
+        const uint64_t i = base + lane;
+        const bool valid = i < N;
+        uint64_t beg = 0, m = 0, dst = 0, room = 0;
+        if (valid) { beg = off[i]; m = off[i + 1] - beg; dst = slot_off[i]; room = slot_off[i + 1] - dst; }
+        uint64_t lo = 0, hi = ix.n - 1, k = ix.last_run_sample;   // :583-584
+        bool alive = valid;
+        bool pend = false;                              // deferred toehold re-sample (k_greedy_seed_runs), resolved where a record needs it
+        uint32_t pend_d = 0, pend_rec = 0;
+        uint64_t pend_e = 0;
+        uint64_t s = 0, next_i = wsize, window_ei = m, nrec = 0;   // s symbols consumed; the next record comes after step next_i
+        ByteCursor rd{reinterpret_cast<const uint4 *>(seqs), ~uint64_t(0), make_uint4(0, 0, 0, 0)};
+        auto record = [&](uint64_t qs, uint64_t qe) {   // :593-595 / :600-602
+            if (pend) { k += run_step_sample2<P>(ix, S2, pend_d, pend_rec, pend_e); pend = false; }
+            if (nrec < room) {
+                const uint64_t at = dst + nrec;
+                lo_out[at] = lo;
+                hi_out[at] = hi;
+                qs_out[at] = qs;
+                qe_out[at] = qe;
+                ss_out[at] = k;
+            }
+            ++nrec;
+        };
+        while (__ballot(alive && s < m)) {
+            bool stepping = alive && s < m;
+            StepPick pick{1u, 0u, 0u, true};
+            if (stepping) {
+                const uint64_t rem = m - s, togo = next_i - s;   // togo symbols may go before the one whose step writes a record (next_i >= s)
+                pick = pick_step(rd, s_lut, s_lut2, tab_first, beg + m - 1 - s, togo < rem ? togo + 1 : rem, D, DMASK, M);
+                if (!pick.ok) { alive = false; stepping = false; }
+            }
+            RunStep r;
+            seeds_lf2<P, sizeof(P) == 8, false>(S2, stepping, pick.d, pick.rec, lo, hi + 1, r);
+            if (stepping) {
+                const uint64_t c_inside = r.c_upto - r.c_before;
+                if (c_inside == 0) alive = false;       // :588-590
+                else {                                  // LF_w_loc, rowbowt.hpp:555-573, pick.adv times nested
+                    if (r.inside) k = k - pick.adv;
+                    else { pend = true; pend_d = pick.d; pend_rec = pick.rec; pend_e = r.samp_e; k = 0; }
+                    lo = r.F + r.c_before;
+                    hi = lo + c_inside - 1;
+                    s += pick.adv;
+                    if (s - 1 == next_i) {              // :592 after step i = s - 1
+                        record(m - next_i, window_ei);
+                        window_ei = m - next_i;         // :596
+                        next_i = next_i + wsize < next_i ? ~uint64_t(0) : next_i + wsize;
+                    }
+                }
+            }
+        }
+        if (alive && (m - 1) % wsize != 0) record(0, m);   // :599-603
+        if (valid) cnt_out[i] = alive ? nrec : 0;
+    }
+}
+
 struct SeedLaunch {
     dim3 grid, block;
     size_t lds;
@@ -951,6 +1143,32 @@ int launch_marker_lmems_runs(const DevIndex &ix, const LaunchCfg &cfg, const uin
     } while (0)
     if (ix.pos_bytes == 4) RBG_LMR(uint32_t); else RBG_LMR(uint64_t);
 #undef RBG_LMR
+    return static_cast<int>(hipGetLastError());
+}
+int launch_greedy_seeds_list_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t min_length,
+                                  bool w_sample, uint64_t *seed_cnt, const uint64_t *seed_off, uint64_t *lo, uint64_t *hi, uint64_t *qs, uint64_t *qe,
+                                  uint64_t *ss, bool fill, void *stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const SeedLaunch L = seed_launch(ix, cfg, N);
+#define RBG_GSL(PT)                                                                                                                          \
+    do {                                                                                                                                     \
+        if (!fill) RBG_LAUNCH_SEEDK((k_greedy_seeds_list_runs<PT, false, false>), seqs, off, N, min_length, w_sample, seed_cnt, seed_off, lo, hi, qs, qe, ss); \
+        else if (w_sample) RBG_LAUNCH_SEEDK((k_greedy_seeds_list_runs<PT, true, true>), seqs, off, N, min_length, w_sample, seed_cnt, seed_off, lo, hi, qs, qe, ss); \
+        else RBG_LAUNCH_SEEDK((k_greedy_seeds_list_runs<PT, true, false>), seqs, off, N, min_length, w_sample, seed_cnt, seed_off, lo, hi, qs, qe, ss); \
+    } while (0)
+    if (ix.pos_bytes == 4) RBG_GSL(uint32_t); else RBG_GSL(uint64_t);
+#undef RBG_GSL
+    return static_cast<int>(hipGetLastError());
+}
+
+int launch_toehold_chkpnts_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t wsize,
+                                const uint64_t *slot_off, uint64_t *cnt, uint64_t *lo, uint64_t *hi, uint64_t *qs, uint64_t *qe, uint64_t *ss,
+                                void *stream) {
+    if (N == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const SeedLaunch L = seed_launch(ix, cfg, N);
+    if (ix.pos_bytes == 4) RBG_LAUNCH_SEEDK((k_toehold_chkpnts_runs<uint32_t>), seqs, off, N, wsize, slot_off, cnt, lo, hi, qs, qe, ss);
+    else RBG_LAUNCH_SEEDK((k_toehold_chkpnts_runs<uint64_t>), seqs, off, N, wsize, slot_off, cnt, lo, hi, qs, qe, ss);
     return static_cast<int>(hipGetLastError());
 }
 #undef RBG_LAUNCH_SEEDK

@@ -490,6 +490,14 @@ int launch_marker_seeds_runs(const DevIndex &ix, const LaunchCfg &cfg, const uin
 int launch_marker_lmems_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t total,
                              uint64_t wsize, uint64_t max_range, uint64_t ftab_k, uint64_t *rec_off, uint64_t *seeds, uint64_t *mk, bool fill,
                              void *stream);
+// greedy seed lists (get_seeds_greedy[_w_sample]): fill == false counts into seed_cnt[i + 1]; fill == true writes the five arrays at seed_off
+int launch_greedy_seeds_list_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t min_length,
+                                  bool w_sample, uint64_t *seed_cnt, const uint64_t *seed_off, uint64_t *lo, uint64_t *hi, uint64_t *qs, uint64_t *qe,
+                                  uint64_t *ss /*nullable without w_sample*/, bool fill, void *stream);
+// toehold checkpoints (find_range_w_toehold_chkpnts): record r of read i at slot_off[i] + r, cnt[i] = 0 or slot_off[i + 1] - slot_off[i]
+int launch_toehold_chkpnts_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t wsize,
+                                const uint64_t *slot_off, uint64_t *cnt, uint64_t *lo, uint64_t *hi, uint64_t *qs, uint64_t *qe, uint64_t *ss,
+                                void *stream);
 int launch_find_range_stats(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N,
                             uint64_t *lo, uint64_t *hi, uint64_t *ssamp /*nullable*/, unsigned long long *stats /*kStatSearchN*/,
                             void *stream);
@@ -565,6 +573,16 @@ int launch_marker_lmems_plan(const DevIndex &ix, const LaunchCfg &cfg, const uin
                              uint64_t wsize, uint64_t max_range, uint64_t ftab_k, uint64_t *mk_off, void *tmp, size_t tmp_bytes, void *stream);
 int launch_marker_lmems_fill(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t total,
                              uint64_t wsize, uint64_t max_range, uint64_t ftab_k, const void *tmp, uint64_t *seeds, uint64_t *mk, void *stream);
+// greedy seed lists, two phases (tmp: scan_tmp_bytes(N)); w_sample = get_seeds_greedy_w_sample, else get_seeds_greedy (ss nullable, written 0)
+int launch_greedy_seeds_plan(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t min_length,
+                             bool w_sample, uint64_t *seed_off, void *tmp, size_t tmp_bytes, void *stream);
+int launch_greedy_seeds_fill(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t min_length,
+                             bool w_sample, const uint64_t *seed_off, uint64_t *lo, uint64_t *hi, uint64_t *qs, uint64_t *qe, uint64_t *ss, void *stream);
+// toehold checkpoints: slot_off[N + 1] from the read lengths (tmp: scan_tmp_bytes(N)), then the walk into the fixed slots (wsize >= 1)
+int launch_toehold_chkpnts_slots(const LaunchCfg &cfg, const uint64_t *off, uint64_t N, uint64_t wsize, uint64_t *slot_off, void *tmp, size_t tmp_bytes,
+                                 void *stream);
+int launch_toehold_chkpnts(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t wsize,
+                           const uint64_t *slot_off, uint64_t *cnt, uint64_t *lo, uint64_t *hi, uint64_t *qs, uint64_t *qe, uint64_t *ss, void *stream);
 int launch_greedy_seed(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N,
                        uint64_t min_length, uint64_t *lo, uint64_t *hi, uint64_t *qs, uint64_t *qe, uint64_t *ss, void *stream, unsigned long long *stats = nullptr);
 int launch_markers_plan(const DevIndex &ix, const LaunchCfg &cfg, const uint64_t *lo, const uint64_t *hi, uint64_t N,

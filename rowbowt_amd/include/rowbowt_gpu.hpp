@@ -82,6 +82,7 @@ class RowBowt {
     struct LFData {
         LFData() {}
         LFData(range_t r, uint64_t s, uint64_t e, uint64_t ss) : rn(r), qstart(s), qend(e), ssamp(ss) {}
+        LFData(range_t r, uint64_t s, uint64_t e) : rn(r), qstart(s), qend(e) {}  // (:148-152 leaves ssamp unset; 0 here)
         void clear() { rn = {1, 0}; qstart = 0; qend = 0; ssamp = 0; markers.clear(); }
         range_t rn = {1, 0};
         uint64_t qstart = 0;
@@ -274,6 +275,62 @@ class RowBowt {
         std::vector<uint64_t> locs;
         return find_locs_greedy_seeding(s, min_length, max_hits, locs);
     }
+    // rowbowt.hpp:191-215: every greedy seed of the query, the rightmost first; the last record (qstart 0) is always pushed.
+    // ssamp is 0 (the reference leaves it unset); works without a toehold SA
+    std::vector<LFData> &get_seeds_greedy(const std::string &query, uint64_t min_length, std::vector<LFData> &lfdata) const {
+        return seed_list(query, min_length, 0u, lfdata);
+    }
+    // rowbowt.hpp:222-256: the same with the toehold of every seed; the last record only if it has min_length symbols;
+    // no toehold SA: an empty list (:225)
+    std::vector<LFData> &get_seeds_greedy_w_sample(const std::string &query, uint64_t min_length, std::vector<LFData> &lfdata) const {
+        lfdata.clear();
+        if (!has_tsa_) return lfdata;
+        return seed_list(query, min_length, RBG_SEEDS_W_SAMPLE, lfdata);
+    }
+    std::vector<LFData> get_seeds_greedy_w_sample(const std::string &query, uint64_t min_length) const {
+        std::vector<LFData> lfs;
+        return get_seeds_greedy_w_sample(query, min_length, lfs);
+    }
+
+    // rowbowt.hpp:575-611: a record after step wsize, 2 wsize, ... of the backward search (labelled one symbol behind its range
+    // and toehold, include/rbg.h) and the whole query's at the end when (m - 1) % wsize != 0; empty when the query does not
+    // occur or there is no toehold SA.  wsize == 0 (the reference divides by it) ends the program with the library's error
+    std::vector<LFData> &find_range_w_toehold_chkpnts(const std::string &query, uint64_t wsize, std::vector<LFData> &lfs) const {
+        lfs.clear();
+        if (!has_tsa_) return lfs;  // :579
+        const uint64_t off[2] = {0, query.size()};
+        uint64_t seed_off[2];
+        detail::LibBuf buf;
+        detail::check(rbg_find_range_w_toehold_chkpnts(ix_.get(), reinterpret_cast<const uint8_t *>(query.data()), off, 1, wsize, seed_off,
+                                                       &buf.p), "rbg_find_range_w_toehold_chkpnts");
+        append_records(buf.p, seed_off[1], 0, seed_off[1], lfs);
+        return lfs;
+    }
+    std::vector<LFData> find_range_w_toehold_chkpnts(const std::string &query, uint64_t wsize) const {
+        std::vector<LFData> lfs;
+        return find_range_w_toehold_chkpnts(query, wsize, lfs);
+    }
+
+    // rowbowt.hpp:664-690: the first seed of strictly greatest length, then locs_at, then minus its qstart; an empty list, or
+    // zero-length seeds only (best_range stays the default LFData, an empty range), gives no locations
+    std::vector<uint64_t> &locate_from_longest_seed(uint64_t max_hits, const std::vector<LFData> &lfs, std::vector<uint64_t> &locs) const {
+        locs.clear();
+        const LFData *best = nullptr;
+        uint64_t max_length = 0;
+        for (const auto &lfd : lfs) {
+            const uint64_t length = lfd.qend - lfd.qstart;
+            if (length > max_length) { max_length = length; best = &lfd; }
+        }
+        if (!best) return locs;
+        locs_at(best->rn, best->ssamp, max_hits, locs);
+        for (auto &l : locs) l -= best->qstart;
+        return locs;
+    }
+    std::vector<uint64_t> locate_from_longest_seed(uint64_t max_hits, const std::vector<LFData> &lfs) {
+        std::vector<uint64_t> locs;
+        return locate_from_longest_seed(max_hits, lfs, locs);
+    }
+
     // the seed locate_from_longest_seed would pick among get_seeds_greedy_w_sample(query, min_length)
     LFData longest_greedy_seed(const std::string &query, uint64_t min_length) const {
         LFData lf;
@@ -339,7 +396,48 @@ class RowBowt {
         mk.assign(buf.p, buf.p + mk_off[N]);
     }
 
+    // get_seeds_greedy_w_sample (w_sample) or get_seeds_greedy for many reads: out[i] = the list of queries[i]
+    void get_seeds_greedy_batch(const std::vector<std::string> &queries, uint64_t min_length, bool w_sample,
+                                std::vector<std::vector<LFData>> &out) const {
+        out.assign(queries.size(), std::vector<LFData>());
+        if (w_sample && !has_tsa_) return;
+        detail::Batch b;
+        for (const auto &q : queries) b.add(q);
+        std::vector<uint64_t> seed_off(b.size() + 1);
+        detail::LibBuf buf;
+        detail::check(rbg_get_seeds_greedy(ix_.get(), b.data(), b.off.data(), b.size(), min_length, w_sample ? RBG_SEEDS_W_SAMPLE : 0u,
+                                           seed_off.data(), &buf.p), "rbg_get_seeds_greedy");
+        for (uint64_t i = 0; i < b.size(); ++i) append_records(buf.p, seed_off[b.size()], seed_off[i], seed_off[i + 1], out[i]);
+    }
+    void find_range_w_toehold_chkpnts_batch(const std::vector<std::string> &queries, uint64_t wsize, std::vector<std::vector<LFData>> &out) const {
+        out.assign(queries.size(), std::vector<LFData>());
+        if (!has_tsa_) return;
+        detail::Batch b;
+        for (const auto &q : queries) b.add(q);
+        std::vector<uint64_t> seed_off(b.size() + 1);
+        detail::LibBuf buf;
+        detail::check(rbg_find_range_w_toehold_chkpnts(ix_.get(), b.data(), b.off.data(), b.size(), wsize, seed_off.data(), &buf.p),
+                      "rbg_find_range_w_toehold_chkpnts");
+        for (uint64_t i = 0; i < b.size(); ++i) append_records(buf.p, seed_off[b.size()], seed_off[i], seed_off[i + 1], out[i]);
+    }
+
    private:
+    // records [from, to) of a library block of five arrays of `total` entries (lo | hi | qstart | qend | ssamp)
+    static void append_records(const uint64_t *p, uint64_t total, uint64_t from, uint64_t to, std::vector<LFData> &lfs) {
+        for (uint64_t t = from; t < to; ++t)
+            lfs.push_back(LFData(range_t(p[t], p[total + t]), p[2 * total + t], p[3 * total + t], p[4 * total + t]));
+    }
+    std::vector<LFData> &seed_list(const std::string &query, uint64_t min_length, uint32_t flags, std::vector<LFData> &lfdata) const {
+        lfdata.clear();
+        const uint64_t off[2] = {0, query.size()};
+        uint64_t seed_off[2];
+        detail::LibBuf buf;
+        detail::check(rbg_get_seeds_greedy(ix_.get(), reinterpret_cast<const uint8_t *>(query.data()), off, 1, min_length, flags, seed_off,
+                                           &buf.p), "rbg_get_seeds_greedy");
+        append_records(buf.p, seed_off[1], 0, seed_off[1], lfdata);
+        return lfdata;
+    }
+
     std::shared_ptr<rbg_index> ix_;
     uint64_t n_ = 0;
     bool has_tsa_ = false, has_ma_ = false, disable_ft_ = false;
