@@ -123,6 +123,18 @@ int rbg_check_ftab(rbg_index *, const char *path, uint64_t *k_out);
  * inclusive SA-index runs + mk_off[nruns+1] offsets into mk_vals. */
 int rbg_set_markers(rbg_index *, const uint64_t *run_start, const uint64_t *run_end, uint64_t nruns,
                     const uint64_t *mk_off, const uint64_t *mk_vals);
+/* A SECOND marker table, keyed by TEXT position (the reference's rle_window_arr `midx`, rb_markers_tsa.cpp:76-101: rb_locs looks up the markers
+ * that overlap the text interval a read aligns to).  Arguments as rbg_set_markers; the runs are inclusive, ascending, disjoint intervals of text
+ * positions in [0, n) (anything else: RBG_EARG).  It lives beside the SA-row table and never replaces it; setting it again replaces the table
+ * set before (whose device memory is given back).  On the primary only (RBG_EARG on a replica): rbg_replicate* carries the table a primary has
+ * at that moment.  Needs a device (RBG_ENODEV on a host-only handle). */
+int rbg_set_text_markers(rbg_index *, const uint64_t *run_start, const uint64_t *run_end, uint64_t nruns,
+                         const uint64_t *mk_off, const uint64_t *mk_vals);
+/* the same from a <prefix>.midx file, read with the .mab reader.  That the two files share a format is INFERRED, not pinned: rle_window_arr and
+ * MarkerArray come from the same pfbwt-f header family (not vendored with the reference), and build_midx.cpp and rowbowt_io.hpp:60 construct and
+ * serialise them the same way (three sd_vectors -- run starts, run ends, first-value flags -- then the int_vector of values); no file written
+ * by the reference's build_midx was available to check against.  RBG_EIO / RBG_EFORMAT as for the other index files. */
+int rbg_load_text_markers(rbg_index *, const char *path);
 /* DocList contents, doclist.hpp:57-73: names '\0'-joined, starts[ndocs]. */
 int rbg_set_docs(rbg_index *, const char *names_joined, const uint64_t *starts, uint64_t ndocs);
 
@@ -339,6 +351,18 @@ int rbg_find_range_w_toehold_chkpnts(rbg_index *, const uint8_t *seqs, const uin
  * locate_from_longest_seed :664-685): locations of the longest seed, each minus the seed's qstart. */
 int rbg_find_locs_greedy_seeding(rbg_index *, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t min_length,
                                  uint64_t max_hits, uint64_t *loc_off, uint64_t **locs);
+/* The markers of the text-position table (rbg_set_text_markers) over the text intervals of located reads: read i has the locations
+ * locs[loc_off[i], loc_off[i+1]) (as rbg_find_locs_greedy_seeding / rbg_locs_at return them) and the length off[i+1] - off[i]; for a location
+ * l its interval is [l, l + m - 1] in wrapping 64-bit arithmetic -- empty when the end lies below the start (m == 0; a location that wrapped
+ * below zero whose end wraps back) or when l >= n; an end beyond the text is clamped to n - 1.  mk_off[N+1] is per READ: *mk holds read i's
+ * markers for its first location, then its second, ...; within a location in run order -- the order rb_markers_tsa.cpp:80-86 prints.
+ * RBG_ENOTLOADED without a text-position table. */
+int rbg_markers_at_locs(rbg_index *, const uint64_t *locs, const uint64_t *loc_off, const uint64_t *off, uint64_t N,
+                        uint64_t *mk_off, uint64_t **mk);
+/* one read of rb_locs, batched (rb_markers_tsa.cpp:76-88): rbg_find_locs_greedy_seeding, then rbg_markers_at_locs over its result, the
+ * locations staying on the device in between.  *locs and *mk through rbg_free_buffer. */
+int rbg_find_loc_markers_greedy_seeding(rbg_index *, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t min_length,
+                                        uint64_t max_hits, uint64_t *loc_off, uint64_t **locs, uint64_t *mk_off, uint64_t **mk);
 /* gives back a result array one of the calls above allocated (*locs, *mk, *seeds).  Always through this call, never free():
  * large blocks are kept and handed to the next result of about that size -- their pages are already there, which is most of
  * what a 3 GB result costs (RBG_RESULT_POOL=0 in the environment: plain malloc / free). */
@@ -490,6 +514,16 @@ int rbg_markers_plan_dev(rbg_index *, const uint64_t *d_lo, const uint64_t *d_hi
                          uint64_t *d_mk_off, void *d_tmp, size_t tmp_bytes, void *stream);
 int rbg_markers_fill_dev(rbg_index *, const uint64_t *d_lo, const uint64_t *d_hi, uint64_t N,
                          const uint64_t *d_mk_off, uint64_t *d_mk, void *stream);
+/* markers at located text positions (rbg_markers_at_locs), two-phase, over what K3 leaves on the device: d_locs as rbg_locate_fill_dev /
+ * rbg_locate_fill_offset_dev write them (64-bit: rbg_locate_fill_dev32's output cannot hold a location that wrapped below zero and is not
+ * taken), d_loc_off[N+1], and the reads' d_off[N+1] (only the lengths are used).  The plan writes d_mk_off[N+1], per read (d_tmp:
+ * rbg_loc_markers_tmp_bytes(N) bytes -- nothing is stored per location); the fill writes the values.  A group of 4, 16 or 64 lanes walks one
+ * read's locations; the width is chosen on the device from d_loc_off[N] / N, or forced by the environment variable RBG_LOCMK_GROUP (tests, A/Bs). */
+size_t rbg_loc_markers_tmp_bytes(uint64_t N);
+int rbg_loc_markers_plan_dev(rbg_index *, const uint64_t *d_locs, const uint64_t *d_loc_off, const uint64_t *d_off, uint64_t N,
+                             uint64_t *d_mk_off, void *d_tmp, size_t tmp_bytes, void *stream);
+int rbg_loc_markers_fill_dev(rbg_index *, const uint64_t *d_locs, const uint64_t *d_loc_off, const uint64_t *d_off, uint64_t N,
+                             const uint64_t *d_mk_off, uint64_t *d_mk, void *stream);
 
 /* ---- global counters (the values the 8-GPU run reduces over RCCL) -------------------------- */
 /* {reads processed, reads matched (non-empty range), sum of occ, sum of located positions}

@@ -163,6 +163,13 @@ _PROTOS = [
     ("rbg_toehold_chkpnts_tmp_bytes", C.c_size_t, [U64]),
     ("rbg_toehold_chkpnts_slots_dev", C.c_int, [VP, VP, U64, U64, VP, VP, C.c_size_t, VP]),
     ("rbg_find_range_w_toehold_chkpnts_dev", C.c_int, [VP, VP, VP, U64, U64, VP, VP, VP, VP, VP, VP, VP, VP]),
+    ("rbg_set_text_markers", C.c_int, [VP, VP, VP, U64, VP, VP]),
+    ("rbg_load_text_markers", C.c_int, [VP, C.c_char_p]),
+    ("rbg_loc_markers_tmp_bytes", C.c_size_t, [U64]),
+    ("rbg_loc_markers_plan_dev", C.c_int, [VP, VP, VP, VP, U64, VP, VP, C.c_size_t, VP]),
+    ("rbg_loc_markers_fill_dev", C.c_int, [VP, VP, VP, VP, U64, VP, VP, VP]),
+    ("rbg_markers_at_locs", C.c_int, [VP, VP, VP, VP, U64, VP, C.POINTER(VP)]),
+    ("rbg_find_loc_markers_greedy_seeding", C.c_int, [VP, VP, VP, U64, U64, U64, VP, C.POINTER(VP), VP, C.POINTER(VP)]),
     ("rbg_set_default_option", C.c_int, [C.c_int, C.c_int64]),
     ("rbg_get_default_option", C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
 ]
@@ -335,6 +342,14 @@ class RowBowt:
     def set_markers(self, run_start, run_end, mk_off, mk_vals):
         a = [_u64(v) for v in (run_start, run_end, mk_off, mk_vals)]
         _check(self.L.rbg_set_markers(self.h, _p(a[0]), _p(a[1]), len(a[0]), _p(a[2]), _p(a[3])), "rbg_set_markers")
+
+    def set_text_markers(self, run_start, run_end, mk_off, mk_vals):
+        """the marker table keyed by TEXT position (rb_locs' .midx): runs of text positions in [0, n); replaces the one set before"""
+        a = [_u64(v) for v in (run_start, run_end, mk_off, mk_vals)]
+        _check(self.L.rbg_set_text_markers(self.h, _p(a[0]), _p(a[1]), len(a[0]), _p(a[2]), _p(a[3])), "rbg_set_text_markers")
+
+    def load_text_markers(self, path):
+        _check(self.L.rbg_load_text_markers(self.h, os.fsencode(path)), f"rbg_load_text_markers({path})")
 
     def set_docs(self, names, starts):
         joined = b"\0".join(n.encode() for n in names) + b"\0"
@@ -525,6 +540,24 @@ class RowBowt:
         _check(self.L.rbg_find_locs_greedy_seeding(self.h, _p(seqs), _p(off), N, min_length, max_hits, _p(loc_off), C.byref(ptr)),
                "rbg_find_locs_greedy_seeding")
         return loc_off, _take(ptr, int(loc_off[N]))
+
+    def markers_at_locs(self, locs, loc_off, off):
+        """markers of the text-position table over [l, l + m_i - 1] for every location l of read i: (mk_off[N+1] per read, values)"""
+        locs, loc_off, off = _u64(locs), _u64(loc_off), _u64(off)
+        N = len(off) - 1
+        mk_off = np.zeros(N + 1, np.uint64)
+        ptr = VP()
+        _check(self.L.rbg_markers_at_locs(self.h, _p(locs), _p(loc_off), _p(off), N, _p(mk_off), C.byref(ptr)), "rbg_markers_at_locs")
+        return mk_off, _take(ptr, int(mk_off[N]))
+
+    def find_loc_markers_greedy_seeding(self, seqs, off, min_length, max_hits=MAXU):
+        """one read of rb_locs, batched (rb_markers_tsa.cpp:76-88): (loc_off, locs, mk_off, mk)"""
+        N = len(off) - 1
+        loc_off, mk_off = np.zeros(N + 1, np.uint64), np.zeros(N + 1, np.uint64)
+        lp, mp = VP(), VP()
+        _check(self.L.rbg_find_loc_markers_greedy_seeding(self.h, _p(seqs), _p(off), N, min_length, max_hits, _p(loc_off), C.byref(lp),
+                                                          _p(mk_off), C.byref(mp)), "rbg_find_loc_markers_greedy_seeding")
+        return loc_off, _take(lp, int(loc_off[N])), mk_off, _take(mp, int(mk_off[N]))
 
     def resolve_offset(self, i):
         name, off = C.c_char_p(), U64()

@@ -76,6 +76,9 @@ struct rbg_index {
     struct TextIn { char *p = nullptr; size_t cap = 0; bool busy = false; };   // pinned staging of a call's inputs (ranges, names)
     std::vector<TextIn> text_in;
     std::mutex text_mu;
+    // the marker table keyed by text position (rbg_set_text_markers; DevIndex::tmk_*): per handle -- a replica has the table its primary had when it was made
+    bool has_tmk = false;
+    std::vector<void *> tmk_allocs;   // its device arrays (each also in `allocs`): given back when another table replaces it
     std::mutex mu;               // guards marker/doc attachment only; queries are lock-free
 };
 

@@ -107,6 +107,9 @@ int replicate_finish(rbg_index *src, ReplicaJob &job) {
     reloc.fix(d.counters); reloc.fix(d.lut); reloc.fix(d.pairs); reloc.fix(d.triples); reloc.fix(d.quads); reloc.fix(d.quints);
     reloc.fix(d.lut2); reloc.fix(d.ftab); reloc.fix(d.dense); reloc.fix(d.jump);
     reloc.fix(d.phi_dir); reloc.fix(d.order_docs);
+    reloc.fix(d.tmk_start); reloc.fix(d.tmk_end); reloc.fix(d.tmk_off); reloc.fix(d.tmk_vals); reloc.fix(d.tmk_bucket); reloc.fix(d.tmk_rec);
+    r->has_tmk = src->has_tmk;
+    for (void *p : src->tmk_allocs) r->tmk_allocs.push_back(const_cast<void *>(reloc(p)));
     for (int t = 0; t < kMaxRunDepth; ++t) reloc.fix(d.run_samp[t]);
     reloc.fix(d.run_tabs2); reloc.fix(d.run_hot); reloc.fix(d.phi_super);
     for (int t = 0; t < kMaxRunDepth; ++t) { reloc.fix(d.run_ent2[t]); reloc.fix(d.run_dir2[t]); reloc.fix(d.run_rec2[t]); }

@@ -565,9 +565,11 @@ int rbg_locate_fill_offset_dev(rbg_index *ix, const uint64_t *d_lo, const uint64
     });
 }
 
+// behind K3's fill, while the locations are still on the device (d_locs, d_loc_off, the reads' d_off): what rbg_find_loc_markers_greedy_seeding hangs on
+typedef std::function<int(const uint64_t *, const uint64_t *, const uint64_t *, hipStream_t)> AfterLocate;
 static int greedy_host(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t min_length,
                        uint64_t *lo, uint64_t *hi, uint64_t *qs, uint64_t *qe, uint64_t *ss, bool locate, uint64_t max_hits,
-                       uint64_t *loc_off, uint64_t **locs) {
+                       uint64_t *loc_off, uint64_t **locs, const AfterLocate *after = nullptr) {
     if (!queryable(ix)) return RBG_ENODEV;
     if (!ix->H().has_tsa) return RBG_ENOTLOADED;
     if (N && !off) return RBG_EARG;
@@ -599,8 +601,9 @@ static int greedy_host(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, 
     const void *order = nullptr;
     if ((rc = make_order(ix, d[4].as<uint64_t>(), N, dord, st, &order))) return rc;
     return ragged_finish(N, doff, loc_off, locs, st, [&](uint64_t *d_vals) {
-        return launch_locate_fill(ix->dev, ix->cfg, d[0].as<uint64_t>(), d[1].as<uint64_t>(), d[4].as<uint64_t>(), N, max_hits,
-                                  doff.as<uint64_t>(), d_vals, d[2].as<uint64_t>(), order, st) ? RBG_ENODEV : RBG_OK;
+        if (launch_locate_fill(ix->dev, ix->cfg, d[0].as<uint64_t>(), d[1].as<uint64_t>(), d[4].as<uint64_t>(), N, max_hits,
+                               doff.as<uint64_t>(), d_vals, d[2].as<uint64_t>(), order, st)) return static_cast<int>(RBG_ENODEV);
+        return after ? (*after)(d_vals, doff.as<uint64_t>(), rb.off.as<uint64_t>(), st) : static_cast<int>(RBG_OK);
     });
 }
 

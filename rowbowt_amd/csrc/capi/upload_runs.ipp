@@ -569,22 +569,42 @@ int upload_tables_runs2(rbg_index *ix) {
     return RBG_OK;
 }
 
-int upload_markers(rbg_index *ix) {
-    const RawMarkers &m = ix->H().ma;
+// One marker table on the device: its four arrays, the bucket directory and the bucket records.  Built twice: the SA-row table (DevIndex::mk_*, from the index
+// files or rbg_set_markers) and the table keyed by text position (DevIndex::tmk_*, rbg_set_text_markers / .midx) -- the same code under the same gates.
+struct DevMarkerTable {
+    const uint64_t *start = nullptr, *end = nullptr, *off = nullptr, *vals = nullptr;
+    uint64_t nruns = 0;
+    const uint32_t *bucket = nullptr;
+    uint32_t shift = 0;
+    const MkRec *rec = nullptr;
+};
+// own != nullptr: every array is an allocation of its own (tracked like any other: replicas copy it, rbg_info counts it) and is listed there, so that the
+// table can be given back when another one replaces it; else the arrays come from the arena while it has room
+int upload_marker_table(rbg_index *ix, const RawMarkers &m, DevMarkerTable &t, std::vector<void *> *own = nullptr) {
+    auto up = [&](const void *src, size_t bytes, const void **dst) -> int {
+        if (!own) return dev_upload(ix, src, bytes, dst);
+        void *p = nullptr;
+        const size_t alloc = arena_round(bytes);
+        HIP_TRY(hipMalloc(&p, alloc));
+        ix->allocs.push_back({p, alloc});
+        ix->hbm_bytes += alloc;
+        own->push_back(p);
+        if (bytes) { const int rc = h2d_big(p, src, bytes); if (rc) return rc; }
+        *dst = p;
+        return RBG_OK;
+    };
+    t = DevMarkerTable();
     const void *p = nullptr;
     int rc;
-    if ((rc = dev_upload(ix, m.start.data(), m.start.size() * 8, &p))) return rc;
-    ix->dev.mk_start = static_cast<const uint64_t *>(p);
-    if ((rc = dev_upload(ix, m.end.data(), m.end.size() * 8, &p))) return rc;
-    ix->dev.mk_end = static_cast<const uint64_t *>(p);
-    if ((rc = dev_upload(ix, m.off.data(), m.off.size() * 8, &p))) return rc;
-    ix->dev.mk_off = static_cast<const uint64_t *>(p);
-    if ((rc = dev_upload(ix, m.vals.data(), m.vals.size() * 8, &p))) return rc;
-    ix->dev.mk_vals = static_cast<const uint64_t *>(p);
-    ix->dev.mk_nruns = m.start.size();
-    ix->dev.mk_bucket = nullptr;
-    ix->dev.mk_shift = 0;
-    ix->dev.mk_rec = nullptr;
+    if ((rc = up(m.start.data(), m.start.size() * 8, &p))) return rc;
+    t.start = static_cast<const uint64_t *>(p);
+    if ((rc = up(m.end.data(), m.end.size() * 8, &p))) return rc;
+    t.end = static_cast<const uint64_t *>(p);
+    if ((rc = up(m.off.data(), m.off.size() * 8, &p))) return rc;
+    t.off = static_cast<const uint64_t *>(p);
+    if ((rc = up(m.vals.data(), m.vals.size() * 8, &p))) return rc;
+    t.vals = static_cast<const uint64_t *>(p);
+    t.nruns = m.start.size();
     const uint64_t nruns = m.start.size(), n = ix->H().n;
     if (nruns && nruns < 0xFFFFFFFFull) {
         // about two buckets per run: at_range's two predecessor searches (2 x log2(nruns) dependent
@@ -599,9 +619,9 @@ int upload_markers(rbg_index *ix) {
             while (j < nruns && m.end[j] < first_row) ++j;
             bucket[b] = static_cast<uint32_t>(j);
         }
-        if ((rc = dev_upload(ix, bucket.data(), nb * 4, &p))) return rc;
-        ix->dev.mk_bucket = static_cast<const uint32_t *>(p);
-        ix->dev.mk_shift = shift;
+        if ((rc = up(bucket.data(), nb * 4, &p))) return rc;
+        t.bucket = static_cast<const uint32_t *>(p);
+        t.shift = shift;
         // the bucket records (rbg_dev.h MkRec): 32 bytes per bucket, i.e. about 64 per run.  RBG_MK_REC=0: the arrays only (A/B, tests)
         // (32 bytes per bucket = about 64 per marker run: only while that is a small part of the device -- at most an eighth of the free HBM and 16 GB; a marker array
         //  of 1e9 runs keeps the 4-byte directory)
@@ -631,10 +651,44 @@ int upload_markers(rbg_index *ix) {
                 }
                 R.nin = over ? static_cast<uint8_t>(kMkRecOverflow) : static_cast<uint8_t>(k);
             }
-            if ((rc = dev_upload(ix, recs.data(), nb * sizeof(MkRec), &p))) return rc;
-            ix->dev.mk_rec = static_cast<const MkRec *>(p);
+            if ((rc = up(recs.data(), nb * sizeof(MkRec), &p))) return rc;
+            t.rec = static_cast<const MkRec *>(p);
         }
     }
+    return RBG_OK;
+}
+
+int upload_markers(rbg_index *ix) {
+    DevIndex &d = ix->dev;
+    d.mk_start = d.mk_end = d.mk_off = d.mk_vals = nullptr;
+    d.mk_nruns = 0; d.mk_bucket = nullptr; d.mk_shift = 0; d.mk_rec = nullptr;
+    DevMarkerTable t;
+    const int rc = upload_marker_table(ix, ix->H().ma, t);
+    // (as before: what was uploaded before an error stays named in the index)
+    d.mk_start = t.start; d.mk_end = t.end; d.mk_off = t.off; d.mk_vals = t.vals; d.mk_nruns = t.nruns;
+    d.mk_bucket = t.bucket; d.mk_shift = t.shift; d.mk_rec = t.rec;
+    return rc;
+}
+
+// the text-position table: replaces the one before it (whose allocations go back first), own allocations throughout
+int upload_text_markers(rbg_index *ix, const RawMarkers &m) {
+    DevIndex &d = ix->dev;
+    HIP_TRY(hipDeviceSynchronize());   // nothing may still read the table that goes
+    d.tmk_start = d.tmk_end = d.tmk_off = d.tmk_vals = nullptr;
+    d.tmk_nruns = 0; d.tmk_bucket = nullptr; d.tmk_shift = 0; d.tmk_rec = nullptr;
+    ix->has_tmk = false;
+    for (void *p : ix->tmk_allocs) free_tracked(ix, p);
+    ix->tmk_allocs.clear();
+    DevMarkerTable t;
+    const int rc = upload_marker_table(ix, m, t, &ix->tmk_allocs);
+    if (rc) {
+        for (void *p : ix->tmk_allocs) free_tracked(ix, p);
+        ix->tmk_allocs.clear();
+        return rc;
+    }
+    d.tmk_start = t.start; d.tmk_end = t.end; d.tmk_off = t.off; d.tmk_vals = t.vals; d.tmk_nruns = t.nruns;
+    d.tmk_bucket = t.bucket; d.tmk_shift = t.shift; d.tmk_rec = t.rec;
+    ix->has_tmk = true;
     return RBG_OK;
 }
 

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -39,4 +40,5 @@
 #include "capi/hostpath.ipp"      // host-pointer entry points, micro-batching
 #include "capi/text.ipp"          // rbg_align_text
 #include "capi/seeds.ipp"         // markers, marker seeds, greedy seeding
+#include "capi/loc_markers.ipp"   // the text-position marker table, markers at located positions (rb_locs' path)
 #include "capi/replicas.ipp"      // replicas in one process, counters, RCCL

@@ -330,6 +330,14 @@ struct DevIndex {
     const void *jump;          // jump_buckets x 64 bytes
     uint64_t jump_buckets;
     uint32_t jump_k;
+    // the marker table keyed by TEXT position (rbg_set_text_markers / <prefix>.midx; k_loc_markers.hip): the fields of the SA-row table above a second
+    // time -- inclusive, ascending, disjoint runs of text positions in [0, n), built by the same code under the same gates (capi/upload_runs.ipp).
+    // All nullptr / 0 until a table is set.  Kept at the end: the kernels that never read it find every other field where it was.
+    uint32_t tmk_shift;
+    const uint64_t *tmk_start, *tmk_end, *tmk_off, *tmk_vals;
+    uint64_t tmk_nruns;
+    const uint32_t *tmk_bucket;
+    const MkRec *tmk_rec;
 };
 
 // What the instrumented instantiations count (sums over the launch; include/rbg.h rbg_search_stats_t mirrors it).
@@ -589,6 +597,14 @@ int launch_markers_plan(const DevIndex &ix, const LaunchCfg &cfg, const uint64_t
                         uint64_t *mk_off, void *tmp, size_t tmp_bytes, void *stream);
 int launch_markers_fill(const DevIndex &ix, const LaunchCfg &cfg, const uint64_t *lo, const uint64_t *hi, uint64_t N,
                         const uint64_t *mk_off, uint64_t *mk, void *stream);
+// markers at located text positions (k_loc_markers.hip): read i's locations locs[loc_off[i], loc_off[i + 1]) against the text-position table, its length
+// from off; plan = per-read counts + scan (tmp: scan_tmp_bytes(N)), fill = the values in location order.  group: lanes per read, 4 / 16 / 64, or 0 = chosen
+// on the device from loc_off[N] / N (loc_markers_group(): what RBG_LOCMK_GROUP forces)
+int loc_markers_group();
+int launch_loc_markers_plan(const DevIndex &ix, const LaunchCfg &cfg, const uint64_t *locs, const uint64_t *loc_off, const uint64_t *off, uint64_t N,
+                            uint64_t *mk_off, void *tmp, size_t tmp_bytes, int group, void *stream);
+int launch_loc_markers_fill(const DevIndex &ix, const LaunchCfg &cfg, const uint64_t *locs, const uint64_t *loc_off, const uint64_t *off, uint64_t N,
+                            const uint64_t *mk_off, uint64_t *mk, int group, void *stream);
 int launch_find_range_markers_plan(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off,
                                    uint64_t N, uint64_t wsize, uint64_t max_range, uint64_t *lo, uint64_t *hi,
                                    uint64_t *mk_off, void *tmp, size_t tmp_bytes, void *stream);

@@ -350,22 +350,32 @@ inline bool chain_hi8_enabled() {
 // start <= hi && end >= lo, in run order.  Runs are disjoint, ascending inclusive SA-index intervals.  From the bucket records (rbg_dev.h MkRec: one or two
 // sectors), else from the directory + the run arrays.  st (instrumented seed walks): [kStatSearchN + 1] += records / directory entries read, [+ 2] += run starts /
 // ends read, [+ 3] += value offsets read.
-__device__ __forceinline__ void marker_span_arrays(const DevIndex &ix, uint64_t lo, uint64_t hi, uint64_t a, uint64_t z, uint64_t *first, uint64_t *last, unsigned long long *st) {
-    while (a < ix.mk_nruns && ix.mk_end[a] < lo) { ++a; if (st) st[kStatSearchN + 2] += 1; }
+// one marker table as the query sees it: the SA-row table (DevIndex::mk_*) or the text-position table (DevIndex::tmk_*), and the length of its key space
+struct MkView {
+    const uint64_t *start, *end, *off, *vals;
+    uint64_t nruns, n;
+    const uint32_t *bucket;
+    const MkRec *rec;
+    uint32_t shift;
+};
+__device__ __forceinline__ MkView sa_marker_view(const DevIndex &ix) { return MkView{ix.mk_start, ix.mk_end, ix.mk_off, ix.mk_vals, ix.mk_nruns, ix.n, ix.mk_bucket, ix.mk_rec, ix.mk_shift}; }
+__device__ __forceinline__ MkView text_marker_view(const DevIndex &ix) { return MkView{ix.tmk_start, ix.tmk_end, ix.tmk_off, ix.tmk_vals, ix.tmk_nruns, ix.n, ix.tmk_bucket, ix.tmk_rec, ix.tmk_shift}; }
+__device__ __forceinline__ void marker_span_arrays(const MkView &v, uint64_t lo, uint64_t hi, uint64_t a, uint64_t z, uint64_t *first, uint64_t *last, unsigned long long *st) {
+    while (a < v.nruns && v.end[a] < lo) { ++a; if (st) st[kStatSearchN + 2] += 1; }
     *first = a;
     if (z < a) z = a;
-    while (z < ix.mk_nruns && ix.mk_start[z] <= hi) { ++z; if (st) st[kStatSearchN + 2] += 1; }
+    while (z < v.nruns && v.start[z] <= hi) { ++z; if (st) st[kStatSearchN + 2] += 1; }
     *last = z;
     if (st) st[kStatSearchN + 2] += 2;
 }
-__device__ __forceinline__ bool marker_query(const DevIndex &ix, uint64_t lo, uint64_t hi, uint64_t *src, uint64_t *cnt, unsigned long long *st = nullptr) {
-    if (lo >= ix.n) return false;          // caller-supplied rows beyond the BWT: nothing
-    if (hi >= ix.n) hi = ix.n - 1;
+__device__ __forceinline__ bool marker_query(const MkView &v, uint64_t lo, uint64_t hi, uint64_t *src, uint64_t *cnt, unsigned long long *st = nullptr) {
+    if (lo >= v.n) return false;          // caller-supplied rows beyond the BWT: nothing
+    if (hi >= v.n) hi = v.n - 1;
     uint64_t f, l;
-    if (ix.mk_rec) {
-        const uint32_t sh = ix.mk_shift;
+    if (v.rec) {
+        const uint32_t sh = v.shift;
         const uint64_t b0 = lo >> sh, b1 = hi >> sh;
-        const u32x4 *r0p = reinterpret_cast<const u32x4 *>(ix.mk_rec + b0), *r1p = reinterpret_cast<const u32x4 *>(ix.mk_rec + b1);
+        const u32x4 *r0p = reinterpret_cast<const u32x4 *>(v.rec + b0), *r1p = reinterpret_cast<const u32x4 *>(v.rec + b1);
         MkRec R0, R1;
         const u32x4 x0 = as_global<u32x4>(static_cast<const void *>(r0p))[0], x1 = as_global<u32x4>(static_cast<const void *>(r0p))[1];
         __builtin_memcpy(&R0, &x0, 16); __builtin_memcpy(reinterpret_cast<char *>(&R0) + 16, &x1, 16);
@@ -395,25 +405,30 @@ __device__ __forceinline__ bool marker_query(const DevIndex &ix, uint64_t lo, ui
             *cnt = off_l - off_f;
             return true;
         }
-        marker_span_arrays(ix, lo, hi, R0.a, R1.a, &f, &l, st);   // an overflowing bucket: the arrays, from the records' first runs
-    } else if (ix.mk_bucket) {
+        marker_span_arrays(v, lo, hi, R0.a, R1.a, &f, &l, st);   // an overflowing bucket: the arrays, from the records' first runs
+    } else if (v.bucket) {
         // first run with end >= lo: the directory gives the first run ending at or after the start of lo's bucket, the answer is at most a bucket's worth of runs
         // further on; one past the last run with start <= hi: every run before the entry of hi's bucket ends, hence starts, before hi
         if (st) st[kStatSearchN + 1] += 2;
-        marker_span_arrays(ix, lo, hi, ix.mk_bucket[lo >> ix.mk_shift], ix.mk_bucket[hi >> ix.mk_shift], &f, &l, st);
+        marker_span_arrays(v, lo, hi, v.bucket[lo >> v.shift], v.bucket[hi >> v.shift], &f, &l, st);
     } else {
-        uint64_t a = 0, z = ix.mk_nruns;
-        while (a < z) { const uint64_t m = a + ((z - a) >> 1); if (ix.mk_end[m] < lo) a = m + 1; else z = m; }
+        uint64_t a = 0, z = v.nruns;
+        while (a < z) { const uint64_t m = a + ((z - a) >> 1); if (v.end[m] < lo) a = m + 1; else z = m; }
         f = a;   // first run with end >= lo
-        a = 0; z = ix.mk_nruns;
-        while (a < z) { const uint64_t m = a + ((z - a) >> 1); if (ix.mk_start[m] <= hi) a = m + 1; else z = m; }
+        a = 0; z = v.nruns;
+        while (a < z) { const uint64_t m = a + ((z - a) >> 1); if (v.start[m] <= hi) a = m + 1; else z = m; }
         l = a;   // one past the last run with start <= hi
     }
     if (l <= f) return false;
     if (st) st[kStatSearchN + 3] += 2;
-    *src = ix.mk_off[f];
-    *cnt = ix.mk_off[l] - *src;
+    *src = v.off[f];
+    *cnt = v.off[l] - *src;
     return true;
+}
+
+// the SA-row table: what every kernel before k_loc_markers.hip asks
+__device__ __forceinline__ bool marker_query(const DevIndex &ix, uint64_t lo, uint64_t hi, uint64_t *src, uint64_t *cnt, unsigned long long *st = nullptr) {
+    return marker_query(sa_marker_view(ix), lo, hi, src, cnt, st);
 }
 
 // ---- K1 / K2 ------------------------------------------------------------------------------------

@@ -351,6 +351,13 @@ class RowBowt {
         detail::check(rc, "load_ftab (the .ftab must be the one rb_build -f made for this index)");
     }
     uint64_t ftab_k() const { return ft_k_; }
+    // the marker index keyed by text position, <prefix>.midx (rle_window_arr::load, rb_markers_tsa.cpp:99-101): what
+    // find_loc_markers_greedy_seeding_batch answers from.  A missing file exits 1 with a message.
+    void load_text_markers(const std::string &fname) {
+        const int rc = rbg_load_text_markers(ix_.get(), fname.c_str());
+        if (rc == RBG_EIO) { std::cerr << "bad file: " << fname << std::endl; std::exit(1); }
+        detail::check(rc, "load_text_markers");
+    }
     void disable_ft() { disable_ft_ = true; }   // rowbowt.hpp:760-766
     void enable_ft() { disable_ft_ = false; }
 
@@ -394,6 +401,27 @@ class RowBowt {
         detail::LibBuf buf;
         detail::check(rbg_markers_at(ix_.get(), lo.data(), hi.data(), N, mk_off.data(), &buf.p), "rbg_markers_at");
         mk.assign(buf.p, buf.p + mk_off[N]);
+    }
+
+    // rb_markers_tsa.cpp:76-88 for many reads: find_locs_greedy_seeding(query, min_length, max_hits), and for every location l the markers
+    // midx.at_range(l, l + query.size() - 1); locs / mk are concatenated per read (loc_off / mk_off, N + 1 each), a read's markers in the
+    // order of its locations.  Needs load_text_markers; without a toehold SA every list is empty, as find_locs_greedy_seeding's are.
+    void find_loc_markers_greedy_seeding_batch(const std::vector<std::string> &queries, uint64_t min_length, uint64_t max_hits,
+                                               std::vector<uint64_t> &loc_off, std::vector<uint64_t> &locs, std::vector<uint64_t> &mk_off,
+                                               std::vector<MarkerT> &mk) const {
+        const uint64_t N = queries.size();
+        loc_off.assign(N + 1, 0);
+        mk_off.assign(N + 1, 0);
+        locs.clear();
+        mk.clear();
+        if (!has_tsa_) return;
+        detail::Batch b;
+        for (const auto &q : queries) b.add(q);
+        detail::LibBuf lbuf, mbuf;
+        detail::check(rbg_find_loc_markers_greedy_seeding(ix_.get(), b.data(), b.off.data(), N, min_length, max_hits, loc_off.data(), &lbuf.p,
+                                                          mk_off.data(), &mbuf.p), "rbg_find_loc_markers_greedy_seeding");
+        locs.assign(lbuf.p, lbuf.p + loc_off[N]);
+        mk.assign(mbuf.p, mbuf.p + mk_off[N]);
     }
 
     // get_seeds_greedy_w_sample (w_sample) or get_seeds_greedy for many reads: out[i] = the list of queries[i]
