@@ -45,16 +45,32 @@ struct PackedBits {   // per-lane reader of a packed read: peek / drop of up to 
     }
 };
 
-// a slot of the jump table as two 16-byte loads (rbg_jump.h jump_probe)
-struct JumpLoad {
-    const uint4 *__restrict__ tab;
-    __device__ __forceinline__ void operator()(uint64_t b, uint32_t s, uint32_t kw[4], uint32_t vw[4]) const {
-        const uint4 *sl = tab + (4 * b + 2 * s);
-        const uint4 k = sl[0], v = sl[1];
-        kw[0] = k.x; kw[1] = k.y; kw[2] = k.z; kw[3] = k.w;
-        vw[0] = v.x; vw[1] = v.y; vw[2] = v.z; vw[3] = v.w;
+// The probe of the jump table (rbg_jump.h) by the whole wave: EVERY lane calls, `probing` says whether the lane has a key to look up.  A lane
+// reading its own 64-byte bucket would issue two to four 16-byte requests to one sector, in up to three dependent round trips (slot 0, slot 1,
+// the next bucket); here the lane's quad fetches the bucket as one request (rbg_runs2_device.hpp quad_fetch_issue / _take, as the bucket records
+// of the steps) and jump_bucket settles both slots from its sixteen words.  A lane that is not probing, or has its answer, names bucket 0 of
+// the table; the rounds go on while any lane's chain does (about 0.2 buckets per read beyond the first).  `tile` (GLDS) must be free: no step
+// is in flight.  Returns true on a hit (v = {lo, hi, toehold}); buckets = buckets this lane's probe read.
+template <bool GLDS>
+__device__ __forceinline__ bool jump_probe_wave(const void *__restrict__ tab, const uint64_t nb, const bool probing, const JumpKey &key, uint32_t v[3],
+                                                uint32_t &buckets, lds_byte *tile) {
+    uint32_t state = probing ? kJumpNext : kJumpAbsent;           // kJumpNext: undecided, the bucket `b` is the next to read
+    uint64_t b = probing ? jump_home(jump_hash(key), nb) : 0u;
+    uint64_t left = nb;                                            // at most nb buckets (jump_probe)
+    while (__ballot(state == kJumpNext)) {
+        const bool undecided = state == kJumpNext;
+        uint32_t w[16];
+        quad_fetch_issue<GLDS>(reinterpret_cast<uint64_t>(tab) + (undecided ? b : 0u) * kJumpBucketBytes, w, tile);
+        quad_fetch_take<GLDS>(w, tile);
+        if (undecided) {
+            ++buckets;
+            state = jump_bucket(w, key, v);
+            b = jump_next(b, nb);
+            if (--left == 0 && state == kJumpNext) state = kJumpAbsent;
+        }
     }
-};
+    return state <= kJumpHit1;
+}
 
 // (the staging of a wave's reads as 2-bit codes in LDS -- stage_read, StageTab, kStageCap -- lives in rbg_runs_device.hpp: the seeding kernels use it too)
 // GLDS: the bucket records arrive by LDS-direct loads (rbg_runs2_device.hpp lane_lf2_quad) instead of quad permutes
@@ -140,14 +156,16 @@ __global__ __launch_bounds__(512, STATS ? 2 : 4) void k_find_range_runs(const De
             uint64_t pend_e = 0;
             ByteCursor rd{reinterpret_cast<const uint4 *>(seqs), ~uint64_t(0), make_uint4(0, 0, 0, 0)};
             // JUMP (rbg_jump.h): a staged read of at least jump_k symbols looks its last jump_k up in the table of the K-mers that occur -- one
-            // probe in place of the ftab entry and the first (jump_k - ftab_k) / 8 steps; a key that is absent takes the ftab path below
+            // probe in place of the ftab entry and the first (jump_k - ftab_k) / 8 steps; a key that is absent takes the ftab path below.
+            // The probe is the wave's (jump_probe_wave): every lane enters it, `probing` is a predicate.
             bool jumped = false;
             if constexpr (STAGED && sizeof(P) == 4) {
-                if (valid && ix.jump && m32 >= ix.jump_k) {
+                if (ix.jump) {                                     // (wave-uniform)
+                    const bool probing = valid && m32 >= ix.jump_k;
                     JumpKey key{{codes[0], codes[64], codes[128], codes[192]}};   // the first 64 symbols in consumption order
                     jump_key_mask(key, ix.jump_k);
                     uint32_t v[3] = {0, 0, 0}, nbk = 0;
-                    if (jump_probe(JumpLoad{static_cast<const uint4 *>(ix.jump)}, ix.jump_buckets, key, v, nbk)) {
+                    if (jump_probe_wave<GLDS>(ix.jump, ix.jump_buckets, probing, key, v, nbk, tile)) {
                         lo = v[0]; hi = v[1];
                         if (TOEHOLD) k = v[2] == 0xFFFFFFFFu ? ~uint64_t(0) : static_cast<uint64_t>(v[2]);
                         p -= ix.jump_k;

@@ -3,7 +3,8 @@
 // ftab_k symbols, this table only the words that occur, so K can be four or five times longer.  A read of at least K symbols
 // looks up its last K in one probe (usually one 64-byte bucket) instead of the ftab entry and (K - ftab_k) / 8 bucket records;
 // a key that is absent -- the read has a symbol in its last K that the text does not -- costs one probe and the read takes the
-// ftab path.  Built at load by the library's own kernels (k_jump.hip), result-neutral by construction.
+// ftab path.  A probe reads whole buckets: the search kernel fetches a bucket as ONE 64-byte request of the owner's quad of lanes (k_runs.hip
+// jump_probe_wave) and jump_bucket below settles both of its slots from those sixteen words.  Built at load by the library's own kernels (k_jump.hip), result-neutral by construction.
 //
 // Key: the K symbols as 2-bit major codes in CONSUMPTION order (symbol t of the key = the read's symbol m - 1 - t at bits
 // [2t, 2t + 2) of the 128-bit key; bits from 2K up are zero) -- the layout of the staged reads (rbg_runs_device.hpp) and of the
@@ -69,6 +70,26 @@ RBG_JUMP_HD uint64_t jump_home(uint64_t h, uint64_t nb) {
     return ((h >> 32) * nb) >> 32;
 }
 
+// One bucket settles a probe.  w = the bucket's 16 words (slot 0, slot 1: key[4], lo, hi, toehold, tag each), read in the probe's order --
+// slot 0, then slot 1: kJumpHit0 / kJumpHit1 = the key sits in that slot (v = {lo, hi, toehold}), kJumpAbsent = an empty slot came before a
+// match (the chain ends here: the key is not in the table), kJumpNext = both slots hold other keys, the chain goes on in the next bucket.
+// Host and device: the kernel fetches a bucket whole (k_runs.hip jump_probe_wave) and decides it here, as jump_probe below does.
+constexpr uint32_t kJumpHit0 = 0, kJumpHit1 = 1, kJumpAbsent = 2, kJumpNext = 3;
+RBG_JUMP_HD uint32_t jump_bucket(const uint32_t w[16], const JumpKey &key, uint32_t v[3]) {
+    for (uint32_t s = 0; s < 2; ++s) {
+        const uint32_t *sl = w + kJumpSlotWords * s;
+        if (sl[7] == kJumpEmptyTag) return kJumpAbsent;
+        if (sl[0] == key.w[0] && sl[1] == key.w[1] && sl[2] == key.w[2] && sl[3] == key.w[3]) {
+            v[0] = sl[4]; v[1] = sl[5]; v[2] = sl[6];
+            return s;
+        }
+    }
+    return kJumpNext;
+}
+
+// the bucket after b in a chain: linear, wrapping at the table's end
+RBG_JUMP_HD uint64_t jump_next(uint64_t b, uint64_t nb) { return b + 1 == nb ? 0 : b + 1; }
+
 // The probe.  load(bucket, slot, key_words[4], val_words[4]) reads one slot.  On a hit fills v = {lo, hi, toehold} and returns true;
 // `buckets` = buckets read (the STATS count).  At most nb buckets are visited (a table that is never full ends far sooner).
 template <typename Load>
@@ -76,16 +97,12 @@ RBG_JUMP_HD bool jump_probe(const Load &load, uint64_t nb, const JumpKey &key, u
     uint64_t b = jump_home(jump_hash(key), nb);
     for (uint64_t step = 0; step < nb; ++step) {
         ++buckets;
-        for (uint32_t s = 0; s < 2; ++s) {
-            uint32_t kw[4], vw[4];
-            load(b, s, kw, vw);
-            if (vw[3] == kJumpEmptyTag) return false;
-            if (kw[0] == key.w[0] && kw[1] == key.w[1] && kw[2] == key.w[2] && kw[3] == key.w[3]) {
-                v[0] = vw[0]; v[1] = vw[1]; v[2] = vw[2];
-                return true;
-            }
-        }
-        b = b + 1 == nb ? 0 : b + 1;
+        uint32_t w[16];
+        load(b, 0, w, w + 4);
+        load(b, 1, w + 8, w + 12);
+        const uint32_t r = jump_bucket(w, key, v);
+        if (r != kJumpNext) return r != kJumpAbsent;
+        b = jump_next(b, nb);
     }
     return false;
 }

@@ -526,6 +526,44 @@ __device__ __forceinline__ void glds_round(const uint32_t a_lo, const uint32_t a
     const uint64_t an = (static_cast<uint64_t>(quad_bcast<r>(a_hi)) << 32) | quad_bcast<r>(a_lo);
     __builtin_amdgcn_global_load_lds(reinterpret_cast<const RBG_GLOBAL void *>(an + 16u * p), reinterpret_cast<__attribute__((address_space(3))) void *>(tile + r * kTileRound), 16, 0, 0);
 }
+// The quad fetch of one 64-byte record per lane, in two halves so that a caller may issue loads of its own while these fly (lane_lf2_quad's second
+// record).  Every lane of the wave calls both; a0 = the address of the lane's record (a lane with nothing to fetch names a record that exists).
+// GLDS: `tile` must be free -- nothing of an earlier fetch unread -- and is free again on return from quad_fetch_take (the two fences).
+template <bool GLDS>
+__device__ __forceinline__ void quad_fetch_issue(const uint64_t a0, uint32_t (&w)[16], lds_byte *tile) {
+    const uint32_t p = threadIdx.x & 3u;
+    const uint32_t a_lo = static_cast<uint32_t>(a0), a_hi = static_cast<uint32_t>(a0 >> 32);
+    if constexpr (GLDS) {
+        glds_round<0>(a_lo, a_hi, p, tile);
+        glds_round<1>(a_lo, a_hi, p, tile);
+        glds_round<2>(a_lo, a_hi, p, tile);
+        glds_round<3>(a_lo, a_hi, p, tile);
+    } else {
+#define RBG_QUAD_ROUND(r)                                                                                                             \
+    {                                                                                                                                  \
+        const uint64_t an = (static_cast<uint64_t>(quad_bcast<r>(a_hi)) << 32) | quad_bcast<r>(a_lo);                                  \
+        const u32x4 t = *as_global<u32x4>(reinterpret_cast<const void *>(an + 16u * p));                                                \
+        w[4 * r] = t.x; w[4 * r + 1] = t.y; w[4 * r + 2] = t.z; w[4 * r + 3] = t.w;                                                      \
+    }
+        RBG_QUAD_ROUND(0) RBG_QUAD_ROUND(1) RBG_QUAD_ROUND(2) RBG_QUAD_ROUND(3)
+#undef RBG_QUAD_ROUND
+    }
+}
+template <bool GLDS>
+__device__ __forceinline__ void quad_fetch_take(uint32_t (&w)[16], lds_byte *tile) {
+    if constexpr (GLDS) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the LDS-direct loads are this wave's own: no barrier, the counter is the wave's)
+        const lds_byte *own = tile + (threadIdx.x & 3u) * kTileRound + (threadIdx.x & 60u) * 16u;
+        typedef __attribute__((address_space(3))) const u32x4 lds_u32x4;
+        const u32x4 t0 = reinterpret_cast<lds_u32x4 *>(own)[0], t1 = reinterpret_cast<lds_u32x4 *>(own)[1], t2 = reinterpret_cast<lds_u32x4 *>(own)[2],
+                    t3 = reinterpret_cast<lds_u32x4 *>(own)[3];
+        w[0] = t0.x; w[1] = t0.y; w[2] = t0.z; w[3] = t0.w; w[4] = t1.x; w[5] = t1.y; w[6] = t1.z; w[7] = t1.w;
+        w[8] = t2.x; w[9] = t2.y; w[10] = t2.z; w[11] = t2.w; w[12] = t3.x; w[13] = t3.y; w[14] = t3.z; w[15] = t3.w;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (the record is in registers before the next fetch's loads may land on the tile)
+    } else {
+        quad_transpose16(w, threadIdx.x & 3u);
+    }
+}
 // LEAN: the second record (hi + 1 in another bucket) is fetched into the first one's registers once that is answered (the seeding kernels)
 // R: the table's hot word (load_run_tab; the caller may have fetched it a step ahead)
 template <typename P, bool STATS = false, bool LEAN = false, bool GLDS = false>
@@ -536,40 +574,15 @@ __device__ __forceinline__ void lane_lf2_quad(const RunSearch2<P> &S, const bool
     const bool by_rec = stepping && S.rec[d] != nullptr;
     if (stepping && !by_rec) lane_lf2_tab<P, STATS, LEAN>(S, d, rec, R, q0, q1, out, st);   // (a depth with directories over its run lists: the lane by itself)
     if (__ballot(by_rec) == 0) return;                                            // (nobody's quad has a record to fetch in this step)
-    const uint32_t p = threadIdx.x & 3u;
     const uint64_t b0 = by_rec ? pos_bucket<P>(q0, sh) : 0u, b1 = by_rec ? pos_bucket<P>(q1, sh) : 0u;
     const char *recs = static_cast<const char *>(by_rec ? S.rec[d] : S.rec_any);
     const uint64_t a0 = reinterpret_cast<uint64_t>(recs) + (by_rec ? (R.dir_off + b0) * 64u : 0u);   // (a lane without a record to fetch names the first record there is)
-    const uint32_t a_lo = static_cast<uint32_t>(a0), a_hi = static_cast<uint32_t>(a0 >> 32);
     LaneRec r0, r1;
     uint32_t (&w0)[16] = r0.w;
     const bool two = by_rec && b1 != b0;
-    if constexpr (GLDS) {
-        glds_round<0>(a_lo, a_hi, p, tile);
-        glds_round<1>(a_lo, a_hi, p, tile);
-        glds_round<2>(a_lo, a_hi, p, tile);
-        glds_round<3>(a_lo, a_hi, p, tile);
-        if constexpr (!LEAN) { if (two) r1.load(recs, R.dir_off + b1); }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the LDS-direct loads are this wave's own: no barrier, the counter is the wave's)
-        const lds_byte *own = tile + (threadIdx.x & 3u) * kTileRound + (threadIdx.x & 60u) * 16u;
-        typedef __attribute__((address_space(3))) const u32x4 lds_u32x4;
-        const u32x4 t0 = reinterpret_cast<lds_u32x4 *>(own)[0], t1 = reinterpret_cast<lds_u32x4 *>(own)[1], t2 = reinterpret_cast<lds_u32x4 *>(own)[2],
-                    t3 = reinterpret_cast<lds_u32x4 *>(own)[3];
-        w0[0] = t0.x; w0[1] = t0.y; w0[2] = t0.z; w0[3] = t0.w; w0[4] = t1.x; w0[5] = t1.y; w0[6] = t1.z; w0[7] = t1.w;
-        w0[8] = t2.x; w0[9] = t2.y; w0[10] = t2.z; w0[11] = t2.w; w0[12] = t3.x; w0[13] = t3.y; w0[14] = t3.z; w0[15] = t3.w;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (the record is in registers before the next step's loads may land on the tile)
-    } else {
-#define RBG_QUAD_ROUND(r)                                                                                                             \
-    {                                                                                                                                  \
-        const uint64_t an = (static_cast<uint64_t>(quad_bcast<r>(a_hi)) << 32) | quad_bcast<r>(a_lo);                                  \
-        const u32x4 t = *as_global<u32x4>(reinterpret_cast<const void *>(an + 16u * p));                                                \
-        w0[4 * r] = t.x; w0[4 * r + 1] = t.y; w0[4 * r + 2] = t.z; w0[4 * r + 3] = t.w;                                                  \
-    }
-        RBG_QUAD_ROUND(0) RBG_QUAD_ROUND(1) RBG_QUAD_ROUND(2) RBG_QUAD_ROUND(3)
-#undef RBG_QUAD_ROUND
-        if constexpr (!LEAN) { if (two) r1.load(recs, R.dir_off + b1); }
-        quad_transpose16(w0, p);
-    }
+    quad_fetch_issue<GLDS>(a0, w0, tile);
+    if constexpr (!LEAN) { if (two) r1.load(recs, R.dir_off + b1); }
+    quad_fetch_take<GLDS>(w0, tile);
     if (!by_rec) return;
     out.F = 0;
     const uint32_t al0 = W ? pos_bucket_base32(q0, sh) - (1u << S.fill) : 0u;
