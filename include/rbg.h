@@ -394,6 +394,38 @@ int rbg_wait_text(rbg_index *, const char *text);
 int rbg_release_text(rbg_index *, const char *text);
 /* make `count` pinned text buffers of `bytes` now (pinning a few hundred MB takes tenths of a second: a tool does it before its clock starts) */
 int rbg_reserve_text(rbg_index *, uint64_t bytes, int count);
+/* ---- rb_markers' report (what the tool prints), made on the device --------------------------------------------------------------
+ * Everything rb_markers does between get_markers_greedy_seeding / get_markers_lmems and its output (rb_markers.cpp:228-315, :365-382,
+ * :396-413, :429-519), for a batch of RAW reads: both strands (sequence 2i = read i through seq_ntoa_table -- ACGT of either case, N/n -> 'A',
+ * any other byte -> 'N' --, 2i + 1 = its reverse complement), the seeding, per callback record the min_range gate, the marker_cmp sort and
+ * std::unique of its markers and (heuristic mode) clear_if_conflicting(read_len) and filter_identical_pos, then per read the records that
+ * are printed, in print order: default mode forward then reverse; heuristic mode the strand first_fwd[i] names first (NULL: forward), the
+ * other one only if the first did not set the stop rule, best-strand-only and min-seed-length as the reference applies them.  A record
+ * with an empty range is never printed.  The coin (one std::mt19937 bit stream over the whole input) stays with the caller. */
+#define RBG_REPORT_LMEM 1u               /* seed through get_markers_lmems (needs ftab_k > 0) instead of get_markers_greedy_seeding */
+#define RBG_REPORT_HEURISTIC 2u          /* worker_heuristic (min_seed_len, the flags below) instead of worker */
+#define RBG_REPORT_BEST_STRAND 4u
+#define RBG_REPORT_CLEAR_CONFLICTING 8u
+#define RBG_REPORT_CLEAR_IDENTICAL 16u
+typedef struct rbg_report_params {
+    uint64_t wsize, max_range, min_range, ftab_k, read_len, min_seed_len;
+    uint32_t flags;   /* RBG_REPORT_LMEM | _HEURISTIC | _BEST_STRAND | _CLEAR_CONFLICTING | _CLEAR_IDENTICAL */
+} rbg_report_params_t;
+typedef struct rbg_report_seed { uint64_t range_size, query_start, query_len, mk_begin, mk_end; uint32_t strand /*0 +, 1 -*/, pad; } rbg_report_seed_t;
+/* seed_off[N+1]: read i prints records [seed_off[i], seed_off[i+1]) of *seeds; a record's markers are (*mk)[mk_begin, mk_end), sorted and unique,
+ * *mk dense in print order.  Both through rbg_free_buffer.  A line of rb_markers is
+ *     <name> <range_size> <+|-> <query_start> <query_len> { " <seq>/<pos>/<allele>" per marker | " ." } "\n".
+ * RBG_EARG: ftab_k - 1 > wsize (rowbowt.hpp:423-426), RBG_REPORT_LMEM with ftab_k == 0 (:346-349), unknown flags.  A read shorter than ftab_k in
+ * greedy mode: its first lookup is a miss (see rbg_get_markers_greedy_seeding).  Works without a marker array (no record has markers).  A large
+ * batch is walked in passes of bounded device memory (greedy: 64 MiB of reads, lmem: 4 Mi records; RBG_REPORT_CHUNK=<read bytes> overrides). */
+int rbg_markers_report(rbg_index *, const uint8_t *seqs, const uint64_t *off, uint64_t N, const uint8_t *first_fwd /* nullable */,
+                       const rbg_report_params_t *params, uint64_t *seed_off, rbg_report_seed_t **seeds, uint64_t **mk);
+/* The same as text, the lines written by kernels: names are N spans of name_base; *text is one of the handle's pinned text buffers, owned as
+ * rbg_align_text's (rbg_wait_text before the first byte is read, rbg_release_text after, rbg_reserve_text to pin ahead of the clock).  An empty
+ * report gives *text = NULL, *text_len = 0. */
+int rbg_markers_report_text(rbg_index *, const uint8_t *seqs, const uint64_t *off, uint64_t N, const uint8_t *first_fwd /* nullable */,
+                            const rbg_report_params_t *params, const char *name_base, const uint64_t *name_begin, const uint32_t *name_len,
+                            const char **text, uint64_t *text_len);
 /* ---- queries, device-resident buffers (HBM in, HBM out; asynchronous on `stream`) ---------- */
 /* d_seqs: the reads back to back as in the host calls, in device memory, 16-BYTE ALIGNED (RBG_EARG otherwise), and the allocation must reach the next
  * multiple of 16 bytes at or past its last read's end: the kernels fetch reads as aligned 16-byte chunks (the bytes beyond a read's end are never used).
@@ -509,6 +541,30 @@ int rbg_toehold_chkpnts_slots_dev(rbg_index *, const uint64_t *d_off, uint64_t N
 int rbg_find_range_w_toehold_chkpnts_dev(rbg_index *, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t wsize,
                                          const uint64_t *d_slot_off, uint64_t *d_cnt, uint64_t *d_lo, uint64_t *d_hi,
                                          uint64_t *d_qstart, uint64_t *d_qend, uint64_t *d_ssamp, void *stream);
+/* The device steps of rbg_markers_report.  rbg_read_strands_dev: d_seqs / d_off[N+1] as in the searches above (16-byte aligned, the allocation reaching the
+ * next multiple of 16; d_off[0] need not be 0) -> the 2N-sequence batch d_seqs2 (16-byte aligned, rbg_read_strands_bytes(total_bytes) bytes, total_bytes
+ * any upper bound on d_off[N] - d_off[0]: the layout the *_dev searches require) and d_off2[2N+1] (d_off2[2i] = 2 (d_off[i] - d_off[0]),
+ * d_off2[2i+1] = d_off2[2i] + length of read i). */
+size_t rbg_read_strands_bytes(uint64_t total_bytes);
+int rbg_read_strands_dev(rbg_index *, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t total_bytes, uint8_t *d_seqs2, uint64_t *d_off2,
+                         void *stream);
+/* In place over what rbg_marker_seeds_fill[_log]_dev / rbg_marker_lmems_fill_dev leave: for every record the survivors of {range_size >= min_range gate,
+ * marker_cmp sort, unique, and by flags (RBG_REPORT_CLEAR_CONFLICTING, RBG_REPORT_CLEAR_IDENTICAL; others ignored) clear_if_conflicting(read_len) and
+ * filter_identical_pos} end up at d_mk[mk_begin, mk_begin + c) and mk_end = mk_begin + c; what lies in the rest of the record's own stretch is
+ * unspecified, no other byte of d_mk is written.  Segments may be of any length (S < 2^32).  d_tmp: rbg_marker_seeds_canon_tmp_bytes(S) bytes, 4-byte
+ * aligned.  A group of 4, 16 or 64 lanes sorts a short segment (the width chosen on the device from the mean length, or forced by the environment
+ * variable RBG_REPORT_GROUP for tests and A/Bs), longer segments get a workgroup each; the result does not depend on the path. */
+size_t rbg_marker_seeds_canon_tmp_bytes(uint64_t S);
+int rbg_marker_seeds_canon_dev(rbg_index *, rbg_marker_seed_t *d_seeds, uint64_t S, uint64_t *d_mk, uint64_t min_range, uint32_t flags, uint64_t read_len,
+                               void *d_tmp, size_t tmp_bytes, void *stream);
+/* Per read the printed records in print order: d_seed_off[2N+1] = the records of every sequence of the 2N batch (rbg_marker_seeds_plan*_dev's scan; d_off2
+ * itself for lmem seeds), d_off2[2N+1] from rbg_read_strands_dev, d_first_fwd[N] the coins (nullable).  params is a HOST pointer (read_len, min_seed_len
+ * and flags are used).  Writes d_rep_off[N+1] (exclusive scan of the records per read), the records at d_out[d_rep_off[i] ...] (room for as many as
+ * there are input records) and, when d_out_read != NULL, each record's read.  d_tmp: rbg_report_select_tmp_bytes(N). */
+size_t rbg_report_select_tmp_bytes(uint64_t N);
+int rbg_report_select_dev(rbg_index *, const rbg_marker_seed_t *d_seeds, const uint64_t *d_seed_off, const uint64_t *d_off2, uint64_t N,
+                          const uint8_t *d_first_fwd, const rbg_report_params_t *params, uint64_t *d_rep_off, rbg_report_seed_t *d_out,
+                          uint32_t *d_out_read, void *d_tmp, size_t tmp_bytes, void *stream);
 /* markers, same two-phase shape */
 int rbg_markers_plan_dev(rbg_index *, const uint64_t *d_lo, const uint64_t *d_hi, uint64_t N,
                          uint64_t *d_mk_off, void *d_tmp, size_t tmp_bytes, void *stream);

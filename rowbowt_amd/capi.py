@@ -71,6 +71,25 @@ class JumpInfo(C.Structure):
     _fields_ = [("k", U64), ("keys", U64), ("bytes", U64), ("buckets", U64), ("build_ms", C.c_double)]
 
 
+class ReportParams(C.Structure):
+    """rbg_report_params_t"""
+    _fields_ = [(n, U64) for n in ("wsize", "max_range", "min_range", "ftab_k", "read_len", "min_seed_len")] + [("flags", C.c_uint32)]
+
+
+REPORT_LMEM, REPORT_HEURISTIC, REPORT_BEST_STRAND, REPORT_CLEAR_CONFLICTING, REPORT_CLEAR_IDENTICAL = 1, 2, 4, 8, 16
+# rbg_report_seed_t as a numpy record
+REPORT_SEED = np.dtype([("range_size", "<u8"), ("query_start", "<u8"), ("query_len", "<u8"), ("mk_begin", "<u8"), ("mk_end", "<u8"),
+                        ("strand", "<u4"), ("pad", "<u4")])
+
+
+def report_params(wsize=19, max_range=1000, min_range=0, ftab_k=0, read_len=101, min_seed_len=0, lmem=False, heuristic=False, best_strand=False,
+                  clear_conflicting=False, clear_identical=False):
+    """rb_markers' options as an rbg_report_params_t (the defaults are the tool's, rb_markers.cpp:22-40)"""
+    flags = ((REPORT_LMEM if lmem else 0) | (REPORT_HEURISTIC if heuristic else 0) | (REPORT_BEST_STRAND if best_strand else 0)
+             | (REPORT_CLEAR_CONFLICTING if clear_conflicting else 0) | (REPORT_CLEAR_IDENTICAL if clear_identical else 0))
+    return ReportParams(wsize, max_range & MAXU, min_range, ftab_k, read_len, min_seed_len, flags)
+
+
 # every symbol include/rbg.h declares: (name, restype, argtypes)
 _PROTOS = [
     ("rbg_abi_version", C.c_int, []),
@@ -170,6 +189,14 @@ _PROTOS = [
     ("rbg_loc_markers_fill_dev", C.c_int, [VP, VP, VP, VP, U64, VP, VP, VP]),
     ("rbg_markers_at_locs", C.c_int, [VP, VP, VP, VP, U64, VP, C.POINTER(VP)]),
     ("rbg_find_loc_markers_greedy_seeding", C.c_int, [VP, VP, VP, U64, U64, U64, VP, C.POINTER(VP), VP, C.POINTER(VP)]),
+    ("rbg_read_strands_bytes", C.c_size_t, [U64]),
+    ("rbg_read_strands_dev", C.c_int, [VP, VP, VP, U64, U64, VP, VP, VP]),
+    ("rbg_marker_seeds_canon_tmp_bytes", C.c_size_t, [U64]),
+    ("rbg_marker_seeds_canon_dev", C.c_int, [VP, VP, U64, VP, U64, C.c_uint32, U64, VP, C.c_size_t, VP]),
+    ("rbg_report_select_tmp_bytes", C.c_size_t, [U64]),
+    ("rbg_report_select_dev", C.c_int, [VP, VP, VP, VP, U64, VP, VP, VP, VP, VP, VP, C.c_size_t, VP]),
+    ("rbg_markers_report", C.c_int, [VP, VP, VP, U64, VP, VP, VP, C.POINTER(VP), C.POINTER(VP)]),
+    ("rbg_markers_report_text", C.c_int, [VP, VP, VP, U64, VP, VP, VP, VP, VP, C.POINTER(VP), C.POINTER(U64)]),
     ("rbg_set_default_option", C.c_int, [C.c_int, C.c_int64]),
     ("rbg_get_default_option", C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
 ]
@@ -579,6 +606,39 @@ class RowBowt:
         try:
             _check(self.L.rbg_wait_text(self.h, text), "rbg_wait_text")
             return C.string_at(text, n.value)
+        finally:
+            self.L.rbg_release_text(self.h, text)
+
+    def markers_report(self, seqs, off, params, first_fwd=None):
+        """rbg_markers_report: what rb_markers prints for a batch of RAW reads, as records -> (seed_off[N+1], records (REPORT_SEED), mk);
+        read i prints records[seed_off[i]:seed_off[i+1]], a record's markers are mk[mk_begin:mk_end] (sorted, unique).  params: report_params(...);
+        first_fwd: the heuristic worker's coin per read (None: forward first)"""
+        N = len(off) - 1
+        seed_off = np.zeros(N + 1, np.uint64)
+        coin = None if first_fwd is None else np.ascontiguousarray(first_fwd, dtype=np.uint8)
+        ps, pm = VP(), VP()
+        _check(self.L.rbg_markers_report(self.h, _p(seqs), _p(off), N, _p(coin), C.byref(params), _p(seed_off), C.byref(ps), C.byref(pm)), "rbg_markers_report")
+        S = int(seed_off[N])
+        recs = _take(ps, 6 * S).view(REPORT_SEED)
+        nmk = int(recs["mk_end"][-1]) if S else 0
+        return seed_off, recs, _take(pm, nmk)
+
+    def markers_report_text(self, seqs, off, names, params, first_fwd=None):
+        """rbg_markers_report_text: rb_markers' stdout for a batch of RAW reads (bytes), written on the device; names = list of bytes"""
+        N = len(off) - 1
+        coin = None if first_fwd is None else np.ascontiguousarray(first_fwd, dtype=np.uint8)
+        blob = b"".join(names)
+        nlen = np.array([len(x) for x in names], dtype=np.uint32)
+        nbeg = np.zeros(len(names), dtype=np.uint64)
+        if len(names) > 1:
+            nbeg[1:] = np.cumsum(nlen[:-1], dtype=np.uint64)
+        buf = C.create_string_buffer(blob, len(blob) + 1)
+        text, n = VP(), U64()
+        _check(self.L.rbg_markers_report_text(self.h, _p(seqs), _p(off), N, _p(coin), C.byref(params), buf, _p(nbeg), _p(nlen), C.byref(text), C.byref(n)),
+               "rbg_markers_report_text")
+        try:
+            _check(self.L.rbg_wait_text(self.h, text), "rbg_wait_text")
+            return C.string_at(text, n.value) if n.value else b""
         finally:
             self.L.rbg_release_text(self.h, text)
 

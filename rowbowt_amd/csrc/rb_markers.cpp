@@ -5,7 +5,8 @@
 // reference's thread pool (rb_markers.cpp:318-535) becomes one batched call into the MI355X engine
 // (rbg_get_markers_greedy_seeding, include/rbg.h) over 2N sequences; what the reference's callback
 // and worker do afterwards (sort/unique the markers, the seed filters, the text) runs on host
-// threads, in read order -- the order the reference produces with --threads 1.
+// threads, in read order -- the order the reference produces with --threads 1 -- or, with --device-format, on the device
+// as well (rbg_markers_report_text: the raw reads go in, the lines come out; same stdout).
 //
 // One stdout line per seed (rb_markers.cpp:253-262):
 //   "<name> <range_size> <+|-> <query_start> <query_len>" { " <seq>/<pos>/<allele>" | " ." } "\n"
@@ -64,6 +65,7 @@ struct RbMarkersArgs {  // rb_markers.cpp:22-40
     uint64_t threads = 8, max_tasks = 1024, read_len = 101, min_seed_len = 0;  // threads: host formatting workers (the reference's default of 1 is its search pool)
     int clear_conflicting = 0, clear_identical = 0, best_strand = 0, heuristic = 0;
     int device = 0;
+    int device_format = 0, host_format = 0;   // --device-format: the lines are made on the device (rbg_markers_report_text); --host-format (the default): on host threads
     uint64_t batch = 1u << 18;   // (2^17 kept more batches per window in flight but paid the library call's fixed costs twice as often: 0.32 against 0.25 s per 2 M reads)
 };
 
@@ -80,6 +82,7 @@ void print_help() {  // rb_markers.cpp:44-54
     fprintf(stderr, "                                     (stdout as the reference's; its per-step debug text on stderr is not printed)\n");
     fprintf(stderr, "    --gpu <n>                        HIP device ordinal (default 0)\n");
     fprintf(stderr, "    --batch <n>                      reads per GPU batch (default 262144)\n");
+    fprintf(stderr, "    --device-format | --host-format  sort, filter and print the seeds on the device | on host threads (default; same stdout)\n");
     fprintf(stderr, "    <input_prefix>                   index prefix\n");
     fprintf(stderr, "    <input_fastq>                    input fastq\n");
 }
@@ -101,6 +104,8 @@ RbMarkersArgs parse_args(int argc, char **argv) {  // rb_markers.cpp:56-134
                                            {"min-seed-length", required_argument, 0, 'y'},
                                            {"clear-conflicting", no_argument, &args.clear_conflicting, 1},
                                            {"clear-identical", no_argument, &args.clear_identical, 1},
+                                           {"device-format", no_argument, &args.device_format, 1},
+                                           {"host-format", no_argument, &args.host_format, 1},
                                            {"gpu", required_argument, 0, 'G'},
                                            {"batch", required_argument, 0, 'B'},
                                            {0, 0, 0, 0}};
@@ -145,6 +150,7 @@ RbMarkersArgs parse_args(int argc, char **argv) {  // rb_markers.cpp:56-134
     if (args.batch == 0) args.batch = 1;
     if (args.lmem) args.batch = std::min<uint64_t>(args.batch, 16384);   // 2 x 16384 strands of 150 bp: 236 MB of records per batch
     if (args.threads == 0) args.threads = 1;
+    if (args.host_format) args.device_format = 0;
     return args;
 }
 
@@ -366,12 +372,53 @@ struct SeedSlot {
     BatchSeeds r;
     int rc = RBG_OK;
     double t_strands = 0, t_query = 0;
+    std::vector<uint8_t> first_fwd;   // the heuristic worker's coins of the batch, drawn in file order before its query
+    // --device-format: the batch's lines in one of the library's pinned text buffers
+    const char *text = nullptr;
+    uint64_t text_len = 0;
+    bool on_device = false;           // false: this batch went the host way
 };
+
+// :483: one coin per read, in file order (the batches are queried ahead of their printing, so the coins are drawn where the queries start)
+void draw_coins(const RbMarkersArgs &args, RandomBoolGenerator &booler, size_t N, SeedSlot &slot) {
+    slot.first_fwd.assign(N, 1);
+    if (args.heuristic)
+        for (size_t i = 0; i < N; ++i) slot.first_fwd[i] = booler.get_bool() ? 1 : 0;
+}
+
+// stage 1 with --device-format: the raw reads go to the library, which makes both strands, seeds, sorts, filters and prints on the device
+// (false: the library could not allocate -- the batch goes the host way)
+bool query_batch_device(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args, const BatchView &b, SeedSlot &slot) {
+    const size_t N = b.size();
+    const auto t0 = std::chrono::steady_clock::now();
+    slot.off.resize(N + 1);
+    slot.off[0] = 0;
+    for (size_t i = 0; i < N; ++i) slot.off[i + 1] = slot.off[i] + b.seq_len(i);
+    slot.seqs.resize(slot.off[N]);
+    for (size_t i = 0; i < N; ++i) memcpy(&slot.seqs[slot.off[i]], b.seq(i), b.seq_len(i));
+    const auto t1 = std::chrono::steady_clock::now();
+    rbg_report_params_t p{};
+    p.wsize = args.wsize; p.max_range = args.max_range; p.min_range = args.min_range; p.ftab_k = rb.ftab_k();
+    p.read_len = args.read_len; p.min_seed_len = args.min_seed_len;
+    p.flags = (args.lmem ? RBG_REPORT_LMEM : 0u) | (args.heuristic ? RBG_REPORT_HEURISTIC : 0u) | (args.best_strand ? RBG_REPORT_BEST_STRAND : 0u) |
+              (args.clear_conflicting ? RBG_REPORT_CLEAR_CONFLICTING : 0u) | (args.clear_identical ? RBG_REPORT_CLEAR_IDENTICAL : 0u);
+    slot.text = nullptr;
+    slot.text_len = 0;
+    slot.rc = rbg_markers_report_text(rb.handle(), reinterpret_cast<const uint8_t *>(slot.seqs.data()), slot.off.data(), N, slot.first_fwd.data(), &p, b.w->base,
+                                      b.w->recs.name_begin.data() + b.w0, b.w->recs.name_len.data() + b.w0, &slot.text, &slot.text_len);
+    if (slot.rc == RBG_ENOMEM) return false;
+    slot.on_device = true;
+    slot.t_strands = std::chrono::duration<double>(t1 - t0).count();
+    slot.t_query = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+    return true;
+}
 
 // stage 1: both strands of every read, one library call for the 2N sequences
 void query_batch(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args, const BatchView &b, SeedSlot &slot) {
     const size_t N = b.size();
     const uint64_t ft_k = rb.ftab_k();
+    slot.on_device = false;
+    if (args.device_format && query_batch_device(rb, args, b, slot)) return;
     const auto t0 = std::chrono::steady_clock::now();
     make_strands(b, slot.seqs, slot.off, static_cast<size_t>(args.threads));
     const auto t1 = std::chrono::steady_clock::now();
@@ -389,15 +436,30 @@ void query_batch(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args, const Bat
 }
 
 // stage 2 (`pieces` is a pool that keeps its buffers from window to window: `used` counts the ones of this window)
-void format_batch(const RbMarkersArgs &args, const BatchView &b, SeedSlot &slot, RandomBoolGenerator &booler, std::vector<rbg_cli::TextBuf> &pieces,
-                  size_t &used) {
+void format_batch(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args, const BatchView &b, SeedSlot &slot, std::vector<rbg_cli::TextBuf> &pieces, size_t &used) {
     const size_t N = b.size();
+    if (slot.on_device) {   // the text is made: wait for its copy, hand it to the writer's pieces
+        rbwt::detail::check(slot.rc, "rbg_markers_report_text");
+        const auto t2 = std::chrono::steady_clock::now();
+        rbwt::detail::check(rbg_wait_text(rb.handle(), slot.text), "rbg_wait_text");
+        used += 1;
+        if (pieces.size() < used) pieces.resize(used);
+        rbg_cli::TextBuf &piece = pieces[used - 1];
+        piece.clear();
+        piece.reserve(slot.text_len);
+        if (slot.text_len) memcpy(piece.p.get(), slot.text, slot.text_len);
+        piece.len = slot.text_len;
+        rbwt::detail::check(rbg_release_text(rb.handle(), slot.text), "rbg_release_text");
+        slot.text = nullptr;
+        g_trace[0] += slot.t_strands;
+        g_trace[1] += slot.t_query;
+        g_trace[2] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t2).count();
+        return;
+    }
     rbwt::detail::check(slot.rc, args.lmem ? "rbg_get_markers_lmems" : "rbg_get_markers_greedy_seeding");
     const BatchSeeds &r = slot.r;
     const auto t2 = std::chrono::steady_clock::now();
-    std::vector<uint8_t> first_fwd(N, 1);
-    if (args.heuristic)
-        for (size_t i = 0; i < N; ++i) first_fwd[i] = booler.get_bool() ? 1 : 0;  // :483
+    const std::vector<uint8_t> &first_fwd = slot.first_fwd;
     const size_t T = std::max<size_t>(1, std::min<size_t>({static_cast<size_t>(args.threads), (N + 4095) / 4096, size_t(64)}));
     const size_t first_piece = used;
     used += T;
@@ -467,15 +529,19 @@ int main(int argc, char **argv) {
             const size_t nb = (cur.size() + args.batch - 1) / args.batch;
             auto view = [&](size_t j) { return BatchView{&cur, j * args.batch, std::min<size_t>(cur.size() - j * args.batch, args.batch)}; };
             std::future<void> ahead;
-            if (nb) query_batch(rb, args, view(0), slots[0]);
+            if (nb) {
+                draw_coins(args, booler, view(0).size(), slots[0]);
+                query_batch(rb, args, view(0), slots[0]);
+            }
             for (size_t j = 0; j < nb; ++j) {
                 if (ahead.valid()) ahead.get();
                 if (j + 1 < nb) {
                     SeedSlot *ns = &slots[(j + 1) & 1];
                     const BatchView nv = view(j + 1);
+                    draw_coins(args, booler, nv.size(), *ns);
                     ahead = std::async(std::launch::async, [&rb, &args, nv, ns] { query_batch(rb, args, nv, *ns); });
                 }
-                format_batch(args, view(j), slots[j & 1], booler, pieces, used);
+                format_batch(rb, args, view(j), slots[j & 1], pieces, used);
             }
         }
         if (writer.valid()) writer.get();

@@ -605,6 +605,26 @@ int launch_loc_markers_plan(const DevIndex &ix, const LaunchCfg &cfg, const uint
                             uint64_t *mk_off, void *tmp, size_t tmp_bytes, int group, void *stream);
 int launch_loc_markers_fill(const DevIndex &ix, const LaunchCfg &cfg, const uint64_t *locs, const uint64_t *loc_off, const uint64_t *off, uint64_t N,
                             const uint64_t *mk_off, uint64_t *mk, int group, void *stream);
+// rb_markers' report on the device (k_report.hip; rbg_markers_report[_text]): both strands of raw reads, the canonical form of the seeding kernels' records
+// (min_range gate, marker_cmp sort, unique, the two per-seed filters; group: lanes per short segment, 4 / 16 / 64, or 0 = chosen on the device --
+// report_canon_group(): what RBG_REPORT_GROUP forces), the per-read choice of printed records, and the lines by elements as in k_text.hip
+int launch_read_strands(const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t total, uint8_t *out, uint64_t *off2, void *stream);
+int report_canon_group();
+size_t seed_canon_tmp_bytes(uint64_t S);
+int launch_seed_canon(const LaunchCfg &cfg, uint64_t *seeds, uint64_t S, uint64_t *mk, uint64_t min_range, uint32_t flags, uint64_t read_len, void *tmp,
+                      size_t tmp_bytes, int group, void *stream);
+int launch_report_select(const uint64_t *seeds, const uint64_t *seed_off, const uint64_t *off2, uint64_t N, const uint8_t *first_fwd, uint64_t read_len,
+                         uint64_t min_seed_len, uint32_t flags, uint64_t *rep_off, void *out, uint32_t *out_read, void *tmp, size_t tmp_bytes, void *stream);
+int launch_report_melem(const void *recs, uint64_t R, uint64_t *melem, void *tmp, size_t tmp_bytes, void *stream);
+size_t report_text_ws_bytes(uint64_t E);
+int launch_report_map(const uint64_t *melem, uint64_t R, uint64_t E, void *ws, size_t ws_bytes, void *stream);
+int launch_report_gather(const void *recs, const uint64_t *melem, const uint64_t *mk, uint64_t R, uint64_t E, void *ws, size_t ws_bytes, void *recs_out,
+                         uint64_t *dense, void *stream);
+int launch_report_text_plan(const void *recs, const uint32_t *rec_read, const uint64_t *melem, const uint64_t *mk, uint64_t R, uint64_t E, const char *names,
+                            const uint32_t *name_off, void *ws, size_t ws_bytes, void *stream);
+void report_text_total_ptrs(void *ws, uint64_t E, const uint64_t **last_at, const uint32_t **last_len);
+int launch_report_text_fill(const void *recs, const uint32_t *rec_read, const uint64_t *melem, const uint64_t *mk, uint64_t R, uint64_t E, const char *names,
+                            const uint32_t *name_off, void *ws, size_t ws_bytes, uint64_t total, char *text, void *stream);
 int launch_find_range_markers_plan(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off,
                                    uint64_t N, uint64_t wsize, uint64_t max_range, uint64_t *lo, uint64_t *hi,
                                    uint64_t *mk_off, void *tmp, size_t tmp_bytes, void *stream);

@@ -424,6 +424,26 @@ class RowBowt {
         mk.assign(mbuf.p, mbuf.p + mk_off[N]);
     }
 
+    // What rb_markers prints for many RAW reads (rb_markers.cpp:357-519: both strands, the seeding, out_fn's sort + unique, the heuristic
+    // worker's filters and choices), as records: read i prints seeds[seed_off[i] .. seed_off[i + 1]) in that order, a record's markers are
+    // mk[mk_begin .. mk_end), sorted by marker_cmp and unique.  params.ftab_k is set to the loaded ftab's k; first_fwd: the heuristic worker's
+    // coin per read (empty: forward first).  Exits like the reference where it would (ftab k - 1 > wsize, lmem without an ftab).
+    void markers_report_batch(const std::vector<std::string> &queries, rbg_report_params_t params, const std::vector<uint8_t> &first_fwd,
+                              std::vector<uint64_t> &seed_off, std::vector<rbg_report_seed_t> &seeds, std::vector<MarkerT> &mk) const {
+        const uint64_t N = queries.size();
+        params.ftab_k = disable_ft_ ? 0 : ft_k_;
+        seed_off.assign(N + 1, 0);
+        detail::Batch b;
+        for (const auto &q : queries) b.add(q);
+        rbg_report_seed_t *recs = nullptr;
+        detail::LibBuf mbuf;
+        detail::check(rbg_markers_report(ix_.get(), b.data(), b.off.data(), N, first_fwd.size() == N && N ? first_fwd.data() : nullptr, &params,
+                                         seed_off.data(), &recs, &mbuf.p), "rbg_markers_report");
+        std::unique_ptr<rbg_report_seed_t, void (*)(void *)> hold(recs, rbg_free_buffer);
+        seeds.assign(recs, recs + seed_off[N]);
+        mk.assign(mbuf.p, mbuf.p + (seed_off[N] ? recs[seed_off[N] - 1].mk_end : 0));
+    }
+
     // get_seeds_greedy_w_sample (w_sample) or get_seeds_greedy for many reads: out[i] = the list of queries[i]
     void get_seeds_greedy_batch(const std::vector<std::string> &queries, uint64_t min_length, bool w_sample,
                                 std::vector<std::vector<LFData>> &out) const {

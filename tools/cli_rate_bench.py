@@ -118,6 +118,9 @@ def main():
     ap.add_argument("--only-markers", action="store_true",
                     help="only the rb_markers rows, each under the layout the tool gets by default (RBG_LAYOUT_AUTO: the run-indexed replica) and under "
                          "RBG_LAYOUT=prefer-slots (what the tool forced until round 5), three processes each (profiles/r05_rb_markers_layout.txt)")
+    ap.add_argument("--ab-markers", default="",
+                    help="with --only-markers: the root of ANOTHER build of this project (e.g. the parent commit).  Its rb_markers, this tree's rb_markers and this "
+                         "tree's rb_markers --device-format then run alternating, three fresh processes each, in both modes (the A/B rule of DESIGN.md 6e)")
     ap.add_argument("--only-sm", type=int, default=0, help="only the rb_align -s -m row on plain FASTQ, this many times (its spread)")
     ap.add_argument("--numa-probe", type=int, default=0,
                     help="the process-to-process spread of rb_align -s -m and its cause: this many fresh processes with the pinned result buffers left where "
@@ -204,13 +207,17 @@ def main():
     if args.only_s or args.only_sm:
         return
     exe2 = os.path.join(ROOT, "rowbowt_amd", "rb_markers")
-    variants = [("", {})]
+    variants = [("", {}, exe2, [])]
     if args.only_markers:
-        variants = [("[default layout] ", {}), ("[RBG_LAYOUT=prefer-slots] ", {"RBG_LAYOUT": "prefer-slots"})] * 3
-    for label, extra_env in variants:
-      for flags in (th, ["--heuristic", "--best-strand-only", "--min-seed-length", "30"] + th):
+        variants = [("[default layout] ", {}, exe2, []), ("[RBG_LAYOUT=prefer-slots] ", {"RBG_LAYOUT": "prefer-slots"}, exe2, [])] * 3
+    if args.only_markers and args.ab_markers:
+        other = os.path.join(os.path.abspath(args.ab_markers), "rowbowt_amd", "rb_markers")
+        variants = [("[other build] ", {}, other, []), ("[this build, host format] ", {}, exe2, ["--host-format"]),
+                    ("[this build, device format] ", {}, exe2, ["--device-format"])] * 3
+    for label, extra_env, exe_m, more in variants:
+      for flags in (more + th, more + ["--heuristic", "--best-strand-only", "--min-seed-length", "30"] + th):
         t0 = time.perf_counter()
-        p = subprocess.run([exe2] + flags + [prefix, fqm], stdout=open(out_txt, "wb"), stderr=subprocess.PIPE, timeout=600, env=dict(os.environ, RB_ALIGN_TRACE="1", **extra_env))
+        p = subprocess.run([exe_m] + flags + [prefix, fqm], stdout=open(out_txt, "wb"), stderr=subprocess.PIPE, timeout=600, env=dict(os.environ, RB_ALIGN_TRACE="1", **extra_env))
         dt = time.perf_counter() - t0
         sz = os.path.getsize(out_txt)
         err = p.stderr.decode().strip().splitlines()
