@@ -426,6 +426,47 @@ int rbg_markers_report(rbg_index *, const uint8_t *seqs, const uint64_t *off, ui
 int rbg_markers_report_text(rbg_index *, const uint8_t *seqs, const uint64_t *off, uint64_t N, const uint8_t *first_fwd /* nullable */,
                             const rbg_report_params_t *params, const char *name_base, const uint64_t *name_begin, const uint32_t *name_len,
                             const char **text, uint64_t *text_len);
+/* ---- the marker tally: per marker, how many of rb_markers' lines carried it ---------------------------------------------------------
+ * For a caller who wants the genotyping evidence and not the lines.  Take the lines rbg_markers_report_text makes for a batch and an
+ * rbg_report_params_t; for every line and every marker m on it: n_fwd[m] += 1 if the line's strand is '+', else n_rev[m] += 1, and
+ * len_sum[m] += the line's query_len (wrapping).  A line with " ." adds nothing; a marker printed on two lines of one read counts twice (no
+ * per-read deduplication).  A marker is the full 64-bit value: every value is a legal key, 0 and 2^64 - 1 included.  The sums are of integers,
+ * so the result does not depend on read order, on how the reads are split into calls and passes, or on the order in which the device's atomic
+ * additions arrive: it is bit-reproducible.
+ *
+ * The table lives on the index's device (an open-addressing table of 32-byte slots, k_tally.hip) and is fed across passes, calls and batches;
+ * nothing but the scalars a pass reads anyway comes back to the host until rbg_tally_export.  Its allocations are the index's: rbg_info().hbm_bytes
+ * counts them.  FREE THE TALLY BEFORE ITS INDEX.  One tally may be fed by any number of calls one after another, NOT concurrently from two threads
+ * (the host side keeps the reserve bookkeeping without a lock); separate tallies are independent.
+ *
+ * rbg_tally_create: capacity = max(64, the power of two >= 2 * distinct_hint) slots.  rbg_tally_reset: empty, the capacity kept.
+ * rbg_tally_reserve: room for `extra` more elements at a load factor of at most 1/2; the host tracks an upper bound of the entries (every element
+ * handed to a launch counts as a new one) and only when that bound says the room is missing does the call synchronise the device, read the
+ * exact count and, if need be, grow (a larger table, every live slot re-inserted).
+ * rbg_tally_add_dev: the records k_report_select left on the device (rbg_report_select_dev's d_out, R of them) and the marker array they point
+ * into; M_upper >= the sum of their marker counts (mk_end - mk_begin) -- it sizes the launch and MUST NOT be less.  Asynchronous on `stream`
+ * (the handle's element map grows, synchronising, when a call needs a larger one than any before); RBG_EARG, and nothing launched, when M_upper
+ * exceeds the reserved room (capacity / 2 - the bound): reserve first.  d_tmp: rbg_tally_add_tmp_bytes(R), 8-byte aligned.
+ * rbg_markers_tally: rbg_markers_report's arguments and checks; the lines' markers are added to the tally instead of being returned.
+ * rbg_tally_add_entries: the export of another tally (another GPU's or rank's) added in: the merge.  Entries without counts add nothing.
+ * rbg_tally_export: the entries with n_fwd + n_rev > 0, sorted by (sequence, position, allele); through rbg_free_buffer.
+ * rbg_tally_info: {entries, capacity, grows since create / reset, records added, elements added, elements dropped}; dropped stays 0 -- a probe
+ * sequence is bounded by the capacity and the reserve rule keeps the table half empty, the counter is the backstop's.
+ * RBG_TALLY_COMBINE=0 (environment) turns off the combining of equal keys within a wave, for A/Bs: same result. */
+typedef struct rbg_tally rbg_tally;
+typedef struct rbg_tally_entry { uint64_t marker, n_fwd, n_rev, len_sum; } rbg_tally_entry_t;
+int rbg_tally_create(rbg_index *, uint64_t distinct_hint, rbg_tally **out);
+void rbg_tally_free(rbg_tally *);
+int rbg_tally_reset(rbg_tally *);
+int rbg_tally_reserve(rbg_tally *, uint64_t extra);
+size_t rbg_tally_add_tmp_bytes(uint64_t R);
+int rbg_tally_add_dev(rbg_tally *, const rbg_report_seed_t *d_recs, uint64_t R, const uint64_t *d_mk, uint64_t M_upper, void *d_tmp, size_t tmp_bytes,
+                      void *stream);
+int rbg_markers_tally(rbg_index *, const uint8_t *seqs, const uint64_t *off, uint64_t N, const uint8_t *first_fwd /* nullable */,
+                      const rbg_report_params_t *params, rbg_tally *);
+int rbg_tally_add_entries(rbg_tally *, const rbg_tally_entry_t *entries, uint64_t count);
+int rbg_tally_export(rbg_tally *, uint64_t *count, rbg_tally_entry_t **entries);
+int rbg_tally_info(rbg_tally *, uint64_t out[6]);
 /* ---- queries, device-resident buffers (HBM in, HBM out; asynchronous on `stream`) ---------- */
 /* d_seqs: the reads back to back as in the host calls, in device memory, 16-BYTE ALIGNED (RBG_EARG otherwise), and the allocation must reach the next
  * multiple of 16 bytes at or past its last read's end: the kernels fetch reads as aligned 16-byte chunks (the bytes beyond a read's end are never used).

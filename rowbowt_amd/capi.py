@@ -82,6 +82,11 @@ REPORT_SEED = np.dtype([("range_size", "<u8"), ("query_start", "<u8"), ("query_l
                         ("strand", "<u4"), ("pad", "<u4")])
 
 
+# rbg_tally_entry_t as a numpy record
+TALLY_ENTRY = np.dtype([("marker", "<u8"), ("n_fwd", "<u8"), ("n_rev", "<u8"), ("len_sum", "<u8")])
+TALLY_INFO = ("entries", "capacity", "grows", "records", "elements", "dropped")
+
+
 def report_params(wsize=19, max_range=1000, min_range=0, ftab_k=0, read_len=101, min_seed_len=0, lmem=False, heuristic=False, best_strand=False,
                   clear_conflicting=False, clear_identical=False):
     """rb_markers' options as an rbg_report_params_t (the defaults are the tool's, rb_markers.cpp:22-40)"""
@@ -197,6 +202,16 @@ _PROTOS = [
     ("rbg_report_select_dev", C.c_int, [VP, VP, VP, VP, U64, VP, VP, VP, VP, VP, VP, C.c_size_t, VP]),
     ("rbg_markers_report", C.c_int, [VP, VP, VP, U64, VP, VP, VP, C.POINTER(VP), C.POINTER(VP)]),
     ("rbg_markers_report_text", C.c_int, [VP, VP, VP, U64, VP, VP, VP, VP, VP, C.POINTER(VP), C.POINTER(U64)]),
+    ("rbg_tally_create", C.c_int, [VP, U64, C.POINTER(VP)]),
+    ("rbg_tally_free", None, [VP]),
+    ("rbg_tally_reset", C.c_int, [VP]),
+    ("rbg_tally_reserve", C.c_int, [VP, U64]),
+    ("rbg_tally_add_tmp_bytes", C.c_size_t, [U64]),
+    ("rbg_tally_add_dev", C.c_int, [VP, VP, U64, VP, U64, VP, C.c_size_t, VP]),
+    ("rbg_markers_tally", C.c_int, [VP, VP, VP, U64, VP, VP, VP]),
+    ("rbg_tally_add_entries", C.c_int, [VP, VP, U64]),
+    ("rbg_tally_export", C.c_int, [VP, C.POINTER(U64), C.POINTER(VP)]),
+    ("rbg_tally_info", C.c_int, [VP, VP]),
     ("rbg_set_default_option", C.c_int, [C.c_int, C.c_int64]),
     ("rbg_get_default_option", C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
 ]
@@ -327,6 +342,51 @@ def _take(ptr, n):
     mem = (C.c_char * (n * 8)).from_address(ptr.value)
     weakref.finalize(mem, lib().rbg_free_buffer, VP(ptr.value))
     return np.frombuffer(mem, dtype=np.uint64)   # .base is `mem`: every view keeps it alive
+
+
+class Tally:
+    """rbg_tally: per marker, how many of rb_markers' lines carried it (n_fwd, n_rev, len_sum), accumulated on the index's device across calls.
+    Close it before its index; feed it from one thread at a time."""
+
+    def __init__(self, rb, distinct_hint=0):
+        self.L = lib()
+        self.rb = rb   # (keeps the index alive)
+        self.h = VP()
+        _check(self.L.rbg_tally_create(rb.h, distinct_hint, C.byref(self.h)), "rbg_tally_create")
+
+    def close(self):
+        if self.h:
+            self.L.rbg_tally_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if self.rb.h:
+                self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        _check(self.L.rbg_tally_reset(self.h), "rbg_tally_reset")
+
+    def reserve(self, extra):
+        _check(self.L.rbg_tally_reserve(self.h, extra), "rbg_tally_reserve")
+
+    def add_entries(self, entries):
+        """merge: the export of another tally (TALLY_ENTRY records) added into this one"""
+        e = np.ascontiguousarray(entries, dtype=TALLY_ENTRY)
+        _check(self.L.rbg_tally_add_entries(self.h, _p(e), len(e)), "rbg_tally_add_entries")
+
+    def export(self):
+        """-> TALLY_ENTRY records with n_fwd + n_rev > 0, sorted by (sequence, position, allele)"""
+        n, ptr = U64(), VP()
+        _check(self.L.rbg_tally_export(self.h, C.byref(n), C.byref(ptr)), "rbg_tally_export")
+        return _take(ptr, 4 * n.value).view(TALLY_ENTRY)
+
+    def info(self):
+        out = np.zeros(6, np.uint64)
+        _check(self.L.rbg_tally_info(self.h, _p(out)), "rbg_tally_info")
+        return dict(zip(TALLY_INFO, (int(v) for v in out)))
 
 
 class RowBowt:
@@ -641,6 +701,13 @@ class RowBowt:
             return C.string_at(text, n.value) if n.value else b""
         finally:
             self.L.rbg_release_text(self.h, text)
+
+    def markers_tally(self, seqs, off, params, first_fwd, tally):
+        """rbg_markers_tally: markers_report's inputs; the markers of the lines rb_markers would print are added to `tally` (a Tally of this
+        index) on the device, nothing is returned"""
+        N = len(off) - 1
+        coin = None if first_fwd is None else np.ascontiguousarray(first_fwd, dtype=np.uint8)
+        _check(self.L.rbg_markers_tally(self.h, _p(seqs), _p(off), N, _p(coin), C.byref(params), tally.h), "rbg_markers_tally")
 
     def counters(self):
         out = np.zeros(4, np.uint64)

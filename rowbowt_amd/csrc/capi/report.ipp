@@ -28,8 +28,8 @@ struct ReportTrace {
     ~ReportTrace() {
         if (on && passes)
             std::fprintf(stderr, "rbg_markers_report: %llu passes, %llu reads, %llu bytes copied out: copy in + strands %.4f s, plan %.4f, fill %.4f, canon %.4f, "
-                                 "select %.4f, text %.4f, copy out %.4f\n", static_cast<unsigned long long>(passes), static_cast<unsigned long long>(reads),
-                         static_cast<unsigned long long>(d2h), t[0], t[1], t[2], t[3], t[4], t[5], t[6]);
+                                 "select %.4f, text %.4f, copy out %.4f, tally %.4f\n", static_cast<unsigned long long>(passes), static_cast<unsigned long long>(reads),
+                         static_cast<unsigned long long>(d2h), t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7]);
     }
 };
 ReportTrace g_report_trace;
@@ -46,6 +46,8 @@ struct ReportOut {   // where a call's result goes
     const uint32_t *name_len = nullptr;
     char *text = nullptr;
     size_t text_cap = 0, text_len = 0;
+    // tally: the printed records' markers are added on the device, nothing is copied out
+    rbg_tally *tally = nullptr;
 };
 
 // room for `need` bytes in the call's pinned text buffer (what is there is kept; no copy is in flight when this is called)
@@ -68,7 +70,7 @@ int report_text_room(rbg_index *ix, ReportOut &o, size_t need, size_t hint) {
     return RBG_OK;
 }
 
-// reads [a, b) of the batch: strands -> seeds -> canon -> select -> records or text
+// reads [a, b) of the batch: strands -> seeds -> canon -> select -> records, text or tally
 int report_pass(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, uint64_t a, uint64_t b, uint64_t N, const uint8_t *first_fwd,
                 const rbg_report_params_t &P, ReportOut &o, hipStream_t st) {
     const uint64_t n = b - a, bytes = off[b] - off[a];
@@ -120,6 +122,7 @@ int report_pass(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, uint64_
         HIP_TRY(hipStreamSynchronize(st));
         lap(1);
         if (S >> 32) return RBG_EARG;   // (a pass holds at most 64 MiB of reads)
+        if (o.tally && (rc = tally_reserve(o.tally, total_mk))) return rc;   // (total_mk bounds the pass's elements from above: canon and select only drop)
         if ((rc = dseeds.alloc(S * sizeof(rbg_marker_seed_t))) || (rc = dmk.alloc(total_mk * 8))) return rc;
         if (S && launch_marker_seeds_fill(ix->dev, ix->cfg, dseq2.as<uint8_t>(), doff2.as<uint64_t>(), n2, P.wsize, P.max_range, P.ftab_k, dsoff.as<uint64_t>(),
                                           dmoff.as<uint64_t>(), dseeds.as<uint64_t>(), dmk.as<uint64_t>(), st, log_bytes ? dlog.p : nullptr, log_bytes))
@@ -136,6 +139,7 @@ int report_pass(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, uint64_
         HIP_TRY(hipMemcpyAsync(&total_mk, dmoff.as<uint64_t>() + n2, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         lap(1);
+        if (o.tally && (rc = tally_reserve(o.tally, total_mk))) return rc;
         if ((rc = dseeds.alloc(S * sizeof(rbg_marker_seed_t))) || (rc = dmk.alloc(total_mk * 8))) return rc;
         if (S && launch_marker_lmems_fill(ix->dev, ix->cfg, dseq2.as<uint8_t>(), doff2.as<uint64_t>(), n2, S, P.wsize, P.max_range, P.ftab_k, dtmp.p,
                                           dseeds.as<uint64_t>(), dmk.as<uint64_t>(), st))
@@ -162,14 +166,14 @@ int report_pass(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, uint64_
         return RBG_ENODEV;
     uint64_t R = 0, M = 0;
     std::vector<uint64_t> rep_off;
-    if (o.want_text) {
+    if (o.want_text || o.tally) {
         HIP_TRY(hipMemcpyAsync(&R, drep.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
     } else {
         rep_off.resize(n + 1);
         HIP_TRY(hipMemcpyAsync(rep_off.data(), drep.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
-    if (!o.want_text) {
+    if (!o.want_text && !o.tally) {
         R = rep_off[n];
         const uint64_t base = o.recs.size();
         for (uint64_t i = 0; i < n; ++i) o.seed_off[a + i + 1] = base + rep_off[i + 1];
@@ -177,84 +181,89 @@ int report_pass(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, uint64_
     lap(4);
     if (R) {
         if (launch_report_melem(drecs.p, R, dmelem.as<uint64_t>(), dstmp.p, stmp_bytes, st)) return RBG_ENODEV;
-        HIP_TRY(hipMemcpyAsync(&M, dmelem.as<uint64_t>() + R, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        const uint64_t E = R + M;
-        DevBuf dws;
-        const size_t ws_bytes = report_text_ws_bytes(E);
-        if ((rc = dws.alloc(ws_bytes))) return rc;
-        if (launch_report_map(dmelem.as<uint64_t>(), R, E, dws.p, ws_bytes, st)) return RBG_ENODEV;
-        if (!o.want_text) {
-            DevBuf drecs2, ddense;
-            if ((rc = drecs2.alloc(R * sizeof(rbg_report_seed_t))) || (rc = ddense.alloc(M * 8))) return rc;
-            if (launch_report_gather(drecs.p, dmelem.as<uint64_t>(), dmk.as<uint64_t>(), R, E, dws.p, ws_bytes, drecs2.p, ddense.as<uint64_t>(), st)) return RBG_ENODEV;
-            lap(5);
-            const uint64_t rbase = o.recs.size(), mbase = o.mk.size();
-            o.recs.resize(rbase + R);
-            o.mk.resize(mbase + M);
-            if ((rc = d2h_result(o.recs.data() + rbase, drecs2.p, R * sizeof(rbg_report_seed_t), st))) return rc;
-            if (M && (rc = d2h_result(o.mk.data() + mbase, ddense.p, M * 8, st))) return rc;
-            HIP_TRY(hipStreamSynchronize(st));
-            if (mbase)
-                for (uint64_t r = rbase; r < rbase + R; ++r) { o.recs[r].mk_begin += mbase; o.recs[r].mk_end += mbase; }
-            d2h_bytes = R * sizeof(rbg_report_seed_t) + M * 8 + (n + 1) * 8;
+        if (o.tally) {   // (room was reserved above; the add is the pass's last launch and nothing comes back)
+            if ((rc = tally_add_mapped(o.tally, drecs.p, R, dmk.as<uint64_t>(), dmelem.as<uint64_t>(), total_mk, st))) return rc;
+            lap(7);
         } else {
-            // the names of the pass, back to back
-            std::vector<uint32_t> noff(n + 1);
-            uint64_t name_bytes = 0;
-            for (uint64_t i = 0; i < n; ++i) { noff[i] = static_cast<uint32_t>(name_bytes); name_bytes += o.name_len[a + i]; }
-            if (name_bytes >> 32) return RBG_EARG;
-            noff[n] = static_cast<uint32_t>(name_bytes);
-            std::vector<char> blob(name_bytes + 1);
-            parallel_for(n, [&](uint64_t x, uint64_t y, unsigned) {
-                for (uint64_t i = x; i < y; ++i) std::memcpy(blob.data() + noff[i], o.name_base + o.name_begin[a + i], o.name_len[a + i]);
-            });
-            DevBuf dnoff, dnames, dtext;
-            if ((rc = dnoff.alloc((n + 1) * 4)) || (rc = dnames.alloc(name_bytes + 1))) return rc;
-            HIP_TRY(hipMemcpyAsync(dnoff.p, noff.data(), (n + 1) * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(dnames.p, blob.data(), name_bytes + 1, hipMemcpyHostToDevice, st));
-            if (launch_report_text_plan(drecs.p, dread.as<uint32_t>(), dmelem.as<uint64_t>(), dmk.as<uint64_t>(), R, E, dnames.as<char>(), dnoff.as<uint32_t>(), dws.p,
-                                        ws_bytes, st))
-                return RBG_ENODEV;
-            const uint64_t *p_at = nullptr;
-            const uint32_t *p_len = nullptr;
-            report_text_total_ptrs(dws.p, E, &p_at, &p_len);
-            uint64_t last_at = 0;
-            uint32_t last_len = 0;
-            HIP_TRY(hipMemcpyAsync(&last_at, p_at, 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(&last_len, p_len, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));   // (the name blob has been copied too)
-            const uint64_t total = last_at + last_len;
-            if ((rc = dtext.alloc(total))) return rc;
-            if (launch_report_text_fill(drecs.p, dread.as<uint32_t>(), dmelem.as<uint64_t>(), dmk.as<uint64_t>(), R, E, dnames.as<char>(), dnoff.as<uint32_t>(), dws.p,
-                                        ws_bytes, total, dtext.as<char>(), st))
-                return RBG_ENODEV;
-            lap(5);
-            // (a first pass that is not the last sizes the buffer for the whole batch from its own text per read byte)
-            const size_t hint = last || !bytes ? 0 : static_cast<size_t>(static_cast<double>(total) / static_cast<double>(bytes) * static_cast<double>(off[N] - off[0]) * 1.25);
-            if ((rc = report_text_room(ix, o, o.text_len + total, hint))) return rc;
-            char *dst = o.text + o.text_len;
-            o.text_len += total;
-            d2h_bytes = total;
-            if (!last || g_report_trace.on) {
-                HIP_TRY(hipMemcpyAsync(dst, dtext.p, total, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(&M, dmelem.as<uint64_t>() + R, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            const uint64_t E = R + M;
+            DevBuf dws;
+            const size_t ws_bytes = report_text_ws_bytes(E);
+            if ((rc = dws.alloc(ws_bytes))) return rc;
+            if (launch_report_map(dmelem.as<uint64_t>(), R, E, dws.p, ws_bytes, st)) return RBG_ENODEV;
+            if (!o.want_text) {
+                DevBuf drecs2, ddense;
+                if ((rc = drecs2.alloc(R * sizeof(rbg_report_seed_t))) || (rc = ddense.alloc(M * 8))) return rc;
+                if (launch_report_gather(drecs.p, dmelem.as<uint64_t>(), dmk.as<uint64_t>(), R, E, dws.p, ws_bytes, drecs2.p, ddense.as<uint64_t>(), st)) return RBG_ENODEV;
+                lap(5);
+                const uint64_t rbase = o.recs.size(), mbase = o.mk.size();
+                o.recs.resize(rbase + R);
+                o.mk.resize(mbase + M);
+                if ((rc = d2h_result(o.recs.data() + rbase, drecs2.p, R * sizeof(rbg_report_seed_t), st))) return rc;
+                if (M && (rc = d2h_result(o.mk.data() + mbase, ddense.p, M * 8, st))) return rc;
                 HIP_TRY(hipStreamSynchronize(st));
+                if (mbase)
+                    for (uint64_t r = rbase; r < rbase + R; ++r) { o.recs[r].mk_begin += mbase; o.recs[r].mk_end += mbase; }
+                d2h_bytes = R * sizeof(rbg_report_seed_t) + M * 8 + (n + 1) * 8;
             } else {
-                // the last copy-out runs on the handle's copy stream behind the fill kernel; the caller returns at once and the text's reader
-                // waits (rbg_wait_text), as in rbg_align_text
-                std::lock_guard<std::mutex> g(ix->text_mu);
-                rbg_index::TextOut *t = find_text_out(ix, o.text);
-                hipError_t e = hipEventRecord(t->done, st);
-                if (e == hipSuccess) e = hipStreamWaitEvent(ix->text_copy_stream, t->done, 0);
-                if (e == hipSuccess) e = hipMemcpyAsync(dst, dtext.p, total, hipMemcpyDeviceToHost, ix->text_copy_stream);
-                if (e == hipSuccess) e = hipEventRecord(t->done, ix->text_copy_stream);
-                HIP_TRY(e);
-                t->pending = true;
-                t->d_text = dtext.p; t->d_cls = dtext.cls; t->d_dev = dtext.dev;
-                dtext.p = nullptr;   // (the record owns the device block until the copy has been waited for)
+                // the names of the pass, back to back
+                std::vector<uint32_t> noff(n + 1);
+                uint64_t name_bytes = 0;
+                for (uint64_t i = 0; i < n; ++i) { noff[i] = static_cast<uint32_t>(name_bytes); name_bytes += o.name_len[a + i]; }
+                if (name_bytes >> 32) return RBG_EARG;
+                noff[n] = static_cast<uint32_t>(name_bytes);
+                std::vector<char> blob(name_bytes + 1);
+                parallel_for(n, [&](uint64_t x, uint64_t y, unsigned) {
+                    for (uint64_t i = x; i < y; ++i) std::memcpy(blob.data() + noff[i], o.name_base + o.name_begin[a + i], o.name_len[a + i]);
+                });
+                DevBuf dnoff, dnames, dtext;
+                if ((rc = dnoff.alloc((n + 1) * 4)) || (rc = dnames.alloc(name_bytes + 1))) return rc;
+                HIP_TRY(hipMemcpyAsync(dnoff.p, noff.data(), (n + 1) * 4, hipMemcpyHostToDevice, st));
+                HIP_TRY(hipMemcpyAsync(dnames.p, blob.data(), name_bytes + 1, hipMemcpyHostToDevice, st));
+                if (launch_report_text_plan(drecs.p, dread.as<uint32_t>(), dmelem.as<uint64_t>(), dmk.as<uint64_t>(), R, E, dnames.as<char>(), dnoff.as<uint32_t>(), dws.p,
+                                            ws_bytes, st))
+                    return RBG_ENODEV;
+                const uint64_t *p_at = nullptr;
+                const uint32_t *p_len = nullptr;
+                report_text_total_ptrs(dws.p, E, &p_at, &p_len);
+                uint64_t last_at = 0;
+                uint32_t last_len = 0;
+                HIP_TRY(hipMemcpyAsync(&last_at, p_at, 8, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(&last_len, p_len, 4, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));   // (the name blob has been copied too)
+                const uint64_t total = last_at + last_len;
+                if ((rc = dtext.alloc(total))) return rc;
+                if (launch_report_text_fill(drecs.p, dread.as<uint32_t>(), dmelem.as<uint64_t>(), dmk.as<uint64_t>(), R, E, dnames.as<char>(), dnoff.as<uint32_t>(), dws.p,
+                                            ws_bytes, total, dtext.as<char>(), st))
+                    return RBG_ENODEV;
+                lap(5);
+                // (a first pass that is not the last sizes the buffer for the whole batch from its own text per read byte)
+                const size_t hint = last || !bytes ? 0 : static_cast<size_t>(static_cast<double>(total) / static_cast<double>(bytes) * static_cast<double>(off[N] - off[0]) * 1.25);
+                if ((rc = report_text_room(ix, o, o.text_len + total, hint))) return rc;
+                char *dst = o.text + o.text_len;
+                o.text_len += total;
+                d2h_bytes = total;
+                if (!last || g_report_trace.on) {
+                    HIP_TRY(hipMemcpyAsync(dst, dtext.p, total, hipMemcpyDeviceToHost, st));
+                    HIP_TRY(hipStreamSynchronize(st));
+                } else {
+                    // the last copy-out runs on the handle's copy stream behind the fill kernel; the caller returns at once and the text's reader
+                    // waits (rbg_wait_text), as in rbg_align_text
+                    std::lock_guard<std::mutex> g(ix->text_mu);
+                    rbg_index::TextOut *t = find_text_out(ix, o.text);
+                    hipError_t e = hipEventRecord(t->done, st);
+                    if (e == hipSuccess) e = hipStreamWaitEvent(ix->text_copy_stream, t->done, 0);
+                    if (e == hipSuccess) e = hipMemcpyAsync(dst, dtext.p, total, hipMemcpyDeviceToHost, ix->text_copy_stream);
+                    if (e == hipSuccess) e = hipEventRecord(t->done, ix->text_copy_stream);
+                    HIP_TRY(e);
+                    t->pending = true;
+                    t->d_text = dtext.p; t->d_cls = dtext.cls; t->d_dev = dtext.dev;
+                    dtext.p = nullptr;   // (the record owns the device block until the copy has been waited for)
+                }
             }
+            lap(6);
         }
-        lap(6);
     }
     if (g_report_trace.on) {
         std::lock_guard<std::mutex> g(g_report_trace.mu);
@@ -349,6 +358,16 @@ int rbg_markers_report(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, 
     *seeds = h_recs;
     *mk = h_mk;
     return RBG_OK;
+    });
+}
+
+int rbg_markers_tally(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, uint64_t N, const uint8_t *first_fwd, const rbg_report_params_t *params,
+                      rbg_tally *tally) {
+    return guarded([&]() -> int {
+    if (!tally || !ix || tally->ix->device != ix->device) return RBG_EARG;
+    ReportOut o;
+    o.tally = tally;
+    return report_run(ix, seqs, off, N, first_fwd, params, o);
     });
 }
 

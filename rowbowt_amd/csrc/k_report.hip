@@ -590,6 +590,7 @@ int launch_report_map(const uint64_t *melem, uint64_t R, uint64_t E, void *ws, s
     e = hipcub::DeviceScan::InclusiveScan(w.tmp, tb, w.erec, w.erec, MaxOp(), static_cast<int64_t>(E), st);
     return static_cast<int>(e != hipSuccess ? e : hipGetLastError());
 }
+const uint32_t *report_map_erec(const void *ws) { return static_cast<const uint32_t *>(ws); }   // (rep_ws: the map comes first)
 int launch_report_gather(const void *recs, const uint64_t *melem, const uint64_t *mk, uint64_t R, uint64_t E, void *ws, size_t ws_bytes, void *recs_out,
                          uint64_t *dense, void *stream) {
     const RepWs w = rep_ws(ws, ws_bytes, E);

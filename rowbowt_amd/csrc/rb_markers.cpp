@@ -19,6 +19,9 @@
 // each strand, m per strand.  Parity is stdout only: the reference's per-step debug text on stderr is not reproduced.
 // --lmem without --ftab exits 1 with the reference's "ftab must be enabled!" (:346-349).
 //
+// --tally <file> (not in the reference): no lines; the markers of the lines that would be printed are counted on the device
+// (rbg_markers_tally) and written at the end, one "<seq>\t<pos>\t<allele>\t<n_fwd>\t<n_rev>\t<len_sum>" per marker.
+//
 // Not carried over (each exits 1 with a message, like the reference does for --overlap):
 //   --fbb/-x    other string type, other index file
 #include <getopt.h>
@@ -66,6 +69,7 @@ struct RbMarkersArgs {  // rb_markers.cpp:22-40
     int clear_conflicting = 0, clear_identical = 0, best_strand = 0, heuristic = 0;
     int device = 0;
     int device_format = 0, host_format = 0;   // --device-format: the lines are made on the device (rbg_markers_report_text); --host-format (the default): on host threads
+    std::string tally_file;   // --tally <file>: no lines; per marker the number of lines that carried it, counted on the device (rbg_markers_tally)
     uint64_t batch = 1u << 18;   // (2^17 kept more batches per window in flight but paid the library call's fixed costs twice as often: 0.32 against 0.25 s per 2 M reads)
 };
 
@@ -83,6 +87,9 @@ void print_help() {  // rb_markers.cpp:44-54
     fprintf(stderr, "    --gpu <n>                        HIP device ordinal (default 0)\n");
     fprintf(stderr, "    --batch <n>                      reads per GPU batch (default 262144)\n");
     fprintf(stderr, "    --device-format | --host-format  sort, filter and print the seeds on the device | on host threads (default; same stdout)\n");
+    fprintf(stderr, "    --tally <file>                   print nothing; count on the device, per marker, the lines that would carry it, and write\n");
+    fprintf(stderr, "                                     <seq>\\t<pos>\\t<allele>\\t<n_fwd>\\t<n_rev>\\t<len_sum> per marker to <file>, sorted by\n");
+    fprintf(stderr, "                                     (seq, pos, allele); works with every mode above, --device-format / --host-format are ignored\n");
     fprintf(stderr, "    <input_prefix>                   index prefix\n");
     fprintf(stderr, "    <input_fastq>                    input fastq\n");
 }
@@ -108,6 +115,7 @@ RbMarkersArgs parse_args(int argc, char **argv) {  // rb_markers.cpp:56-134
                                            {"host-format", no_argument, &args.host_format, 1},
                                            {"gpu", required_argument, 0, 'G'},
                                            {"batch", required_argument, 0, 'B'},
+                                           {"tally", required_argument, 0, 'T'},
                                            {0, 0, 0, 0}};
     int c, long_index = 0;
     // "o:" is accepted by the reference's optstring but has no case: it ends in the default branch
@@ -126,6 +134,7 @@ RbMarkersArgs parse_args(int argc, char **argv) {  // rb_markers.cpp:56-134
             case 'x': args.fbb = 1; break;
             case 'G': args.device = atoi(optarg); break;
             case 'B': args.batch = strtoull(optarg, nullptr, 10); break;
+            case 'T': args.tally_file = optarg; break;
             default: print_help(); exit(1);
         }
     }
@@ -151,6 +160,10 @@ RbMarkersArgs parse_args(int argc, char **argv) {  // rb_markers.cpp:56-134
     if (args.lmem) args.batch = std::min<uint64_t>(args.batch, 16384);   // 2 x 16384 strands of 150 bp: 236 MB of records per batch
     if (args.threads == 0) args.threads = 1;
     if (args.host_format) args.device_format = 0;
+    if (!args.tally_file.empty() && (args.device_format || args.host_format)) {
+        fprintf(stderr, "rb_markers: --tally prints no lines: --device-format / --host-format ignored\n");
+        args.device_format = args.host_format = 0;
+    }
     return args;
 }
 
@@ -388,20 +401,42 @@ void draw_coins(const RbMarkersArgs &args, RandomBoolGenerator &booler, size_t N
 
 // stage 1 with --device-format: the raw reads go to the library, which makes both strands, seeds, sorts, filters and prints on the device
 // (false: the library could not allocate -- the batch goes the host way)
-bool query_batch_device(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args, const BatchView &b, SeedSlot &slot) {
+// the raw reads of a batch back to back, and the tool's options as the library takes them
+void pack_raw_reads(const BatchView &b, SeedSlot &slot) {
     const size_t N = b.size();
-    const auto t0 = std::chrono::steady_clock::now();
     slot.off.resize(N + 1);
     slot.off[0] = 0;
     for (size_t i = 0; i < N; ++i) slot.off[i + 1] = slot.off[i] + b.seq_len(i);
     slot.seqs.resize(slot.off[N]);
     for (size_t i = 0; i < N; ++i) memcpy(&slot.seqs[slot.off[i]], b.seq(i), b.seq_len(i));
-    const auto t1 = std::chrono::steady_clock::now();
+}
+rbg_report_params_t report_params(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args) {
     rbg_report_params_t p{};
     p.wsize = args.wsize; p.max_range = args.max_range; p.min_range = args.min_range; p.ftab_k = rb.ftab_k();
     p.read_len = args.read_len; p.min_seed_len = args.min_seed_len;
     p.flags = (args.lmem ? RBG_REPORT_LMEM : 0u) | (args.heuristic ? RBG_REPORT_HEURISTIC : 0u) | (args.best_strand ? RBG_REPORT_BEST_STRAND : 0u) |
               (args.clear_conflicting ? RBG_REPORT_CLEAR_CONFLICTING : 0u) | (args.clear_identical ? RBG_REPORT_CLEAR_IDENTICAL : 0u);
+    return p;
+}
+
+// --tally: the raw reads go to the library, which counts the markers of the lines it would print; nothing comes back
+void tally_batch(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args, const BatchView &b, SeedSlot &slot, rbwt::MarkerTally &tally) {
+    const auto t0 = std::chrono::steady_clock::now();
+    pack_raw_reads(b, slot);
+    const auto t1 = std::chrono::steady_clock::now();
+    const rbg_report_params_t p = report_params(rb, args);
+    rbwt::detail::check(rbg_markers_tally(rb.handle(), reinterpret_cast<const uint8_t *>(slot.seqs.data()), slot.off.data(), b.size(), slot.first_fwd.data(), &p,
+                                          tally.handle()), "rbg_markers_tally");
+    g_trace[0] += std::chrono::duration<double>(t1 - t0).count();
+    g_trace[1] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+}
+
+bool query_batch_device(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args, const BatchView &b, SeedSlot &slot) {
+    const size_t N = b.size();
+    const auto t0 = std::chrono::steady_clock::now();
+    pack_raw_reads(b, slot);
+    const auto t1 = std::chrono::steady_clock::now();
+    const rbg_report_params_t p = report_params(rb, args);
     slot.text = nullptr;
     slot.text_len = 0;
     slot.rc = rbg_markers_report_text(rb.handle(), reinterpret_cast<const uint8_t *>(slot.seqs.data()), slot.off.data(), N, slot.first_fwd.data(), &p, b.w->base,
@@ -505,6 +540,9 @@ int main(int argc, char **argv) {
         exit(1);
     }
     RandomBoolGenerator booler;
+    rbwt::MarkerTally tally;
+    const bool tallying = !args.tally_file.empty();
+    if (tallying) tally = rb.make_tally();
     // three overlapped stages: scan window i+1 | query + format window i (in batches of --batch reads) | write window i-1
     int err = 0;
     Window cur, nxt;
@@ -529,11 +567,16 @@ int main(int argc, char **argv) {
             const size_t nb = (cur.size() + args.batch - 1) / args.batch;
             auto view = [&](size_t j) { return BatchView{&cur, j * args.batch, std::min<size_t>(cur.size() - j * args.batch, args.batch)}; };
             std::future<void> ahead;
-            if (nb) {
+            if (tallying) {   // one call per batch, the coins drawn in file order as below; no text, nothing to overlap with
+                for (size_t j = 0; j < nb; ++j) {
+                    draw_coins(args, booler, view(j).size(), slots[0]);
+                    tally_batch(rb, args, view(j), slots[0], tally);
+                }
+            } else if (nb) {
                 draw_coins(args, booler, view(0).size(), slots[0]);
                 query_batch(rb, args, view(0), slots[0]);
             }
-            for (size_t j = 0; j < nb; ++j) {
+            for (size_t j = 0; j < nb && !tallying; ++j) {
                 if (ahead.valid()) ahead.get();
                 if (j + 1 < nb) {
                     SeedSlot *ns = &slots[(j + 1) & 1];
@@ -560,6 +603,22 @@ int main(int argc, char **argv) {
         case -2: fprintf(stderr, "ERROR: truncated quality string\n"); exit(1);
         case -3: fprintf(stderr, "ERROR: error reading stream\n"); exit(1);
         default: break;
+    }
+    if (tallying) {   // one line per marker, in export order
+        FILE *f = fopen(args.tally_file.c_str(), "wb");
+        if (!f) {
+            fprintf(stderr, "rb_markers: cannot write %s\n", args.tally_file.c_str());
+            exit(1);
+        }
+        for (const rbg_tally_entry_t &e : tally.entries())
+            fprintf(f, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", static_cast<unsigned long long>(get_seq(e.marker)), static_cast<unsigned long long>(get_pos(e.marker)),
+                    static_cast<unsigned long long>(get_allele(e.marker)), static_cast<unsigned long long>(e.n_fwd), static_cast<unsigned long long>(e.n_rev),
+                    static_cast<unsigned long long>(e.len_sum));
+        if (fclose(f) != 0) {
+            fprintf(stderr, "rb_markers: error writing %s\n", args.tally_file.c_str());
+            exit(1);
+        }
+        tally = rbwt::MarkerTally();   // (before the index goes)
     }
     stop = std::chrono::high_resolution_clock::now();
     diff = stop - start;

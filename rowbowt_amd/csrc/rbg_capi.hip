@@ -40,6 +40,7 @@
 #include "capi/hostpath.ipp"      // host-pointer entry points, micro-batching
 #include "capi/text.ipp"          // rbg_align_text
 #include "capi/seeds.ipp"         // markers, marker seeds, greedy seeding
+#include "capi/tally.ipp"         // the marker tally: per-marker counts of the report's lines, accumulated on the device (rbg_markers_tally: report.ipp)
 #include "capi/report.ipp"        // rb_markers' report on the device: strands, canonical records, selection, text
 #include "capi/loc_markers.ipp"   // the text-position marker table, markers at located positions (rb_locs' path)
 #include "capi/replicas.ipp"      // replicas in one process, counters, RCCL

@@ -625,6 +625,19 @@ int launch_report_text_plan(const void *recs, const uint32_t *rec_read, const ui
 void report_text_total_ptrs(void *ws, uint64_t E, const uint64_t **last_at, const uint32_t **last_len);
 int launch_report_text_fill(const void *recs, const uint32_t *rec_read, const uint64_t *melem, const uint64_t *mk, uint64_t R, uint64_t E, const char *names,
                             const uint32_t *name_off, void *ws, size_t ws_bytes, uint64_t total, char *text, void *stream);
+const uint32_t *report_map_erec(const void *ws);   // launch_report_map's result: the record of every element
+// the marker tally (k_tally.hip; rbg_tally_*): an open-addressing table of cap (a power of two) 32-byte slots {key, n_fwd, n_rev, len_sum} with empty key
+// 2^64 - 1, and a header of eight u64 {-, the three sums of marker 2^64 - 1, dropped, claimed slots, records added, elements added}.  Every probe
+// sequence is bounded by cap.  launch_tally_add: one lane per element of launch_report_map's E elements (E >= R + melem[R]).
+bool tally_combine_default();   // RBG_TALLY_COMBINE=0: no combining of equal keys within a wave
+int launch_tally_clear(uint64_t *slots, uint64_t cap, void *stream);
+int launch_tally_add(uint64_t *slots, uint64_t cap, uint64_t *hdr, const void *recs, const uint64_t *melem, const uint64_t *mk, const uint32_t *erec, uint64_t R,
+                     uint64_t E, bool combine, void *stream);
+int launch_tally_add_entries(uint64_t *slots, uint64_t cap, uint64_t *hdr, const void *entries, uint64_t count, void *stream);
+int launch_tally_rehash(const uint64_t *old_slots, uint64_t old_cap, uint64_t *new_slots, uint64_t new_cap, uint64_t *hdr, void *stream);
+size_t tally_compact_tmp_bytes(uint64_t cap);
+int launch_tally_compact_plan(const uint64_t *slots, uint64_t cap, uint64_t *pos, void *tmp, size_t tmp_bytes, void *stream);
+int launch_tally_compact_fill(uint64_t *slots, uint64_t cap, uint64_t *hdr, const uint64_t *pos, void *out, void *stream);
 int launch_find_range_markers_plan(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off,
                                    uint64_t N, uint64_t wsize, uint64_t max_range, uint64_t *lo, uint64_t *hi,
                                    uint64_t *mk_off, void *tmp, size_t tmp_bytes, void *stream);

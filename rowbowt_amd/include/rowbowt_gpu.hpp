@@ -73,6 +73,42 @@ struct LibBuf {  // library-malloc'ed ragged output
 };
 }  // namespace detail
 
+// The marker tally of an index (include/rbg.h, rbg_tally_*): per marker, how many of rb_markers' lines carried it, accumulated on the device by
+// RowBowt::markers_tally.  Destroy it before the RowBowt it was made from; feed it from one thread at a time.
+class MarkerTally {
+   public:
+    MarkerTally() {}
+    MarkerTally(rbg_index *ix, uint64_t distinct_hint) {
+        rbg_tally *t = nullptr;
+        detail::check(rbg_tally_create(ix, distinct_hint, &t), "rbg_tally_create");
+        t_.reset(t);
+    }
+    rbg_tally *handle() const { return t_.get(); }
+    void reset() { detail::check(rbg_tally_reset(t_.get()), "rbg_tally_reset"); }
+    void reserve(uint64_t extra) { detail::check(rbg_tally_reserve(t_.get(), extra), "rbg_tally_reserve"); }
+    void add_entries(const std::vector<rbg_tally_entry_t> &entries) {
+        detail::check(rbg_tally_add_entries(t_.get(), entries.data(), entries.size()), "rbg_tally_add_entries");
+    }
+    // the entries with n_fwd + n_rev > 0, sorted by (sequence, position, allele)
+    std::vector<rbg_tally_entry_t> entries() const {
+        uint64_t n = 0;
+        rbg_tally_entry_t *p = nullptr;
+        detail::check(rbg_tally_export(t_.get(), &n, &p), "rbg_tally_export");
+        std::unique_ptr<rbg_tally_entry_t, void (*)(void *)> hold(p, rbg_free_buffer);
+        return std::vector<rbg_tally_entry_t>(p, p + n);
+    }
+    struct Info { uint64_t entries, capacity, grows, records, elements, dropped; };
+    Info info() const {
+        uint64_t v[6];
+        detail::check(rbg_tally_info(t_.get(), v), "rbg_tally_info");
+        return Info{v[0], v[1], v[2], v[3], v[4], v[5]};
+    }
+
+   private:
+    struct Free { void operator()(rbg_tally *t) const { rbg_tally_free(t); } };
+    std::unique_ptr<rbg_tally, Free> t_;
+};
+
 template <typename RLEString = rle_string_t>
 class RowBowt {
    public:
@@ -442,6 +478,18 @@ class RowBowt {
         std::unique_ptr<rbg_report_seed_t, void (*)(void *)> hold(recs, rbg_free_buffer);
         seeds.assign(recs, recs + seed_off[N]);
         mk.assign(mbuf.p, mbuf.p + (seed_off[N] ? recs[seed_off[N] - 1].mk_end : 0));
+    }
+
+    // The same reads and parameters as markers_report_batch, but the printed lines' markers are counted on the device into `tally` (made by
+    // make_tally of this index) instead of coming back: n_fwd / n_rev per strand of the line, len_sum of the lines' query_len.
+    MarkerTally make_tally(uint64_t distinct_hint = 0) const { return MarkerTally(ix_.get(), distinct_hint); }
+    void markers_tally(const std::vector<std::string> &queries, rbg_report_params_t params, const std::vector<uint8_t> &first_fwd, MarkerTally &tally) const {
+        const uint64_t N = queries.size();
+        params.ftab_k = disable_ft_ ? 0 : ft_k_;
+        detail::Batch b;
+        for (const auto &q : queries) b.add(q);
+        detail::check(rbg_markers_tally(ix_.get(), b.data(), b.off.data(), N, first_fwd.size() == N && N ? first_fwd.data() : nullptr, &params, tally.handle()),
+                      "rbg_markers_tally");
     }
 
     // get_seeds_greedy_w_sample (w_sample) or get_seeds_greedy for many reads: out[i] = the list of queries[i]
