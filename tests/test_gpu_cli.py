@@ -114,8 +114,8 @@ def test_cli_locs_and_markers_stdout(data_dir, tmp_path, small, simple_reads):
 def test_cli_locs_text_made_on_the_device(data_dir, tmp_path, small, simple_reads, error_reads, synth):
     """`rb_align -s` (no -m): the text comes from rbg_align_text -- locs_at, resolve_offset and the decimals on the device
     (k_text.hip) -- and is byte-identical to the oracle's rendering of rb_report (rb_align.cpp:118-139) and to the host
-    formatter (RB_ALIGN_HOST_TEXT=1): reads without a match, names of 1 and of 700 characters (beyond what a workgroup
-    stages in LDS), descriptions, one read per batch, three replicas, and a synthetic pangenome whose reads have tens of
+    formatter (RB_ALIGN_HOST_TEXT=1): reads without a match, names of 1, 300 and 700 characters (the dozen reads still total a
+    few KB, so their one block is staged in LDS; blocks beyond the stage are test_gpu_text_writers.py's), descriptions, one read per batch, three replicas, and a synthetic pangenome whose reads have tens of
     locations in 50 documents, in batches that do not divide the input."""
     import shutil
     rb, o = small
