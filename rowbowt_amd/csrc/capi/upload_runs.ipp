@@ -607,50 +607,19 @@ int upload_marker_table(rbg_index *ix, const RawMarkers &m, DevMarkerTable &t, s
     t.nruns = m.start.size();
     const uint64_t nruns = m.start.size(), n = ix->H().n;
     if (nruns && nruns < 0xFFFFFFFFull) {
-        // about two buckets per run: at_range's two predecessor searches (2 x log2(nruns) dependent
-        // loads) become one table read and a scan over the runs of one bucket
-        uint32_t shift = 0;
-        while (shift < 20 && (n >> shift) > 2 * nruns) ++shift;
-        const uint64_t nb = (n >> shift) + 2;
-        std::vector<uint32_t> bucket(nb);
-        uint64_t j = 0;
-        for (uint64_t b = 0; b < nb; ++b) {
-            const uint64_t first_row = b << shift;
-            while (j < nruns && m.end[j] < first_row) ++j;
-            bucket[b] = static_cast<uint32_t>(j);
-        }
+        // the shift, the directory, the records and the gates they are built under: rbg_mkdir.hpp
+        const uint32_t shift = mk_dir_shift(n, nruns);
+        const uint64_t nb = mk_dir_buckets(n, shift);
+        std::vector<uint32_t> bucket;
+        mk_build_dir(m.end.data(), nruns, n, shift, bucket);
         if ((rc = up(bucket.data(), nb * 4, &p))) return rc;
         t.bucket = static_cast<const uint32_t *>(p);
         t.shift = shift;
-        // the bucket records (rbg_dev.h MkRec): 32 bytes per bucket, i.e. about 64 per run.  RBG_MK_REC=0: the arrays only (A/B, tests)
-        // (32 bytes per bucket = about 64 per marker run: only while that is a small part of the device -- at most an eighth of the free HBM and 16 GB; a marker array
-        //  of 1e9 runs keeps the 4-byte directory)
-        const char *e = std::getenv("RBG_MK_REC");
         size_t free_b = 0, total_b = 0;
         (void)hipMemGetInfo(&free_b, &total_b);
-        const bool rec_fits = nb * sizeof(MkRec) <= std::min<size_t>(free_b / 8, size_t(16) << 30);
-        if (shift <= 16 && !(e && e[0] == '0') && (m.vals.size() >> 40) == 0 && rec_fits) {
-            std::vector<MkRec> recs(nb);
-            for (uint64_t b = 0; b < nb; ++b) {
-                MkRec &R = recs[b];
-                std::memset(&R, 0, sizeof(R));
-                const uint64_t a = bucket[b], first_row = b << shift, end_row = first_row + (uint64_t(1) << shift);
-                R.a = static_cast<uint32_t>(a);
-                const uint64_t off_a = a < nruns ? m.off[a] : m.vals.size();
-                R.off_lo = static_cast<uint32_t>(off_a);
-                R.off_hi = static_cast<uint8_t>(off_a >> 32);
-                uint32_t k = 0;
-                bool over = false;
-                for (uint64_t j2 = a; j2 < nruns && m.start[j2] < end_row; ++j2) {
-                    const uint64_t c = m.off[j2 + 1] - m.off[j2];
-                    if (k == kMkRecRuns || c > 0xFFFF) { over = true; break; }
-                    R.s_off[k] = static_cast<uint16_t>(m.start[j2] > first_row ? m.start[j2] - first_row : 0);
-                    R.e_off[k] = static_cast<uint16_t>(std::min<uint64_t>(m.end[j2] - first_row, 0xFFFF));   // (end >= first_row: j2 >= a)
-                    R.cnt[k] = static_cast<uint16_t>(c);
-                    ++k;
-                }
-                R.nin = over ? static_cast<uint8_t>(kMkRecOverflow) : static_cast<uint8_t>(k);
-            }
+        if (mk_rec_wanted(shift, std::getenv("RBG_MK_REC"), m.vals.size(), nb, free_b)) {
+            std::vector<MkRec> recs;
+            mk_build_recs(m.start.data(), m.end.data(), m.off.data(), nruns, m.vals.size(), shift, bucket, recs);
             if ((rc = up(recs.data(), nb * sizeof(MkRec), &p))) return rc;
             t.rec = static_cast<const MkRec *>(p);
         }

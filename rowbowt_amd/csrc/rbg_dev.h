@@ -10,6 +10,8 @@
 #include <cstdio>
 #include <vector>
 
+#include "rbg_mkdir.hpp"
+
 namespace rbg {
 
 // One run of one symbol.  P = uint32_t when n < 2^32-1, else uint64_t.
@@ -224,22 +226,7 @@ constexpr int kMaxRunDepth = 8;
 constexpr int kLdsRunDepth = 5;
 constexpr int kMaxLdsRunTabs = kLdsSyms + 16 + 64 + 256 + 1024 + kLdsRunDepth;  // records staged in LDS by k_find_range_runs
 
-// One 32-byte record per bucket of the marker directory (round 6): at_range(lo, hi) -- MarkerArray::at_range as rowbowt.hpp:272-290 / :437-441 call it -- from the
-// records of the buckets of lo and hi, ONE or two sectors, instead of a directory entry, the run ends, the run starts and the value offsets (4.9 sectors per query,
-// a third of the marker seeds' misses: profiles/r06_pmc_markers.txt).  `a` = the first run whose end is >= the bucket's first row (what mk_bucket holds), its value
-// offset, and EVERY run from `a` on that starts before the bucket's end, as {start, end} relative to the bucket's first row (start clamped to 0 from below, end to
-// 0xFFFF from above) and its number of values.  Runs are disjoint and ascending, so for lo in this bucket the first run with end >= lo is a + #{listed: end < lo},
-// and for hi in this bucket one past the last run with start <= hi is a + #{listed: start <= hi}; the value offsets follow from off_a and the listed counts.
-// nin == kMkRecOverflow: more than kMkRecRuns such runs, or a run with more than 65535 values: the arrays answer (from `a`, as before).
-constexpr uint32_t kMkRecRuns = 3, kMkRecOverflow = 0xFF;
-struct MkRec {
-    uint32_t a;
-    uint32_t off_lo;
-    uint8_t off_hi, nin;
-    uint16_t s_off[kMkRecRuns], e_off[kMkRecRuns], cnt[kMkRecRuns];
-    uint16_t pad[2];
-};
-static_assert(sizeof(MkRec) == 32, "two marker records per 64-byte sector");
+// (the marker directory's 32-byte bucket records, MkRec: rbg_mkdir.hpp)
 
 struct DevIndex {
     uint64_t n, r;
@@ -354,6 +341,7 @@ enum SearchStat {
     kStSymbols,     // read symbols consumed (reference LF iterations covered)
     kStatSearchN
 };
+static_assert(kMkStatRuns == kStatSearchN + 2, "marker_span_arrays counts the run starts / ends it reads behind the search counters");
 enum LocateStat {
     kLsPhiSteps = 0,  // phi evaluations (PhiSlot loads)
     kLsPhiOvf,        // of them: overflow buckets searched in the run list

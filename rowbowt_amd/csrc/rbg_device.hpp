@@ -347,27 +347,12 @@ inline bool chain_hi8_enabled() {
 }
 
 // ---- the marker query: MarkerArray::at_range(lo, hi) (rowbowt.hpp:272-290, :318, :437-441) as {src, cnt}: the values mk_vals[src, src + cnt) of all runs with
-// start <= hi && end >= lo, in run order.  Runs are disjoint, ascending inclusive SA-index intervals.  From the bucket records (rbg_dev.h MkRec: one or two
+// start <= hi && end >= lo, in run order.  Runs are disjoint, ascending inclusive SA-index intervals.  From the bucket records (rbg_mkdir.hpp MkRec: one or two
 // sectors), else from the directory + the run arrays.  st (instrumented seed walks): [kStatSearchN + 1] += records / directory entries read, [+ 2] += run starts /
 // ends read, [+ 3] += value offsets read.
-// one marker table as the query sees it: the SA-row table (DevIndex::mk_*) or the text-position table (DevIndex::tmk_*), and the length of its key space
-struct MkView {
-    const uint64_t *start, *end, *off, *vals;
-    uint64_t nruns, n;
-    const uint32_t *bucket;
-    const MkRec *rec;
-    uint32_t shift;
-};
+// (MkView, one marker table as the query sees it, the record arithmetic RBG_MK_REC_ANSWER and marker_span_arrays: rbg_mkdir.hpp, shared with the host)
 __device__ __forceinline__ MkView sa_marker_view(const DevIndex &ix) { return MkView{ix.mk_start, ix.mk_end, ix.mk_off, ix.mk_vals, ix.mk_nruns, ix.n, ix.mk_bucket, ix.mk_rec, ix.mk_shift}; }
 __device__ __forceinline__ MkView text_marker_view(const DevIndex &ix) { return MkView{ix.tmk_start, ix.tmk_end, ix.tmk_off, ix.tmk_vals, ix.tmk_nruns, ix.n, ix.tmk_bucket, ix.tmk_rec, ix.tmk_shift}; }
-__device__ __forceinline__ void marker_span_arrays(const MkView &v, uint64_t lo, uint64_t hi, uint64_t a, uint64_t z, uint64_t *first, uint64_t *last, unsigned long long *st) {
-    while (a < v.nruns && v.end[a] < lo) { ++a; if (st) st[kStatSearchN + 2] += 1; }
-    *first = a;
-    if (z < a) z = a;
-    while (z < v.nruns && v.start[z] <= hi) { ++z; if (st) st[kStatSearchN + 2] += 1; }
-    *last = z;
-    if (st) st[kStatSearchN + 2] += 2;
-}
 __device__ __forceinline__ bool marker_query(const MkView &v, uint64_t lo, uint64_t hi, uint64_t *src, uint64_t *cnt, unsigned long long *st = nullptr) {
     if (lo >= v.n) return false;          // caller-supplied rows beyond the BWT: nothing
     if (hi >= v.n) hi = v.n - 1;
@@ -388,18 +373,7 @@ __device__ __forceinline__ bool marker_query(const MkView &v, uint64_t lo, uint6
         if (st) st[kStatSearchN + 1] += b1 != b0 ? 2 : 1;
         if (R0.nin != kMkRecOverflow && R1.nin != kMkRecOverflow) {
             const uint32_t lo_rel = static_cast<uint32_t>(lo - (b0 << sh)), hi_rel = static_cast<uint32_t>(hi - (b1 << sh));
-            uint64_t off_f = static_cast<uint64_t>(R0.off_lo) | (static_cast<uint64_t>(R0.off_hi) << 32);
-            uint64_t off_l = static_cast<uint64_t>(R1.off_lo) | (static_cast<uint64_t>(R1.off_hi) << 32);
-            uint32_t nf = 0, nl = 0;
-#pragma unroll
-            for (uint32_t j = 0; j < kMkRecRuns; ++j) {
-                const bool bf = j < R0.nin && R0.e_off[j] < lo_rel;      // (ends ascend: a prefix of the listed runs)
-                const bool bl = j < R1.nin && R1.s_off[j] <= hi_rel;     // (starts ascend)
-                nf += bf ? 1u : 0u; off_f += bf ? R0.cnt[j] : 0u;
-                nl += bl ? 1u : 0u; off_l += bl ? R1.cnt[j] : 0u;
-            }
-            f = static_cast<uint64_t>(R0.a) + nf;
-            l = static_cast<uint64_t>(R1.a) + nl;
+            RBG_MK_REC_ANSWER(R0, R1, lo_rel, hi_rel, f, l, off_f, off_l)
             if (l <= f) return false;
             *src = off_f;
             *cnt = off_l - off_f;
