@@ -1,4 +1,5 @@
-// capi/report.ipp -- rb_markers' report on the device (k_report.hip): the device steps and the two host calls above them.  Part of rbg_capi.hip.
+// capi/report.ipp -- rb_markers' report on the device (k_report.hip): the device steps and the three host calls above them (records, text, tally), one
+// pass of reads at a time: stage + strands, the seed pass (seeds.ipp), canon + select, then one of emit_records / emit_text / emit_tally.  Part of rbg_capi.hip.
 namespace {
 constexpr uint32_t kReportFlags = RBG_REPORT_LMEM | RBG_REPORT_HEURISTIC | RBG_REPORT_BEST_STRAND | RBG_REPORT_CLEAR_CONFLICTING | RBG_REPORT_CLEAR_IDENTICAL;
 
@@ -34,6 +35,28 @@ struct ReportTrace {
 };
 ReportTrace g_report_trace;
 
+// one pass's share of the trace: lap(slot) charges the time since the last lap to a slot.  Without tracing it does nothing, a synchronisation least of all.
+struct ReportLap {
+    hipStream_t st;
+    double t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::chrono::steady_clock::time_point from = std::chrono::steady_clock::now();
+    void operator()(int slot) {
+        if (!g_report_trace.on) return;
+        (void)hipStreamSynchronize(st);
+        const auto now = std::chrono::steady_clock::now();
+        t[slot] += std::chrono::duration<double>(now - from).count();
+        from = now;
+    }
+    void done(uint64_t reads, uint64_t d2h_bytes) {   // a finished pass joins the process's sums
+        if (!g_report_trace.on) return;
+        std::lock_guard<std::mutex> g(g_report_trace.mu);
+        for (int j = 0; j < 8; ++j) g_report_trace.t[j] += t[j];
+        g_report_trace.passes += 1;
+        g_report_trace.reads += reads;
+        g_report_trace.d2h += d2h_bytes;
+    }
+};
+
 struct ReportOut {   // where a call's result goes
     // records
     uint64_t *seed_off = nullptr;
@@ -48,6 +71,21 @@ struct ReportOut {   // where a call's result goes
     size_t text_cap = 0, text_len = 0;
     // tally: the printed records' markers are added on the device, nothing is copied out
     rbg_tally *tally = nullptr;
+};
+
+struct ReportPass {   // reads [a, b) of the batch on the device, from step to step
+    uint64_t a = 0, n = 0, bytes = 0;        // the first read, how many, their bytes
+    uint64_t batch_bytes = 0;                // (of all N reads)
+    bool last = false;
+    ReportLap lap;
+    uint64_t d2h_bytes = 0;
+    DevBuf draw, doff, dcoin, dseq2, doff2;  // stage: the raw reads, their offsets and coins; the 2n strands and theirs
+    std::vector<uint64_t> roff;              // (the offsets on the host: an asynchronous copy reads them, so they live as long as the pass)
+    const uint8_t *d_coin = nullptr;
+    SeedPass seeds;                          // the strands' seed records (canonical after select_records) and markers
+    DevBuf dctmp, drep, drecs, dread, dstmp, dmelem, dws;   // select: printed records per read, the records, their reads; the element map of the outputs
+    size_t stmp_bytes = 0, ws_bytes = 0;
+    uint64_t R = 0, M = 0, E = 0;            // printed records, their markers, R + M
 };
 
 // room for `need` bytes in the call's pinned text buffer (what is there is kept; no copy is in flight when this is called)
@@ -70,208 +108,185 @@ int report_text_room(rbg_index *ix, ReportOut &o, size_t need, size_t hint) {
     return RBG_OK;
 }
 
-// reads [a, b) of the batch: strands -> seeds -> canon -> select -> records, text or tally
+// the raw reads and their offsets go in (off[a] is not 0 in a later pass: the strand kernel subtracts it), the 2n strands come out
+int stage_strands(const uint8_t *seqs, const uint64_t *off, const uint8_t *first_fwd, const rbg_report_params_t &P, ReportPass &p, hipStream_t st) {
+    const uint64_t a = p.a, n = p.n, b = a + n;
+    int rc;
+    const uint64_t first16 = off[a] & ~uint64_t(15), raw_bytes = off[b] - first16;
+    p.roff.resize(n + 1);
+    for (uint64_t i = 0; i <= n; ++i) p.roff[i] = off[a + i] - first16;
+    if ((rc = p.draw.alloc(((raw_bytes + 15) & ~uint64_t(15)) + 16)) || (rc = p.doff.alloc((n + 1) * 8)) ||
+        (rc = p.dseq2.alloc(((2 * p.bytes + 15) & ~uint64_t(15)) + 16)) || (rc = p.doff2.alloc((2 * n + 1) * 8)))
+        return rc;
+    if (raw_bytes) HIP_TRY(hipMemcpyAsync(p.draw.p, seqs + first16, raw_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(p.doff.p, p.roff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+    if (first_fwd && (P.flags & RBG_REPORT_HEURISTIC)) {
+        if ((rc = p.dcoin.alloc(n))) return rc;
+        HIP_TRY(hipMemcpyAsync(p.dcoin.p, first_fwd + a, n, hipMemcpyHostToDevice, st));
+        p.d_coin = p.dcoin.as<uint8_t>();
+    }
+    return launch_read_strands(p.draw.as<uint8_t>(), p.doff.as<uint64_t>(), n, p.bytes, p.dseq2.as<uint8_t>(), p.doff2.as<uint64_t>(), st) ? RBG_ENODEV : RBG_OK;
+}
+
+// canonical records, then the printed records of every read: R of them in drecs, the read of each in dread
+int select_records(rbg_index *ix, const rbg_report_params_t &P, ReportOut &o, ReportPass &p, hipStream_t st) {
+    SeedPass &sp = p.seeds;
+    const uint64_t n = p.n, S = sp.S;
+    int rc;
+    const size_t ctmp_bytes = seed_canon_tmp_bytes(S);
+    if ((rc = p.dctmp.alloc(ctmp_bytes))) return rc;
+    const uint32_t cflags = (P.flags & RBG_REPORT_HEURISTIC) ? P.flags & (RBG_REPORT_CLEAR_CONFLICTING | RBG_REPORT_CLEAR_IDENTICAL) : 0;
+    if (sp.total_mk && launch_seed_canon(ix->cfg, sp.dseeds.as<uint64_t>(), S, sp.dmk.as<uint64_t>(), P.min_range, cflags, P.read_len, p.dctmp.p, ctmp_bytes, report_canon_group(), st))
+        return RBG_ENODEV;
+    p.lap(3);
+    p.stmp_bytes = scan_tmp_bytes(std::max<uint64_t>(n, S));
+    if ((rc = p.drep.alloc((n + 1) * 8)) || (rc = p.drecs.alloc(S * sizeof(rbg_report_seed_t))) || (rc = p.dread.alloc(S * 4)) || (rc = p.dstmp.alloc(p.stmp_bytes)) ||
+        (rc = p.dmelem.alloc((S + 1) * 8)))
+        return rc;
+    if (launch_report_select(sp.dseeds.as<uint64_t>(), sp.d_rec_off, p.doff2.as<uint64_t>(), n, p.d_coin, P.read_len, P.min_seed_len, P.flags, p.drep.as<uint64_t>(), p.drecs.p,
+                             p.dread.as<uint32_t>(), p.dstmp.p, p.stmp_bytes, st))
+        return RBG_ENODEV;
+    if (o.want_text || o.tally) {   // (only the records output tells its caller which read printed what)
+        HIP_TRY(hipMemcpyAsync(&p.R, p.drep.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return RBG_OK;
+    }
+    std::vector<uint64_t> rep_off(n + 1);
+    HIP_TRY(hipMemcpyAsync(rep_off.data(), p.drep.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    p.R = rep_off[n];
+    const uint64_t base = o.recs.size();
+    for (uint64_t i = 0; i < n; ++i) o.seed_off[p.a + i + 1] = base + rep_off[i + 1];
+    return RBG_OK;
+}
+
+// records: the printed records and their markers, dense, behind what the passes before left in o
+int emit_records(ReportOut &o, ReportPass &p, hipStream_t st) {
+    const uint64_t R = p.R, M = p.M;
+    int rc;
+    DevBuf drecs2, ddense;
+    if ((rc = drecs2.alloc(R * sizeof(rbg_report_seed_t))) || (rc = ddense.alloc(M * 8))) return rc;
+    if (launch_report_gather(p.drecs.p, p.dmelem.as<uint64_t>(), p.seeds.dmk.as<uint64_t>(), R, p.E, p.dws.p, p.ws_bytes, drecs2.p, ddense.as<uint64_t>(), st)) return RBG_ENODEV;
+    p.lap(5);
+    const uint64_t rbase = o.recs.size(), mbase = o.mk.size();
+    o.recs.resize(rbase + R);
+    o.mk.resize(mbase + M);
+    if ((rc = d2h_result(o.recs.data() + rbase, drecs2.p, R * sizeof(rbg_report_seed_t), st))) return rc;
+    if (M && (rc = d2h_result(o.mk.data() + mbase, ddense.p, M * 8, st))) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    rebase_markers(o.recs.data() + rbase, R, mbase);
+    p.d2h_bytes = R * sizeof(rbg_report_seed_t) + M * 8 + (p.n + 1) * 8;
+    return RBG_OK;
+}
+
+// a pass's text to its place in the call's pinned buffer.  behind: the last pass's copy runs on the handle's copy stream behind the fill kernel; the caller
+// returns at once and the text's reader waits (rbg_wait_text), as in rbg_align_text
+int copy_text_out(rbg_index *ix, ReportOut &o, char *dst, DevBuf &dtext, uint64_t total, bool behind, hipStream_t st) {
+    if (!behind) {
+        HIP_TRY(hipMemcpyAsync(dst, dtext.p, total, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return RBG_OK;
+    }
+    std::lock_guard<std::mutex> g(ix->text_mu);
+    rbg_index::TextOut *t = find_text_out(ix, o.text);
+    hipError_t e = hipEventRecord(t->done, st);
+    if (e == hipSuccess) e = hipStreamWaitEvent(ix->text_copy_stream, t->done, 0);
+    if (e == hipSuccess) e = hipMemcpyAsync(dst, dtext.p, total, hipMemcpyDeviceToHost, ix->text_copy_stream);
+    if (e == hipSuccess) e = hipEventRecord(t->done, ix->text_copy_stream);
+    HIP_TRY(e);
+    t->pending = true;
+    t->d_text = dtext.p; t->d_cls = dtext.cls; t->d_dev = dtext.dev;
+    dtext.p = nullptr;   // (the record owns the device block until the copy has been waited for)
+    return RBG_OK;
+}
+
+// text: the pass's lines written on the device, copied behind the text of the passes before
+int emit_text(rbg_index *ix, ReportOut &o, ReportPass &p, hipStream_t st) {
+    const uint64_t a = p.a, n = p.n, R = p.R, E = p.E;
+    int rc;
+    // the names of the pass, back to back
+    std::vector<uint32_t> noff(n + 1);
+    uint64_t name_bytes = 0;
+    for (uint64_t i = 0; i < n; ++i) { noff[i] = static_cast<uint32_t>(name_bytes); name_bytes += o.name_len[a + i]; }
+    if (name_bytes >> 32) return RBG_EARG;
+    noff[n] = static_cast<uint32_t>(name_bytes);
+    std::vector<char> blob(name_bytes + 1);
+    parallel_for(n, [&](uint64_t x, uint64_t y, unsigned) {
+        for (uint64_t i = x; i < y; ++i) std::memcpy(blob.data() + noff[i], o.name_base + o.name_begin[a + i], o.name_len[a + i]);
+    });
+    DevBuf dnoff, dnames, dtext;
+    if ((rc = dnoff.alloc((n + 1) * 4)) || (rc = dnames.alloc(name_bytes + 1))) return rc;
+    HIP_TRY(hipMemcpyAsync(dnoff.p, noff.data(), (n + 1) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dnames.p, blob.data(), name_bytes + 1, hipMemcpyHostToDevice, st));
+    if (launch_report_text_plan(p.drecs.p, p.dread.as<uint32_t>(), p.dmelem.as<uint64_t>(), p.seeds.dmk.as<uint64_t>(), R, E, dnames.as<char>(), dnoff.as<uint32_t>(), p.dws.p,
+                                p.ws_bytes, st))
+        return RBG_ENODEV;
+    const uint64_t *p_at = nullptr;
+    const uint32_t *p_len = nullptr;
+    report_text_total_ptrs(p.dws.p, E, &p_at, &p_len);
+    uint64_t last_at = 0;
+    uint32_t last_len = 0;
+    HIP_TRY(hipMemcpyAsync(&last_at, p_at, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&last_len, p_len, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // (the name blob has been copied too)
+    const uint64_t total = last_at + last_len;
+    if ((rc = dtext.alloc(total))) return rc;
+    if (launch_report_text_fill(p.drecs.p, p.dread.as<uint32_t>(), p.dmelem.as<uint64_t>(), p.seeds.dmk.as<uint64_t>(), R, E, dnames.as<char>(), dnoff.as<uint32_t>(), p.dws.p,
+                                p.ws_bytes, total, dtext.as<char>(), st))
+        return RBG_ENODEV;
+    p.lap(5);
+    // (a first pass that is not the last sizes the buffer for the whole batch from its own text per read byte)
+    const size_t hint = p.last || !p.bytes ? 0 : static_cast<size_t>(static_cast<double>(total) / static_cast<double>(p.bytes) * static_cast<double>(p.batch_bytes) * 1.25);
+    if ((rc = report_text_room(ix, o, o.text_len + total, hint))) return rc;
+    char *dst = o.text + o.text_len;
+    o.text_len += total;
+    p.d2h_bytes = total;
+    return copy_text_out(ix, o, dst, dtext, total, p.last && !g_report_trace.on, st);
+}
+
+// tally: room was reserved between the seed phases; the add is the pass's last launch and nothing comes back
+int emit_tally(ReportOut &o, ReportPass &p, hipStream_t st) {
+    return tally_add_mapped(o.tally, p.drecs.p, p.R, p.seeds.dmk.as<uint64_t>(), p.dmelem.as<uint64_t>(), p.seeds.total_mk, st);
+}
+
+// reads [a, b) of the batch: strands -> seeds -> canon -> select -> records, text or tally.  The trace's slots in their order: 0 copy in + strands, 1 plan,
+// 2 fill, 3 canon (select_records laps it before its second launch), 4 select, then 7 tally, or 5 gather or text (the emit laps it before it copies) and 6 copy out
 int report_pass(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, uint64_t a, uint64_t b, uint64_t N, const uint8_t *first_fwd,
                 const rbg_report_params_t &P, ReportOut &o, hipStream_t st) {
-    const uint64_t n = b - a, bytes = off[b] - off[a];
-    const bool lmem = (P.flags & RBG_REPORT_LMEM) != 0, last = b == N;
+    ReportPass p;
+    p.a = a; p.n = b - a; p.bytes = off[b] - off[a]; p.batch_bytes = off[N] - off[0]; p.last = b == N;
+    p.lap.st = st;
+    SeedPass &sp = p.seeds;
+    const bool lmem = (P.flags & RBG_REPORT_LMEM) != 0;
     int rc;
-    double lap_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto lap_from = std::chrono::steady_clock::now();
-    auto lap = [&](int slot) {
-        if (!g_report_trace.on) return;
-        (void)hipStreamSynchronize(st);
-        const auto now = std::chrono::steady_clock::now();
-        lap_t[slot] += std::chrono::duration<double>(now - lap_from).count();
-        lap_from = now;
-    };
-    uint64_t d2h_bytes = 0;
-    // the raw reads and their offsets (off[a] is not 0 in a later pass: the strand kernel subtracts it)
-    DevBuf draw, doff, dcoin, dseq2, doff2;
-    const uint64_t first16 = off[a] & ~uint64_t(15), raw_bytes = off[b] - first16;
-    std::vector<uint64_t> roff(n + 1);
-    for (uint64_t i = 0; i <= n; ++i) roff[i] = off[a + i] - first16;
-    if ((rc = draw.alloc(((raw_bytes + 15) & ~uint64_t(15)) + 16)) || (rc = doff.alloc((n + 1) * 8)) || (rc = dseq2.alloc(((2 * bytes + 15) & ~uint64_t(15)) + 16)) ||
-        (rc = doff2.alloc((2 * n + 1) * 8)))
-        return rc;
-    if (raw_bytes) HIP_TRY(hipMemcpyAsync(draw.p, seqs + first16, raw_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(doff.p, roff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
-    const uint8_t *d_coin = nullptr;
-    if (first_fwd && (P.flags & RBG_REPORT_HEURISTIC)) {
-        if ((rc = dcoin.alloc(n))) return rc;
-        HIP_TRY(hipMemcpyAsync(dcoin.p, first_fwd + a, n, hipMemcpyHostToDevice, st));
-        d_coin = dcoin.as<uint8_t>();
-    }
-    if (launch_read_strands(draw.as<uint8_t>(), doff.as<uint64_t>(), n, bytes, dseq2.as<uint8_t>(), doff2.as<uint64_t>(), st)) return RBG_ENODEV;
-    lap(0);
-    // the seeds of the 2n sequences
-    const uint64_t n2 = 2 * n;
-    DevBuf dsoff, dmoff, dtmp, dlog, dseeds, dmk;
-    const uint64_t *d_seed_off = nullptr;
-    uint64_t S = 0, total_mk = 0;
-    if (!lmem) {
-        const size_t tmp_bytes = scan_tmp_bytes(n2);
-        if ((rc = dsoff.alloc((n2 + 1) * 8)) || (rc = dmoff.alloc((n2 + 1) * 8)) || (rc = dtmp.alloc(tmp_bytes))) return rc;
-        size_t log_bytes = seed_log_bytes(n2, ix->H().pos_bytes, kSeedLogSeedsDefault);
-        if (dlog.alloc(log_bytes)) log_bytes = 0;
-        if (launch_marker_seeds_plan(ix->dev, ix->cfg, dseq2.as<uint8_t>(), doff2.as<uint64_t>(), n2, P.wsize, P.max_range, P.ftab_k, dsoff.as<uint64_t>(),
-                                     dmoff.as<uint64_t>(), dtmp.p, tmp_bytes, st, log_bytes ? dlog.p : nullptr, log_bytes))
-            return RBG_ENODEV;
-        HIP_TRY(hipMemcpyAsync(&S, dsoff.as<uint64_t>() + n2, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(&total_mk, dmoff.as<uint64_t>() + n2, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        lap(1);
-        if (S >> 32) return RBG_EARG;   // (a pass holds at most 64 MiB of reads)
-        if (o.tally && (rc = tally_reserve(o.tally, total_mk))) return rc;   // (total_mk bounds the pass's elements from above: canon and select only drop)
-        if ((rc = dseeds.alloc(S * sizeof(rbg_marker_seed_t))) || (rc = dmk.alloc(total_mk * 8))) return rc;
-        if (S && launch_marker_seeds_fill(ix->dev, ix->cfg, dseq2.as<uint8_t>(), doff2.as<uint64_t>(), n2, P.wsize, P.max_range, P.ftab_k, dsoff.as<uint64_t>(),
-                                          dmoff.as<uint64_t>(), dseeds.as<uint64_t>(), dmk.as<uint64_t>(), st, log_bytes ? dlog.p : nullptr, log_bytes))
-            return RBG_ENODEV;
-        d_seed_off = dsoff.as<uint64_t>();
-    } else {
-        S = 2 * bytes;   // one record per end position of every strand
-        if (S >> 32) return RBG_EARG;
-        const size_t tmp_bytes = marker_lmems_tmp_bytes(S);
-        if ((rc = dmoff.alloc((n2 + 1) * 8)) || (rc = dtmp.alloc(tmp_bytes))) return rc;
-        if (launch_marker_lmems_plan(ix->dev, ix->cfg, dseq2.as<uint8_t>(), doff2.as<uint64_t>(), n2, S, P.wsize, P.max_range, P.ftab_k, dmoff.as<uint64_t>(), dtmp.p,
-                                     tmp_bytes, st))
-            return RBG_ENODEV;
-        HIP_TRY(hipMemcpyAsync(&total_mk, dmoff.as<uint64_t>() + n2, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        lap(1);
-        if (o.tally && (rc = tally_reserve(o.tally, total_mk))) return rc;
-        if ((rc = dseeds.alloc(S * sizeof(rbg_marker_seed_t))) || (rc = dmk.alloc(total_mk * 8))) return rc;
-        if (S && launch_marker_lmems_fill(ix->dev, ix->cfg, dseq2.as<uint8_t>(), doff2.as<uint64_t>(), n2, S, P.wsize, P.max_range, P.ftab_k, dtmp.p,
-                                          dseeds.as<uint64_t>(), dmk.as<uint64_t>(), st))
-            return RBG_ENODEV;
-        d_seed_off = doff2.as<uint64_t>();
-    }
-    lap(2);
-    // canonical records
-    DevBuf dctmp;
-    const size_t ctmp_bytes = seed_canon_tmp_bytes(S);
-    if ((rc = dctmp.alloc(ctmp_bytes))) return rc;
-    const uint32_t cflags = (P.flags & RBG_REPORT_HEURISTIC) ? P.flags & (RBG_REPORT_CLEAR_CONFLICTING | RBG_REPORT_CLEAR_IDENTICAL) : 0;
-    if (total_mk && launch_seed_canon(ix->cfg, dseeds.as<uint64_t>(), S, dmk.as<uint64_t>(), P.min_range, cflags, P.read_len, dctmp.p, ctmp_bytes, report_canon_group(), st))
-        return RBG_ENODEV;
-    lap(3);
-    // the printed records of every read
-    DevBuf drep, drecs, dread, dstmp, dmelem;
-    const size_t stmp_bytes = scan_tmp_bytes(std::max<uint64_t>(n, S));
-    if ((rc = drep.alloc((n + 1) * 8)) || (rc = drecs.alloc(S * sizeof(rbg_report_seed_t))) || (rc = dread.alloc(S * 4)) || (rc = dstmp.alloc(stmp_bytes)) ||
-        (rc = dmelem.alloc((S + 1) * 8)))
-        return rc;
-    if (launch_report_select(dseeds.as<uint64_t>(), d_seed_off, doff2.as<uint64_t>(), n, d_coin, P.read_len, P.min_seed_len, P.flags, drep.as<uint64_t>(), drecs.p,
-                             dread.as<uint32_t>(), dstmp.p, stmp_bytes, st))
-        return RBG_ENODEV;
-    uint64_t R = 0, M = 0;
-    std::vector<uint64_t> rep_off;
-    if (o.want_text || o.tally) {
-        HIP_TRY(hipMemcpyAsync(&R, drep.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
-    } else {
-        rep_off.resize(n + 1);
-        HIP_TRY(hipMemcpyAsync(rep_off.data(), drep.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    if (!o.want_text && !o.tally) {
-        R = rep_off[n];
-        const uint64_t base = o.recs.size();
-        for (uint64_t i = 0; i < n; ++i) o.seed_off[a + i + 1] = base + rep_off[i + 1];
-    }
-    lap(4);
-    if (R) {
-        if (launch_report_melem(drecs.p, R, dmelem.as<uint64_t>(), dstmp.p, stmp_bytes, st)) return RBG_ENODEV;
-        if (o.tally) {   // (room was reserved above; the add is the pass's last launch and nothing comes back)
-            if ((rc = tally_add_mapped(o.tally, drecs.p, R, dmk.as<uint64_t>(), dmelem.as<uint64_t>(), total_mk, st))) return rc;
-            lap(7);
-        } else {
-            HIP_TRY(hipMemcpyAsync(&M, dmelem.as<uint64_t>() + R, 8, hipMemcpyDeviceToHost, st));
+    if ((rc = stage_strands(seqs, off, first_fwd, P, p, st))) return rc;
+    p.lap(0);
+    if (lmem && p.bytes >> 31) return RBG_EARG;   // (lmem: S = 2 * bytes is known before the plan, which sizes its scratch by it)
+    if ((rc = seed_pass_plan(ix, sp, p.dseq2.as<uint8_t>(), p.doff2.as<uint64_t>(), 2 * p.n, 2 * p.bytes, P.wsize, P.max_range, P.ftab_k, lmem, st))) return rc;
+    p.lap(1);
+    if (sp.S >> 32) return RBG_EARG;   // (a pass holds at most 64 MiB of reads)
+    if (o.tally && (rc = tally_reserve(o.tally, sp.total_mk))) return rc;   // (total_mk bounds the pass's elements from above: canon and select only drop)
+    if ((rc = seed_pass_fill(ix, sp, st))) return rc;
+    p.lap(2);
+    if ((rc = select_records(ix, P, o, p, st))) return rc;
+    p.lap(4);
+    if (p.R) {
+        if (launch_report_melem(p.drecs.p, p.R, p.dmelem.as<uint64_t>(), p.dstmp.p, p.stmp_bytes, st)) return RBG_ENODEV;
+        if (o.tally) {
+            if ((rc = emit_tally(o, p, st))) return rc;
+            p.lap(7);
+        } else {   // the element -> record map of the printed records' markers, for the records and the text (the tally keeps a map of its own)
+            HIP_TRY(hipMemcpyAsync(&p.M, p.dmelem.as<uint64_t>() + p.R, 8, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            const uint64_t E = R + M;
-            DevBuf dws;
-            const size_t ws_bytes = report_text_ws_bytes(E);
-            if ((rc = dws.alloc(ws_bytes))) return rc;
-            if (launch_report_map(dmelem.as<uint64_t>(), R, E, dws.p, ws_bytes, st)) return RBG_ENODEV;
-            if (!o.want_text) {
-                DevBuf drecs2, ddense;
-                if ((rc = drecs2.alloc(R * sizeof(rbg_report_seed_t))) || (rc = ddense.alloc(M * 8))) return rc;
-                if (launch_report_gather(drecs.p, dmelem.as<uint64_t>(), dmk.as<uint64_t>(), R, E, dws.p, ws_bytes, drecs2.p, ddense.as<uint64_t>(), st)) return RBG_ENODEV;
-                lap(5);
-                const uint64_t rbase = o.recs.size(), mbase = o.mk.size();
-                o.recs.resize(rbase + R);
-                o.mk.resize(mbase + M);
-                if ((rc = d2h_result(o.recs.data() + rbase, drecs2.p, R * sizeof(rbg_report_seed_t), st))) return rc;
-                if (M && (rc = d2h_result(o.mk.data() + mbase, ddense.p, M * 8, st))) return rc;
-                HIP_TRY(hipStreamSynchronize(st));
-                if (mbase)
-                    for (uint64_t r = rbase; r < rbase + R; ++r) { o.recs[r].mk_begin += mbase; o.recs[r].mk_end += mbase; }
-                d2h_bytes = R * sizeof(rbg_report_seed_t) + M * 8 + (n + 1) * 8;
-            } else {
-                // the names of the pass, back to back
-                std::vector<uint32_t> noff(n + 1);
-                uint64_t name_bytes = 0;
-                for (uint64_t i = 0; i < n; ++i) { noff[i] = static_cast<uint32_t>(name_bytes); name_bytes += o.name_len[a + i]; }
-                if (name_bytes >> 32) return RBG_EARG;
-                noff[n] = static_cast<uint32_t>(name_bytes);
-                std::vector<char> blob(name_bytes + 1);
-                parallel_for(n, [&](uint64_t x, uint64_t y, unsigned) {
-                    for (uint64_t i = x; i < y; ++i) std::memcpy(blob.data() + noff[i], o.name_base + o.name_begin[a + i], o.name_len[a + i]);
-                });
-                DevBuf dnoff, dnames, dtext;
-                if ((rc = dnoff.alloc((n + 1) * 4)) || (rc = dnames.alloc(name_bytes + 1))) return rc;
-                HIP_TRY(hipMemcpyAsync(dnoff.p, noff.data(), (n + 1) * 4, hipMemcpyHostToDevice, st));
-                HIP_TRY(hipMemcpyAsync(dnames.p, blob.data(), name_bytes + 1, hipMemcpyHostToDevice, st));
-                if (launch_report_text_plan(drecs.p, dread.as<uint32_t>(), dmelem.as<uint64_t>(), dmk.as<uint64_t>(), R, E, dnames.as<char>(), dnoff.as<uint32_t>(), dws.p,
-                                            ws_bytes, st))
-                    return RBG_ENODEV;
-                const uint64_t *p_at = nullptr;
-                const uint32_t *p_len = nullptr;
-                report_text_total_ptrs(dws.p, E, &p_at, &p_len);
-                uint64_t last_at = 0;
-                uint32_t last_len = 0;
-                HIP_TRY(hipMemcpyAsync(&last_at, p_at, 8, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipMemcpyAsync(&last_len, p_len, 4, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));   // (the name blob has been copied too)
-                const uint64_t total = last_at + last_len;
-                if ((rc = dtext.alloc(total))) return rc;
-                if (launch_report_text_fill(drecs.p, dread.as<uint32_t>(), dmelem.as<uint64_t>(), dmk.as<uint64_t>(), R, E, dnames.as<char>(), dnoff.as<uint32_t>(), dws.p,
-                                            ws_bytes, total, dtext.as<char>(), st))
-                    return RBG_ENODEV;
-                lap(5);
-                // (a first pass that is not the last sizes the buffer for the whole batch from its own text per read byte)
-                const size_t hint = last || !bytes ? 0 : static_cast<size_t>(static_cast<double>(total) / static_cast<double>(bytes) * static_cast<double>(off[N] - off[0]) * 1.25);
-                if ((rc = report_text_room(ix, o, o.text_len + total, hint))) return rc;
-                char *dst = o.text + o.text_len;
-                o.text_len += total;
-                d2h_bytes = total;
-                if (!last || g_report_trace.on) {
-                    HIP_TRY(hipMemcpyAsync(dst, dtext.p, total, hipMemcpyDeviceToHost, st));
-                    HIP_TRY(hipStreamSynchronize(st));
-                } else {
-                    // the last copy-out runs on the handle's copy stream behind the fill kernel; the caller returns at once and the text's reader
-                    // waits (rbg_wait_text), as in rbg_align_text
-                    std::lock_guard<std::mutex> g(ix->text_mu);
-                    rbg_index::TextOut *t = find_text_out(ix, o.text);
-                    hipError_t e = hipEventRecord(t->done, st);
-                    if (e == hipSuccess) e = hipStreamWaitEvent(ix->text_copy_stream, t->done, 0);
-                    if (e == hipSuccess) e = hipMemcpyAsync(dst, dtext.p, total, hipMemcpyDeviceToHost, ix->text_copy_stream);
-                    if (e == hipSuccess) e = hipEventRecord(t->done, ix->text_copy_stream);
-                    HIP_TRY(e);
-                    t->pending = true;
-                    t->d_text = dtext.p; t->d_cls = dtext.cls; t->d_dev = dtext.dev;
-                    dtext.p = nullptr;   // (the record owns the device block until the copy has been waited for)
-                }
-            }
-            lap(6);
+            p.E = p.R + p.M;
+            p.ws_bytes = report_text_ws_bytes(p.E);
+            if ((rc = p.dws.alloc(p.ws_bytes))) return rc;
+            if (launch_report_map(p.dmelem.as<uint64_t>(), p.R, p.E, p.dws.p, p.ws_bytes, st)) return RBG_ENODEV;
+            if ((rc = o.want_text ? emit_text(ix, o, p, st) : emit_records(o, p, st))) return rc;
+            p.lap(6);
         }
     }
-    if (g_report_trace.on) {
-        std::lock_guard<std::mutex> g(g_report_trace.mu);
-        for (int j = 0; j < 8; ++j) g_report_trace.t[j] += lap_t[j];
-        g_report_trace.passes += 1;
-        g_report_trace.reads += n;
-        g_report_trace.d2h += d2h_bytes;
-    }
+    p.lap.done(p.n, p.d2h_bytes);
     return RBG_OK;
 }
 
@@ -288,8 +303,7 @@ int report_run(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, uint64_t
     hipStream_t st = hipStreamPerThread;
     const uint64_t chunk = report_chunk_bytes((params->flags & RBG_REPORT_LMEM) != 0);
     for (uint64_t a = 0; a < N && !rc;) {
-        uint64_t b = a + 1;   // reads [a, b): at least one, and as many whole ones as fit the chunk (and 2^31 records' worth at most)
-        while (b < N && off[b + 1] - off[a] <= chunk && b - a < (uint64_t(1) << 28)) ++b;
+        const uint64_t b = pass_end(off, N, a, chunk, uint64_t(1) << 28);   // (2^31 records' worth of reads at most)
         rc = report_pass(ix, seqs, off, a, b, N, first_fwd, *params, o, st);
         a = b;
     }

@@ -1,4 +1,102 @@
-// capi/seeds.ipp -- markers, marker seeds and greedy seeding (rb_markers' path), device and host entry points.  Part of rbg_capi.hip.
+// capi/seeds.ipp -- markers, marker seeds and greedy seeding (rb_markers' path), device and host entry points; the seed pass and the pass splitter
+// that the host calls here and the report (report.ipp) share.  Part of rbg_capi.hip.
+namespace {
+// One device pass of marker seeds over n staged sequences, greedy (get_markers_greedy_seeding) or lmem (get_markers_lmems), in the kernels' two phases:
+// seed_pass_plan() counts, seed_pass_fill() writes.  marker_seeds_host(), rbg_get_markers_lmems() and the report's report_pass() run their seeds
+// through these two; what differs between them -- staging, copy-out, the tally's reserve between the phases -- stays with them.
+struct SeedPass {
+    DevBuf dsoff, dmoff, dtmp, dlog, dseeds, dmk;   // seed offsets and the log (greedy), marker offsets, scan scratch (lmem: the records' marker offsets too), records, markers
+    size_t tmp_bytes = 0, log_bytes = 0;            // (log_bytes == 0: no log, the fill walks again)
+    const uint8_t *d_seqs = nullptr;                // the plan's arguments, kept for the fill
+    const uint64_t *d_off = nullptr;
+    uint64_t n = 0, wsize = 0, max_range = 0, ftab_k = 0;
+    bool lmem = false;
+    uint64_t S = 0, total_mk = 0;                   // what the plan found: records and markers of the pass (lmem: one record per end position, S = the sequences' bytes)
+    const uint64_t *d_rec_off = nullptr;            // on the device: the first record of every sequence, n + 1 values (greedy: the scanned dsoff; lmem: the sequences' own offsets)
+};
+
+// The n sequences are on the device, d_off[0] == 0 and d_off[n] == total_bytes.  Returns with the stream synchronised and S and total_mk known.
+// h_seed_off (greedy, nullable): every sequence's first record for the caller, n + 1 values, out of the same copy-back.
+int seed_pass_plan(rbg_index *ix, SeedPass &sp, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t n, uint64_t total_bytes, uint64_t wsize, uint64_t max_range,
+                   uint64_t ftab_k, bool lmem, hipStream_t st, uint64_t *h_seed_off = nullptr) {
+    sp.d_seqs = d_seqs; sp.d_off = d_off; sp.n = n; sp.wsize = wsize; sp.max_range = max_range; sp.ftab_k = ftab_k; sp.lmem = lmem;
+    int rc;
+    if (lmem) {
+        sp.S = total_bytes;
+        sp.d_rec_off = d_off;
+        sp.tmp_bytes = marker_lmems_tmp_bytes(sp.S);
+        if ((rc = sp.dmoff.alloc((n + 1) * 8)) || (rc = sp.dtmp.alloc(sp.tmp_bytes))) return rc;
+        if (launch_marker_lmems_plan(ix->dev, ix->cfg, d_seqs, d_off, n, sp.S, wsize, max_range, ftab_k, sp.dmoff.as<uint64_t>(), sp.dtmp.p, sp.tmp_bytes, st)) return RBG_ENODEV;
+    } else {
+        sp.tmp_bytes = scan_tmp_bytes(n);
+        if ((rc = sp.dsoff.alloc((n + 1) * 8)) || (rc = sp.dmoff.alloc((n + 1) * 8)) || (rc = sp.dtmp.alloc(sp.tmp_bytes))) return rc;
+        sp.d_rec_off = sp.dsoff.as<uint64_t>();
+        // the log between the two phases (one walk instead of two); without the memory for it the fill pass walks again
+        sp.log_bytes = seed_log_bytes(n, ix->H().pos_bytes, kSeedLogSeedsDefault);
+        if (sp.dlog.alloc(sp.log_bytes)) sp.log_bytes = 0;
+        if (launch_marker_seeds_plan(ix->dev, ix->cfg, d_seqs, d_off, n, wsize, max_range, ftab_k, sp.dsoff.as<uint64_t>(), sp.dmoff.as<uint64_t>(), sp.dtmp.p, sp.tmp_bytes, st,
+                                     sp.log_bytes ? sp.dlog.p : nullptr, sp.log_bytes))
+            return RBG_ENODEV;
+        if (h_seed_off) HIP_TRY(hipMemcpyAsync(h_seed_off, sp.dsoff.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+        else HIP_TRY(hipMemcpyAsync(&sp.S, sp.dsoff.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(&sp.total_mk, sp.dmoff.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (!lmem && h_seed_off) sp.S = h_seed_off[n];
+    return RBG_OK;
+}
+
+// Records and markers are allocated (DevBuf::alloc(0) is a block of 8 bytes: no pointer of an empty pass is null) and, when the pass has records, filled.
+// Nothing is waited for: the caller's next step or copy-out follows on the stream.
+int seed_pass_fill(rbg_index *ix, SeedPass &sp, hipStream_t st) {
+    int rc;
+    if ((rc = sp.dseeds.alloc(sp.S * sizeof(rbg_marker_seed_t))) || (rc = sp.dmk.alloc(sp.total_mk * 8))) return rc;
+    if (sp.S == 0) return RBG_OK;
+    uint64_t *seeds = sp.dseeds.as<uint64_t>(), *mk = sp.dmk.as<uint64_t>();
+    const int e = sp.lmem ? launch_marker_lmems_fill(ix->dev, ix->cfg, sp.d_seqs, sp.d_off, sp.n, sp.S, sp.wsize, sp.max_range, sp.ftab_k, sp.dtmp.p, seeds, mk, st)
+                          : launch_marker_seeds_fill(ix->dev, ix->cfg, sp.d_seqs, sp.d_off, sp.n, sp.wsize, sp.max_range, sp.ftab_k, sp.dsoff.as<uint64_t>(), sp.dmoff.as<uint64_t>(),
+                                                     seeds, mk, st, sp.log_bytes ? sp.dlog.p : nullptr, sp.log_bytes);
+    return e ? RBG_ENODEV : RBG_OK;
+}
+
+// A batch too big for one pass goes in passes of whole reads.  The end b of the pass that starts at read a: at least one read, then whole reads
+// while they fit `chunk` (read bytes = lmem records per strand) and `max_reads`.
+uint64_t pass_end(const uint64_t *off, uint64_t N, uint64_t a, uint64_t chunk, uint64_t max_reads = ~uint64_t(0)) {
+    uint64_t b = a + 1;
+    while (b < N && off[b + 1] - off[a] <= chunk && b - a < max_reads) ++b;
+    return b;
+}
+
+// a pass's records index its own markers from 0: behind the mbase markers of the passes before, they move up
+template <typename Rec>
+void rebase_markers(Rec *recs, uint64_t count, uint64_t mbase) {
+    for (uint64_t r = 0; mbase && r < count; ++r) { recs[r].mk_begin += mbase; recs[r].mk_end += mbase; }
+}
+
+// The argument checks and the launch of rbg_marker_seeds_plan_dev; rbg_marker_seeds_plan_log_dev checks its log and then comes here with it
+int seeds_plan_dev(rbg_index *ix, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t wsize, uint64_t max_range, uint64_t ftab_k, uint64_t *d_seed_off,
+                   uint64_t *d_mk_off, void *d_tmp, size_t tmp_bytes, void *stream, void *d_log = nullptr, size_t log_bytes = 0) {
+    if (!queryable(ix)) return RBG_ENODEV;
+    if (!d_seed_off || !d_mk_off || (N && (!d_seqs || !d_off))) return RBG_EARG;
+    if (reinterpret_cast<uintptr_t>(d_seqs) & 15) return RBG_EARG;
+    if (tmp_bytes < scan_tmp_bytes(N) || (N && !d_tmp)) return RBG_EARG;
+    return launch_marker_seeds_plan(ix->dev, ix->cfg, d_seqs, d_off, N, wsize, max_range, ftab_k, d_seed_off, d_mk_off, d_tmp, tmp_bytes, stream, d_log, log_bytes) ? RBG_ENODEV : RBG_OK;
+}
+
+// the same for rbg_marker_seeds_fill_dev and rbg_marker_seeds_fill_log_dev
+int seeds_fill_dev(rbg_index *ix, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t wsize, uint64_t max_range, uint64_t ftab_k, const uint64_t *d_seed_off,
+                   const uint64_t *d_mk_off, rbg_marker_seed_t *d_seeds, uint64_t *d_mk, void *stream, void *d_log = nullptr, size_t log_bytes = 0) {
+    if (!queryable(ix)) return RBG_ENODEV;
+    if (N && (!d_seqs || !d_off || !d_seed_off || !d_mk_off || !d_seeds)) return RBG_EARG;
+    if (reinterpret_cast<uintptr_t>(d_seqs) & 15) return RBG_EARG;
+    return launch_marker_seeds_fill(ix->dev, ix->cfg, d_seqs, d_off, N, wsize, max_range, ftab_k, d_seed_off, d_mk_off, reinterpret_cast<uint64_t *>(d_seeds), d_mk, stream, d_log,
+                                    log_bytes) ? RBG_ENODEV : RBG_OK;
+}
+
+// what the two logged calls ask of their log: aligned, and room for two seeds per sequence
+bool seed_log_ok(const rbg_index *ix, void *d_log, size_t log_bytes, uint64_t N) { return !N || make_seed_log(d_log, log_bytes, N, ix->H().pos_bytes).base; }
+}  // namespace
+
 extern "C" {
 int rbg_markers_at(rbg_index *ix, const uint64_t *lo, const uint64_t *hi, uint64_t N, uint64_t *mk_off, uint64_t **mk) {
     return guarded([&]() -> int {
@@ -64,26 +162,13 @@ int rbg_find_range_w_markers(rbg_index *ix, const uint8_t *seqs, const uint64_t 
 int rbg_marker_seeds_plan_dev(rbg_index *ix, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t wsize,
                               uint64_t max_range, uint64_t ftab_k, uint64_t *d_seed_off, uint64_t *d_mk_off, void *d_tmp, size_t tmp_bytes,
                               void *stream) {
-    return guarded([&]() -> int {
-    if (!queryable(ix)) return RBG_ENODEV;
-    if (!d_seed_off || !d_mk_off || (N && (!d_seqs || !d_off))) return RBG_EARG;
-    if (reinterpret_cast<uintptr_t>(d_seqs) & 15) return RBG_EARG;
-    if (tmp_bytes < scan_tmp_bytes(N) || (N && !d_tmp)) return RBG_EARG;
-    return launch_marker_seeds_plan(ix->dev, ix->cfg, d_seqs, d_off, N, wsize, max_range, ftab_k, d_seed_off, d_mk_off, d_tmp, tmp_bytes,
-                                    stream) ? RBG_ENODEV : RBG_OK;
-    });
+    return guarded([&]() -> int { return seeds_plan_dev(ix, d_seqs, d_off, N, wsize, max_range, ftab_k, d_seed_off, d_mk_off, d_tmp, tmp_bytes, stream); });
 }
 
 int rbg_marker_seeds_fill_dev(rbg_index *ix, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, uint64_t wsize,
                               uint64_t max_range, uint64_t ftab_k, const uint64_t *d_seed_off, const uint64_t *d_mk_off,
                               rbg_marker_seed_t *d_seeds, uint64_t *d_mk, void *stream) {
-    return guarded([&]() -> int {
-    if (!queryable(ix)) return RBG_ENODEV;
-    if (N && (!d_seqs || !d_off || !d_seed_off || !d_mk_off || !d_seeds)) return RBG_EARG;
-    if (reinterpret_cast<uintptr_t>(d_seqs) & 15) return RBG_EARG;
-    return launch_marker_seeds_fill(ix->dev, ix->cfg, d_seqs, d_off, N, wsize, max_range, ftab_k, d_seed_off, d_mk_off,
-                                    reinterpret_cast<uint64_t *>(d_seeds), d_mk, stream) ? RBG_ENODEV : RBG_OK;
-    });
+    return guarded([&]() -> int { return seeds_fill_dev(ix, d_seqs, d_off, N, wsize, max_range, ftab_k, d_seed_off, d_mk_off, d_seeds, d_mk, stream); });
 }
 
 // The same two phases with a LOG between them (rbg_dev.h SeedLog): the plan leaves every sequence's seed records and the
@@ -101,12 +186,8 @@ int rbg_marker_seeds_plan_log_dev(rbg_index *ix, const uint8_t *d_seqs, const ui
                                   void *d_log, size_t log_bytes, void *stream) {
     return guarded([&]() -> int {
     if (!queryable(ix)) return RBG_ENODEV;
-    if (!d_seed_off || !d_mk_off || (N && (!d_seqs || !d_off))) return RBG_EARG;
-    if (reinterpret_cast<uintptr_t>(d_seqs) & 15) return RBG_EARG;
-    if (tmp_bytes < scan_tmp_bytes(N) || (N && !d_tmp)) return RBG_EARG;
-    if (N && !make_seed_log(d_log, log_bytes, N, ix->H().pos_bytes).base) return RBG_EARG;   // unaligned, or no room for two seeds per sequence
-    return launch_marker_seeds_plan(ix->dev, ix->cfg, d_seqs, d_off, N, wsize, max_range, ftab_k, d_seed_off, d_mk_off, d_tmp, tmp_bytes,
-                                    stream, d_log, log_bytes) ? RBG_ENODEV : RBG_OK;
+    if (!seed_log_ok(ix, d_log, log_bytes, N)) return RBG_EARG;
+    return seeds_plan_dev(ix, d_seqs, d_off, N, wsize, max_range, ftab_k, d_seed_off, d_mk_off, d_tmp, tmp_bytes, stream, d_log, log_bytes);
     });
 }
 
@@ -115,16 +196,35 @@ int rbg_marker_seeds_fill_log_dev(rbg_index *ix, const uint8_t *d_seqs, const ui
                                   rbg_marker_seed_t *d_seeds, uint64_t *d_mk, void *d_log, size_t log_bytes, void *stream) {
     return guarded([&]() -> int {
     if (!queryable(ix)) return RBG_ENODEV;
-    if (N && (!d_seqs || !d_off || !d_seed_off || !d_mk_off || !d_seeds)) return RBG_EARG;
-    if (reinterpret_cast<uintptr_t>(d_seqs) & 15 || reinterpret_cast<uintptr_t>(d_seeds) & 15) return RBG_EARG;
-    if (N && !make_seed_log(d_log, log_bytes, N, ix->H().pos_bytes).base) return RBG_EARG;
-    return launch_marker_seeds_fill(ix->dev, ix->cfg, d_seqs, d_off, N, wsize, max_range, ftab_k, d_seed_off, d_mk_off,
-                                    reinterpret_cast<uint64_t *>(d_seeds), d_mk, stream, d_log, log_bytes) ? RBG_ENODEV : RBG_OK;
+    // (d_seeds: only here, not in rbg_marker_seeds_fill_dev: the logged fill copies 16-byte records, the walking fill writes words)
+    if (reinterpret_cast<uintptr_t>(d_seeds) & 15 || !seed_log_ok(ix, d_log, log_bytes, N)) return RBG_EARG;
+    return seeds_fill_dev(ix, d_seqs, d_off, N, wsize, max_range, ftab_k, d_seed_off, d_mk_off, d_seeds, d_mk, stream, d_log, log_bytes);
     });
 }
 
 static int marker_seeds_host(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t wsize, uint64_t max_range,
-                             uint64_t ftab_k, uint64_t *seed_off, rbg_marker_seed_t **seeds, uint64_t **mk);
+                             uint64_t ftab_k, uint64_t *seed_off, rbg_marker_seed_t **seeds, uint64_t **mk) {
+    int rc;
+    *seeds = nullptr;
+    *mk = nullptr;
+    DeviceScope scope(ix->device);
+    if (scope.rc) return scope.rc;
+    hipStream_t st = hipStreamPerThread;
+    ReadBatch rb;
+    SeedPass sp;
+    if ((rc = rb.stage(seqs, off, N, st)) ||
+        (rc = seed_pass_plan(ix, sp, rb.seqs.as<uint8_t>(), rb.off.as<uint64_t>(), N, N ? off[N] : 0, wsize, max_range, ftab_k, false, st, seed_off)))
+        return rc;
+    auto *h_seeds = static_cast<rbg_marker_seed_t *>(alloc_result(sp.S * sizeof(rbg_marker_seed_t)));
+    auto *h_mk = static_cast<uint64_t *>(alloc_result(sp.total_mk * 8));
+    rc = h_seeds && h_mk ? seed_pass_fill(ix, sp, st) : RBG_ENOMEM;
+    if (!rc) rc = d2h_result(h_seeds, sp.dseeds.p, sp.S * sizeof(rbg_marker_seed_t), st);
+    if (!rc) rc = d2h_result(h_mk, sp.dmk.p, sp.total_mk * 8, st);
+    if (rc) { rbg_free_buffer(h_seeds); rbg_free_buffer(h_mk); return rc; }
+    *seeds = h_seeds;
+    *mk = h_mk;
+    return RBG_OK;
+}
 
 struct SeedsReq : CombineReq {
     const uint8_t *seq = nullptr;
@@ -204,52 +304,6 @@ int rbg_get_markers_greedy_seeding(rbg_index *ix, const uint8_t *seqs, const uin
     });
 }
 
-static int marker_seeds_host(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t wsize, uint64_t max_range,
-                             uint64_t ftab_k, uint64_t *seed_off, rbg_marker_seed_t **seeds, uint64_t **mk) {
-    {
-    int rc;
-    *seeds = nullptr;
-    *mk = nullptr;
-    DeviceScope scope(ix->device);
-    if (scope.rc) return scope.rc;
-    hipStream_t st = hipStreamPerThread;
-    ReadBatch rb;
-    if ((rc = rb.stage(seqs, off, N, st))) return rc;
-    DevBuf dsoff, dmoff, dtmp, dseeds, dmk, dlog;
-    const size_t tmp_bytes = scan_tmp_bytes(N);
-    if ((rc = dsoff.alloc((N + 1) * 8)) || (rc = dmoff.alloc((N + 1) * 8)) || (rc = dtmp.alloc(tmp_bytes))) return rc;
-    // the log between the two phases (one walk instead of two); without the memory for it the fill pass walks again
-    size_t log_bytes = seed_log_bytes(N, ix->H().pos_bytes, kSeedLogSeedsDefault);
-    if (dlog.alloc(log_bytes)) log_bytes = 0;
-    if (launch_marker_seeds_plan(ix->dev, ix->cfg, rb.seqs.as<uint8_t>(), rb.off.as<uint64_t>(), N, wsize, max_range, ftab_k,
-                                 dsoff.as<uint64_t>(), dmoff.as<uint64_t>(), dtmp.p, tmp_bytes, st, log_bytes ? dlog.p : nullptr, log_bytes))
-        return RBG_ENODEV;
-    uint64_t total_mk = 0;
-    HIP_TRY(hipMemcpyAsync(seed_off, dsoff.p, (N + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&total_mk, dmoff.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const uint64_t total_seeds = seed_off[N];
-    auto *h_seeds = static_cast<rbg_marker_seed_t *>(alloc_result(total_seeds * sizeof(rbg_marker_seed_t)));
-    auto *h_mk = static_cast<uint64_t *>(alloc_result(total_mk * 8));
-    if (!h_seeds || !h_mk) { rbg_free_buffer(h_seeds); rbg_free_buffer(h_mk); return RBG_ENOMEM; }
-    rc = RBG_OK;
-    if (total_seeds) {
-        if (!(rc = dseeds.alloc(total_seeds * sizeof(rbg_marker_seed_t))) && !(rc = dmk.alloc(total_mk ? total_mk * 8 : 8))) {
-            if (launch_marker_seeds_fill(ix->dev, ix->cfg, rb.seqs.as<uint8_t>(), rb.off.as<uint64_t>(), N, wsize, max_range, ftab_k,
-                                         dsoff.as<uint64_t>(), dmoff.as<uint64_t>(), dseeds.as<uint64_t>(), dmk.as<uint64_t>(), st,
-                                         log_bytes ? dlog.p : nullptr, log_bytes))
-                rc = RBG_ENODEV;
-            if (!rc) rc = d2h_result(h_seeds, dseeds.p, total_seeds * sizeof(rbg_marker_seed_t), st);
-            if (!rc && total_mk) rc = d2h_result(h_mk, dmk.p, total_mk * 8, st);
-        }
-    }
-    if (rc) { rbg_free_buffer(h_seeds); rbg_free_buffer(h_mk); return rc; }
-    *seeds = h_seeds;
-    *mk = h_mk;
-    return RBG_OK;
-    }
-}
-
 // ---- lmem marker seeds: get_markers_lmems, rowbowt.hpp:341-404 -------------------------------------------------
 // One record per (sequence, end position): record k of sequence i at off[i] - off[0] + k.  The plan walks every end position
 // once to count its markers, scans those counts in d_tmp and writes the per-sequence scan; the fill walks again and writes.
@@ -309,33 +363,22 @@ int rbg_get_markers_lmems(rbg_index *ix, const uint8_t *seqs, const uint64_t *of
     std::vector<uint64_t> h_mk;
     const uint64_t chunk = lmem_chunk_records();
     for (uint64_t a = 0; a < N && !rc;) {
-        uint64_t b = a + 1;   // sequences [a, b): at least one, and as many whole ones as fit the chunk
-        while (b < N && off[b + 1] - off[a] <= chunk) ++b;
+        const uint64_t b = pass_end(off, N, a, chunk);   // (a sequence longer than the chunk gets a pass of its own)
         const uint64_t n = b - a, recs = off[b] - off[a];
         std::vector<uint64_t> roff(n + 1);
         for (uint64_t i = 0; i <= n; ++i) roff[i] = off[a + i] - off[a];
         ReadBatch rb;
-        DevBuf dmoff, dtmp, dseeds, dmk;
-        const size_t tmp_bytes = marker_lmems_tmp_bytes(recs);
-        if ((rc = rb.stage(seqs + off[a], roff.data(), n, st)) || (rc = dmoff.alloc((n + 1) * 8)) || (rc = dtmp.alloc(tmp_bytes))) break;
-        if (launch_marker_lmems_plan(ix->dev, ix->cfg, rb.seqs.as<uint8_t>(), rb.off.as<uint64_t>(), n, recs, wsize, max_range, ftab_k,
-                                     dmoff.as<uint64_t>(), dtmp.p, tmp_bytes, st)) { rc = RBG_ENODEV; break; }
-        uint64_t nmk = 0;
-        if (hipMemcpyAsync(&nmk, dmoff.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-            rc = RBG_ENODEV;
+        SeedPass sp;
+        if ((rc = rb.stage(seqs + off[a], roff.data(), n, st)) ||
+            (rc = seed_pass_plan(ix, sp, rb.seqs.as<uint8_t>(), rb.off.as<uint64_t>(), n, recs, wsize, max_range, ftab_k, true, st)) || (rc = seed_pass_fill(ix, sp, st)))
             break;
-        }
-        if ((rc = dseeds.alloc(recs * sizeof(rbg_marker_seed_t))) || (rc = dmk.alloc(nmk * 8))) break;
-        if (launch_marker_lmems_fill(ix->dev, ix->cfg, rb.seqs.as<uint8_t>(), rb.off.as<uint64_t>(), n, recs, wsize, max_range, ftab_k, dtmp.p,
-                                     dseeds.as<uint64_t>(), dmk.as<uint64_t>(), st)) { rc = RBG_ENODEV; break; }
         rbg_marker_seed_t *dst = h_seeds + off[a];
-        if ((rc = d2h_result(dst, dseeds.p, recs * sizeof(rbg_marker_seed_t), st))) break;
+        if ((rc = d2h_result(dst, sp.dseeds.p, recs * sizeof(rbg_marker_seed_t), st))) break;
         const uint64_t mbase = h_mk.size();
-        h_mk.resize(mbase + nmk);
-        if (nmk && (rc = d2h_result(h_mk.data() + mbase, dmk.p, nmk * 8, st))) break;
+        h_mk.resize(mbase + sp.total_mk);
+        if ((rc = d2h_result(h_mk.data() + mbase, sp.dmk.p, sp.total_mk * 8, st))) break;
         if (hipStreamSynchronize(st) != hipSuccess) { rc = RBG_ENODEV; break; }
-        if (mbase)
-            for (uint64_t r = 0; r < recs; ++r) { dst[r].mk_begin += mbase; dst[r].mk_end += mbase; }
+        rebase_markers(dst, recs, mbase);
         a = b;
     }
     if (!rc) {

@@ -35,12 +35,13 @@
 // anonymous namespace, and the kernels' launchers are declared once in rbg_dev.h):
 #include "capi/core.ipp"          // the handle, options, pools, arena
 #include "capi/upload_runs.ipp"   // run-indexed layout: tables on the device, composition of the k-mer depths
+#include "capi/query.ipp"         // what every query entry point shares: staging of a host batch, the result pool, the big copies, ragged_finish
 #include "capi/load.ipp"          // upload() and its budget / layout rules; load / convert / build entry points; info
 #include "capi/device_api.ipp"    // *_dev entry points
 #include "capi/hostpath.ipp"      // host-pointer entry points, micro-batching
 #include "capi/text.ipp"          // rbg_align_text
-#include "capi/seeds.ipp"         // markers, marker seeds, greedy seeding
+#include "capi/seeds.ipp"         // markers, marker seeds (the shared seed pass: greedy or lmem, plan and fill), greedy seeding
 #include "capi/tally.ipp"         // the marker tally: per-marker counts of the report's lines, accumulated on the device (rbg_markers_tally: report.ipp)
-#include "capi/report.ipp"        // rb_markers' report on the device: strands, canonical records, selection, text
+#include "capi/report.ipp"        // rb_markers' report on the device, pass by pass: strands, the seed pass, canonical records, selection; records, text or tally
 #include "capi/loc_markers.ipp"   // the text-position marker table, markers at located positions (rb_locs' path)
 #include "capi/replicas.ipp"      // replicas in one process, counters, RCCL

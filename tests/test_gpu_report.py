@@ -9,6 +9,7 @@ import golden_values as G
 import orc
 import rb_markers_model as RM
 import rowbowt_amd as ra
+import tally_model as TM
 from lmem_model import LmemAsGreedy
 from rowbowt_amd import capi
 from gpu_common import _run_rb_markers
@@ -289,6 +290,110 @@ def test_report_edges(small, toy_reads, monkeypatch):
     monkeypatch.setenv("RBG_REPORT_CHUNK", "300")
     dozen = toy_reads[:4] + toy_reads[40:46] + toy_reads[-2:]
     _both(rb, dozen, RM.expected_stdout(LmemAsGreedy(o), dozen, wsize=8, ftab_k=6), wsize=8, ftab_k=6, lmem=True)
+
+
+# ---- the shared seed pass at its pass boundaries --------------------------------------------------------------------------------------------
+
+def _boundary_reads(data_dir):
+    """Cuts of small.fa of 7, 16, 33, 50 and 8 bytes in this order: with one read per pass the later passes start at read offsets 7, 23, 56 and 106,
+    off the 16-byte grid by 7, 7, 8 and 10; the fifth lets a later pass of two reads (3-4) start off the grid too.  The first cut is shorter than the wsize of 8 the test uses, so no window of it reaches a marker lookup
+    (no marker in its pass), and shorter than min_seed_len = 12, so the heuristic settings print nothing for it; the 33- and 50-byte cuts lie over
+    variant sites (chosen with the model on the CPU; the test asserts both from the model's output).  The last cut goes in reverse-complemented."""
+    text = open(os.path.join(data_dir, "small.fa"), "rb").read().split(b"\n", 1)[1].replace(b"\n", b"")
+    cuts = [text[p:p + m] for p, m in ((40, 7), (1840, 16), (270, 33), (2205, 50), (905, 8))]
+    cuts[3] = cuts[3].translate(RM.COMP)[::-1]
+    return [(f"b{i}".encode(), c) for i, c in enumerate(cuts)]
+
+
+def _strands(recs):
+    out = []
+    for _, raw in recs:
+        fwd = raw.translate(RM.NT)
+        out += [fwd, fwd.translate(RM.COMP)[::-1]]
+    return out
+
+
+@pytest.fixture(scope="module")
+def uncombined_singles(data_dir):
+    """rbg_get_markers_greedy_seeding with N == 1 for every strand of _boundary_reads in a process of its own under RBG_HOST_COMBINE=0 (the switch is
+    read once per process): [[records as lists of 6], markers] per strand"""
+    import json
+    import subprocess
+    import sys
+    code = ("import json, os, sys\nsys.path[:0] = [%r, %r]\nimport rowbowt_amd as ra\nimport test_gpu_report as T\n"
+            "rb = ra.load_rowbowt(os.path.join(%r, 'small.fa'), ra.LoadRbwtFlag.SA | ra.LoadRbwtFlag.MA, device=0)\nout = []\n"
+            "for s in T._strands(T._boundary_reads(%r)):\n    _, seeds, mk = rb.get_markers_greedy_seeding(*ra.pack_reads([s]), 8, 1000, 0)\n"
+            "    out.append([seeds.tolist(), mk.tolist()])\nrb.close()\nprint('SINGLES', json.dumps(out))\n") % (
+                os.path.dirname(os.path.abspath(__file__)), os.path.dirname(os.path.dirname(os.path.abspath(__file__))), data_dir, data_dir)
+    p = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", code], capture_output=True, timeout=120,
+                       env=dict(os.environ, RBG_HOST_COMBINE="0"))
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    return json.loads([line for line in p.stdout.decode().splitlines() if line.startswith("SINGLES ")][0][8:])
+
+
+@pytest.mark.parametrize("lmem", [False, True], ids=["greedy", "lmem-ftab6"])
+@pytest.mark.parametrize("kw", [dict(wsize=8), dict(wsize=8, heuristic=True, min_seed_len=12)], ids=["default", "heuristic-y12"])
+def test_report_pass_boundaries(small, data_dir, uncombined_singles, monkeypatch, lmem, kw):
+    """One device pass serves rbg_get_markers_greedy_seeding, rbg_get_markers_lmems and the three report calls.  Records, text and tally must not
+    depend on how a batch is cut into passes: one pass, one read per pass (passes that start off the 16-byte grid; a first pass without a marker
+    and, in the heuristic settings, without a printed record, before passes with both: mbase == 0 then mbase > 0, a tally pass that adds nothing)
+    and two reads per pass as far as the lengths allow (no chunk of bytes cuts 7, 16, 33, 50 into 2 + 2: 55 bytes give reads 0-1, 2, 3, 4, and 60
+    bytes give 0-2, 3-4, a later pass of two reads that starts off the grid).  All equal the model fed with the host
+    call's own seeds of the 2N strands; those equal the oracle's, the host call in passes of one sequence, and its N == 1 form with the one-read
+    combiner on and off."""
+    rb, o = small
+    recs = _boundary_reads(data_dir)
+    assert [len(s) for _, s in recs] == [7, 16, 33, 50, 8]
+    ftab_k = 6 if lmem else 0
+    strands = _strands(recs)
+    pk = ra.pack_reads(strands)
+    host = rb.get_markers_lmems if lmem else rb.get_markers_greedy_seeding
+    h_off, h_seeds, h_mk = host(*pk, 8, 1000, ftab_k)
+
+    def records(i, off=h_off, seeds=h_seeds, mk=h_mk):
+        return [tuple(int(v) for v in s[:4]) + (mk[int(s[4]):int(s[5])].tolist(),) for s in seeds[int(off[i]):int(off[i + 1])]]
+
+    table = {s: records(i) for i, s in enumerate(strands)}
+    ref = LmemAsGreedy(o) if lmem else o
+    for s in strands:   # the host call against the oracle, record for record
+        assert table[s] == [tuple(r[:4]) + (list(r[4]),) for r in ref.markers_greedy_seeding(s, 8, 1000, ftab_k)], s
+    if lmem:
+        assert (h_off == pk[1]).all()
+        monkeypatch.setenv("RBG_LMEM_CHUNK", "1")   # a pass per sequence: every later pass rebases its records' marker offsets
+        c_off, c_seeds, c_mk = host(*pk, 8, 1000, ftab_k)
+        monkeypatch.delenv("RBG_LMEM_CHUNK")
+        assert (c_off == h_off).all() and (c_seeds == h_seeds).all() and (c_mk == h_mk).all()
+    else:
+        for i, s in enumerate(strands):   # N == 1: through the combiner here, around it in the child process
+            one = host(*ra.pack_reads([s]), 8, 1000, 0)
+            assert one[0].tolist() == [0, len(table[s])] and records(0, *one) == table[s], i
+            u_seeds, u_mk = uncombined_singles[i]
+            assert [tuple(r[:4]) + (u_mk[r[4]:r[5]],) for r in u_seeds] == table[s], i
+    want = RM.expected_stdout(_FakeSeeds(table), recs, ftab_k=ftab_k, **kw)
+    lines = lambda name: [x for x in want.splitlines() if x.startswith(name + " ")]
+    assert not any(m for rec in table[strands[0]] + table[strands[1]] for m in rec[4])       # the first read's pass has no marker at all ...
+    assert bool(lines("b0")) == (not kw.get("heuristic"))                                     # ... and under min_seed_len no printed record
+    assert any(not x.endswith(" .") for x in lines("b2")) and any(not x.endswith(" .") for x in lines("b3"))
+    want_tally = TM.tally_from_stdout(want)[1]
+    assert want_tally
+    seqs, off = ra.pack_reads([s for _, s in recs])
+    names = [n for n, _ in recs]
+    params = capi.report_params(lmem=lmem, ftab_k=ftab_k, **kw)
+    coins = _coins(len(recs)) if kw.get("heuristic") else None
+    first = None
+    for chunk in (None, "1", "55", "60"):
+        if chunk:
+            monkeypatch.setenv("RBG_REPORT_CHUNK", chunk)
+        text = rb.markers_report_text(seqs, off, names, params, coins).decode()
+        seed_off, seeds, mk = rb.markers_report(seqs, off, params, coins)
+        t = capi.Tally(rb, 0)
+        rb.markers_tally(seqs, off, params, coins, t)
+        tally = [(int(x["marker"]), int(x["n_fwd"]), int(x["n_rev"]), int(x["len_sum"])) for x in t.export()]
+        t.close()
+        assert text == want and _render(recs, seed_off, seeds, mk) == want and tally == want_tally, chunk
+        got = (seed_off.tolist(), seeds.tobytes(), mk.tolist())
+        first = first or got
+        assert got == first and (not len(seeds) or int(seeds["mk_end"][-1]) == len(mk)), chunk
 
 
 def test_report_dense_markers():
