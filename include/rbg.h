@@ -135,7 +135,8 @@ int rbg_set_text_markers(rbg_index *, const uint64_t *run_start, const uint64_t 
  * serialise them the same way (three sd_vectors -- run starts, run ends, first-value flags -- then the int_vector of values); no file written
  * by the reference's build_midx was available to check against.  RBG_EIO / RBG_EFORMAT as for the other index files. */
 int rbg_load_text_markers(rbg_index *, const char *path);
-/* DocList contents, doclist.hpp:57-73: names '\0'-joined, starts[ndocs]. */
+/* DocList contents, doclist.hpp:57-73: names '\0'-joined, starts[ndocs].  A second call replaces the table (and frees the device copy of the first one's
+ * sorted starts): rbg_set_docs must not overlap queries on the handle. */
 int rbg_set_docs(rbg_index *, const char *names_joined, const uint64_t *starts, uint64_t ndocs);
 
 void rbg_free(rbg_index *);
@@ -649,6 +650,12 @@ int rbg_replicate_many(rbg_index *primary, const int *devices, int G, rbg_index 
  * peer copies"; the reference has no counterpart): out = {milliseconds its copies took on its own stream (HIP events), bytes
  * copied, peer access to the primary's device (1 = direct, 0 = staged through the host by the runtime, -1 = same device)}. */
 int rbg_replicate_stats(const rbg_index *replica, double out[3]);
+/* What the check of the re-pointed copy found when this replica was made (no device work; RBG_EARG on a primary): a source word that points into the
+ * primary's i-th allocation must be the replica's i-th allocation plus the same offset on the replica, every other word of DevIndex and of the DevSym records
+ * must be bit-identical.  out = {words of DevIndex recognised as such pointers, words of DevIndex that break the rule, the same two over every record of the
+ * pointer tables}.  A violation also went to stderr with its byte offset and kind; queries answer correctly either way (from the primary's memory over the
+ * peer link, or by the path that does without the array), which is why this is a call and not an error of rbg_replicate. */
+int rbg_replica_pointer_check(const rbg_index *replica, uint64_t out[4]);
 /* contiguous block [begin, end) of `rank` out of `world` (sizes differ by at most one; concatenating the ranks'
  * outputs restores the input order): read i of N goes to rank i * world / N */
 int rbg_shard_bounds(uint64_t n_items, int rank, int world, uint64_t *begin, uint64_t *end);

@@ -167,6 +167,7 @@ _PROTOS = [
     ("rbg_replicate", C.c_int, [VP, C.c_int, C.POINTER(VP)]),
     ("rbg_replicate_many", C.c_int, [VP, C.POINTER(C.c_int), C.c_int, C.POINTER(VP)]),
     ("rbg_replicate_stats", C.c_int, [VP, C.POINTER(C.c_double)]),
+    ("rbg_replica_pointer_check", C.c_int, [VP, VP]),
     ("rbg_comm_cache_clear", C.c_int, []),
     ("rbg_shard_bounds", C.c_int, [U64, C.c_int, C.c_int, C.POINTER(U64), C.POINTER(U64)]),
     ("rbg_find_range_sharded", C.c_int, [VP, C.c_int, VP, VP, U64, VP, VP, VP]),
@@ -743,6 +744,13 @@ class RowBowt:
         ms, nbytes, peer = float(out[0]), int(out[1]), int(out[2])
         return {"copy_ms": ms, "bytes": nbytes, "GBps": (nbytes / (ms * 1e-3) / 1e9) if ms > 0 else None,
                 "peer_access": {1: "direct", 0: "staged through the host", -1: "same device"}[peer]}
+
+    def replica_pointer_check(self):
+        """what the check of the re-pointed copy found when this replica was made (rbg_replica_pointer_check): pointer words recognised and words that
+        break the invariant, in DevIndex and in the records of the pointer tables"""
+        out = np.zeros(4, np.uint64)
+        _check(self.L.rbg_replica_pointer_check(self.h, _p(out)), "rbg_replica_pointer_check")
+        return dict(zip(("dev_pointers", "dev_violations", "table_pointers", "table_violations"), (int(v) for v in out)))
 
     def counters_reset(self):
         _check(self.L.rbg_counters_reset(self.h), "rbg_counters_reset")

@@ -4,6 +4,7 @@ using namespace rbg;
 static_assert(kMaxRunDepth == kMaxKmerDepth && kLdsRunDepth == kMaxSlotKmerDepth, "rbg_dev.h and rbg_host.hpp name the same depths");
 
 #include "../rbg_hostpath.hpp"
+#include "../rbg_reloc_check.hpp"
 
 struct DevAlloc {
     void *p;
@@ -34,6 +35,7 @@ struct rbg_index {
     bool runs_layout = false;
     double replicate_ms = 0.0;     // replica handle: duration of its peer copies on its own stream (HIP events; rbg_replicate_stats)
     int replicate_peer = -1;       // replica handle: 1 = peer access to the source's device was enabled, 0 = the runtime stages the copy, -1 = same device / primary
+    uint64_t reloc_check[4] = {};  // replica handle: what rbg_reloc_check.hpp found when the copy was re-pointed (rbg_replica_pointer_check)
     uint64_t plan_free = 0, plan_budget = 0;   // free HBM and replica budget as options_for() saw them BEFORE anything of this load was on the device (0: not taken)
     bool budget_raised = false;                // RBG_LAYOUT_AUTO raised the default budget from a quarter to three quarters of the free HBM (an index too large for the quarter)
     bool auto_runs = false;        // RBG_LAYOUT_AUTO chose the run-indexed layout because the slot tables of every requested symbol per step exceed the budget

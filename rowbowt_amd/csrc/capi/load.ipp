@@ -966,6 +966,14 @@ namespace {
 // the document starts on the device for K3's locus order (rbg_dev.h order_docs).  RBG_LOCATE_ORDER=abs keeps the order by absolute position.
 int upload_order_docs(rbg_index *ix) {
     DevIndex &d = ix->dev;
+    if (d.order_docs && ix->device != RBG_DEVICE_NONE && !ix->primary) {
+        // a table attached before: its array goes back (it would be copied to every replica and counted in hbm_bytes), whether or not the new table gets
+        // one (the order may have become ineligible) -- rbg_set_docs must not overlap queries on the handle (include/rbg.h)
+        DeviceScope scope(ix->device);
+        if (scope.rc) return scope.rc;
+        HIP_TRY(hipDeviceSynchronize());
+        free_tracked(ix, const_cast<uint64_t *>(d.order_docs));
+    }
     d.order_docs = nullptr;
     d.order_ndocs = d.order_dbits = d.order_lowbits = d.order_obits = 0;
     if (ix->device == RBG_DEVICE_NONE || ix->primary) return RBG_OK;
@@ -986,9 +994,13 @@ int upload_order_docs(rbg_index *ix) {
     if (obits + dbits > 60) return RBG_OK;
     DeviceScope scope(ix->device);
     if (scope.rc) return scope.rc;
-    const void *p = nullptr;
-    int rc = dev_upload(ix, dl.sorted.data(), nd * 8, &p);
-    if (rc) return rc;
+    // (an allocation of its own, never a piece of the arena: free_tracked must be able to give it back when another table replaces this one)
+    void *p = nullptr;
+    const size_t alloc = arena_round(nd * 8);
+    HIP_TRY(hipMalloc(&p, alloc));
+    ix->allocs.push_back({p, alloc});
+    ix->hbm_bytes += alloc;
+    if (const int rc = h2d_big(p, dl.sorted.data(), nd * 8)) { free_tracked(ix, p); return rc; }
     d.order_docs = static_cast<const uint64_t *>(p);
     d.order_ndocs = static_cast<uint32_t>(nd);
     d.order_dbits = dbits;

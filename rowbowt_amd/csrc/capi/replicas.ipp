@@ -86,11 +86,26 @@ int replicate_finish(rbg_index *src, ReplicaJob &job) {
     }
     float ms = 0.f;
     if (job.ev0 && job.ev1 && hipEventElapsedTime(&ms, job.ev0, job.ev1) == hipSuccess) r->replicate_ms = ms;
+    // the invariant of a re-pointed copy (rbg_reloc_check.hpp), checked on every record as it is finished: a line on stderr per word that breaks it, the
+    // counts kept for rbg_replica_pointer_check; the replica is made all the same
+    std::vector<RelocRange> rfrom, rto;
+    for (const DevAlloc &a : reloc.from) rfrom.push_back({a.p, a.bytes});
+    for (const DevAlloc &a : reloc.to) rto.push_back({a.p, a.bytes});
+    std::vector<RelocViolation> bad;
+    auto report = [&](const char *what, size_t rec, size_t first) {
+        for (size_t v = first; v < bad.size(); ++v)
+            std::fprintf(stderr, "rbg: replica on device %d: %s record %zu, byte offset %zu: %s\n", r->device, what, rec, bad[v].offset, reloc_fault_name(bad[v].fault));
+    };
+    size_t ti = 0;
     for (const PtrTable &t : src->ptr_tables) {
-        std::vector<char> buf(t.count * t.stride);
+        std::vector<char> buf(t.count * t.stride), sbuf(t.count * t.stride);
         void *dst = const_cast<void *>(reloc(t.d_ptr));
         if (!dst) return RBG_ENODEV;
         if (hipMemcpy(buf.data(), dst, buf.size(), hipMemcpyDeviceToHost) != hipSuccess) return RBG_ENODEV;
+        {   // the source's records, read the same way: both images are byte copies of the same device memory, padding included
+            DeviceScope s0(src->device);
+            if (s0.rc || hipMemcpy(sbuf.data(), t.d_ptr, sbuf.size(), hipMemcpyDeviceToHost) != hipSuccess) return RBG_ENODEV;
+        }
         for (size_t i = 0; i < t.count; ++i)
             for (size_t o : t.ptr_offsets) {
                 const void *old;
@@ -100,8 +115,17 @@ int replicate_finish(rbg_index *src, ReplicaJob &job) {
             }
         if (hipMemcpy(dst, buf.data(), buf.size(), hipMemcpyHostToDevice) != hipSuccess) return RBG_ENODEV;
         r->ptr_tables.push_back({dst, t.count, t.stride, t.ptr_offsets});
+        const std::string what = "pointer table " + std::to_string(ti++) + ",";
+        for (size_t i = 0; i < t.count; ++i) {   // EVERY word of the record, not only ptr_offsets: a pointer member nobody registered shows as well
+            const size_t first = bad.size();
+            r->reloc_check[2] += reloc_check(sbuf.data() + i * t.stride, buf.data() + i * t.stride, t.stride, rfrom.data(), rto.data(), rfrom.size(), bad);
+            report(what.c_str(), i, first);
+        }
     }
-    DevIndex d = src->dev;
+    r->reloc_check[3] = bad.size();
+    // (a byte copy, and r->dev a byte copy of it below: the padding of DevIndex is the source's in both, whatever the compiler makes of a struct assignment)
+    DevIndex d;
+    std::memcpy(&d, &src->dev, sizeof(d));
     reloc.fix(d.syms); reloc.fix(d.phi_ent); reloc.fix(d.phi_slots); reloc.fix(d.phi_ord);
     reloc.fix(d.mk_start); reloc.fix(d.mk_end); reloc.fix(d.mk_off); reloc.fix(d.mk_vals); reloc.fix(d.mk_bucket); reloc.fix(d.mk_rec);
     reloc.fix(d.counters); reloc.fix(d.lut); reloc.fix(d.pairs); reloc.fix(d.triples); reloc.fix(d.quads); reloc.fix(d.quints);
@@ -113,7 +137,13 @@ int replicate_finish(rbg_index *src, ReplicaJob &job) {
     for (int t = 0; t < kMaxRunDepth; ++t) reloc.fix(d.run_samp[t]);
     reloc.fix(d.run_tabs2); reloc.fix(d.run_hot); reloc.fix(d.phi_super);
     for (int t = 0; t < kMaxRunDepth; ++t) { reloc.fix(d.run_ent2[t]); reloc.fix(d.run_dir2[t]); reloc.fix(d.run_rec2[t]); }
-    r->dev = d;
+    std::memcpy(&r->dev, &d, sizeof(d));
+    {
+        const size_t first = bad.size();
+        r->reloc_check[0] = reloc_check(&src->dev, &r->dev, sizeof(DevIndex), rfrom.data(), rto.data(), rfrom.size(), bad);
+        r->reloc_check[1] = bad.size() - first;
+        report("DevIndex,", 0, first);
+    }
     if (hipMemset(d.counters, 0, 4 * sizeof(uint64_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return RBG_ENODEV;
     return RBG_OK;
 }
@@ -168,6 +198,15 @@ int rbg_replicate_stats(const rbg_index *replica, double out[3]) {
     out[0] = replica->replicate_ms;
     out[1] = static_cast<double>(replica->hbm_bytes);
     out[2] = replica->replicate_peer;
+    return RBG_OK;
+}
+
+// What rbg_reloc_check.hpp found when this replica was re-pointed (nothing runs here): out = {words of DevIndex recognised as pointers into the source's
+// allocations, words of DevIndex that break the invariant, the same two over every record of the pointer tables}.
+int rbg_replica_pointer_check(const rbg_index *replica, uint64_t out[4]) {
+    if (!replica || !out) return RBG_EARG;
+    if (!replica->primary) return RBG_EARG;   // a primary was built, not copied
+    for (int t = 0; t < 4; ++t) out[t] = replica->reloc_check[t];
     return RBG_OK;
 }
 

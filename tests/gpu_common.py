@@ -100,8 +100,9 @@ def _with_layout(layout, build):
         ra.set_default_option(capi.OPT_RANK_LAYOUT, capi.LAYOUT_AUTO)
 
 
-def _run_indexed_checks(S, rb):
-    """every query of the run-indexed layout against the oracle (rb is closed at the end)"""
+def _run_indexed_checks(S, rb, markers_attached=False):
+    """every query of the run-indexed layout against the oracle (rb is closed at the end); markers_attached: rb already holds S.markers(wsize=10) -- a
+    replica, which refuses a table of its own"""
     o = orc.Oracle.from_runs(S.heads, S.lens, S.ssa, S.esa)
     reads = S.sample_reads(3000, 60, seed=5, sub_rate=0.15, ragged=True)
     reads += [b"", b"A", b"N", b"ACGTN", b"NACGT", b"ACNGT", b"AC", b"ACG", b"acgt", bytes([1]), bytes([255]) * 3, bytes([0]),
@@ -131,7 +132,8 @@ def _run_indexed_checks(S, rb):
     for j in range(500):
         assert (int(nlo[j]), int(nhi[j])) == o.LF(int(rows[j]), int(his[j]), int(cs[j]))
     ms, me, mo, mv = S.markers(wsize=10)
-    rb.set_markers(ms, me, mo, mv)
+    if not markers_attached:
+        rb.set_markers(ms, me, mo, mv)
     o.set_markers(ms, me, mo, mv)
     nseed, nmk = _check_marker_seeds(rb, o, reads[:300] + reads[-19:], 10, 1000)
     assert nseed > 330 and nmk > 20

@@ -464,8 +464,10 @@ def test_host_pointer_pipeline(small, packed, request):
 @pytest.mark.parametrize("layout", [capi.LAYOUT_AUTO, capi.LAYOUT_RUNS])
 def test_replicas_sharded_queries_and_rccl_counters(synth, layout):
     """More than one replica in one process (include/rbg.h "several GPUs"): rbg_replicate copies the device index
-    peer to peer and re-points it -- onto the SAME device here when the box has one GPU, which exercises every
-    relocation -- rbg_find_range_sharded splits a batch by rbg_shard_bounds, and the counters are reduced by
+    peer to peer and re-points it -- onto the SAME device here when the box has one GPU.  Right answers from such a replica do
+    NOT show that every pointer was re-pointed: one that was forgotten reads the primary's identical bytes.  What does is
+    rbg_replica_pointer_check (asserted clean here on every replica; tests/test_gpu_replicas.py takes it through every index form
+    and query family).  rbg_find_range_sharded splits a batch by rbg_shard_bounds, and the counters are reduced by
     RCCL (a one-rank clique on a single GPU; one rank per device when there are more)."""
     import torch
     S = synth
@@ -477,6 +479,10 @@ def test_replicas_sharded_queries_and_rccl_counters(synth, layout):
     ndev = torch.cuda.device_count()
     rep = rb.replicate(1 if ndev > 1 else 0)
     assert rep.info().hbm_bytes == rb.info().hbm_bytes and rep.info().rank_layout == rb.info().rank_layout
+    chk = rep.replica_pointer_check()
+    assert chk["dev_pointers"] > 10 and chk["dev_violations"] == 0 and chk["table_violations"] == 0, chk   # (syms, counters, lut, six marker arrays, phi: more than ten)
+    with pytest.raises(ra.RbgError):
+        rb.replica_pointer_check()             # a primary was built, not copied
     with pytest.raises(ra.RbgError):
         rep.replicate(0)                       # replicas are made from the primary
     with pytest.raises(ra.RbgError):
@@ -529,6 +535,7 @@ def test_replicas_sharded_queries_and_rccl_counters(synth, layout):
     # several replicas at once (rbg_replicate_many: the peer copies of all targets are in flight together)
     many = rb.replicate_many([1 if ndev > 1 else 0, 0, (2 if ndev > 2 else 0)])
     assert len(many) == 3 and all(r.info().hbm_bytes == rb.info().hbm_bytes for r in many)
+    assert all(r.replica_pointer_check() == chk for r in many)
     for r in many:
         lo4, hi4, k4 = r.find_range_w_toehold(seqs, off)
         assert (lo4 == wlo).all() and (hi4 == whi).all() and (k4 == wk).all()
