@@ -430,8 +430,8 @@ int rbg_markers_report_text(rbg_index *, const uint8_t *seqs, const uint64_t *of
 /* ---- the marker tally: per marker, how many of rb_markers' lines carried it ---------------------------------------------------------
  * For a caller who wants the genotyping evidence and not the lines.  Take the lines rbg_markers_report_text makes for a batch and an
  * rbg_report_params_t; for every line and every marker m on it: n_fwd[m] += 1 if the line's strand is '+', else n_rev[m] += 1, and
- * len_sum[m] += the line's query_len (wrapping).  A line with " ." adds nothing; a marker printed on two lines of one read counts twice (no
- * per-read deduplication).  A marker is the full 64-bit value: every value is a legal key, 0 and 2^64 - 1 included.  The sums are of integers,
+ * len_sum[m] += the line's query_len (wrapping).  A line with " ." adds nothing; a marker printed on two lines of one read counts twice (LINE
+ * MODE, the default; PER-READ MODE below counts it once).  A marker is the full 64-bit value: every value is a legal key, 0 and 2^64 - 1 included.  The sums are of integers,
  * so the result does not depend on read order, on how the reads are split into calls and passes, or on the order in which the device's atomic
  * additions arrive: it is bit-reproducible.
  *
@@ -453,7 +453,29 @@ int rbg_markers_report_text(rbg_index *, const uint8_t *seqs, const uint64_t *of
  * rbg_tally_export: the entries with n_fwd + n_rev > 0, sorted by (sequence, position, allele); through rbg_free_buffer.
  * rbg_tally_info: {entries, capacity, grows since create / reset, records added, elements added, elements dropped}; dropped stays 0 -- a probe
  * sequence is bounded by the capacity and the reserve rule keeps the table half empty, the counter is the backstop's.
- * RBG_TALLY_COMBINE=0 (environment) turns off the combining of equal keys within a wave, for A/Bs: same result. */
+ * RBG_TALLY_COMBINE=0 (environment) turns off the combining of equal keys within a wave, for A/Bs: same result.
+ *
+ * PER-READ MODE (tally_flags = RBG_TALLY_PER_READ): the unit of evidence is the read.  Take one read and the lines printed for it, in print order.
+ * For each DISTINCT marker m on them, the line carrying m with the greatest query_len -- the earliest such line on a tie -- adds: +1 to n_fwd[m] or
+ * n_rev[m] by that line's strand, + its query_len to len_sum[m].  The read's other lines add nothing for m.
+ * RBG_TALLY_DROP_SITE_CONFLICTS (only together with RBG_TALLY_PER_READ, RBG_EARG otherwise): a site is the marker without its allele -- bits 0-59,
+ * sequence and position; the allele is bits 60-63.  A read whose lines carry two or more different alleles of one site, on one line or over several,
+ * adds nothing for any marker of that site.  Every 64-bit value stays a legal marker: 2^64 - 1 is allele 15 of site (0xFFF, 2^48 - 1).
+ * The additions are still sums of integers, so the export does not depend on read order, on the split into calls and passes (a pass holds whole
+ * reads) or on the order of the atomics.  Line-mode and per-read adds may go into one tally; what such a mixture means is the caller's business.
+ * rbg_markers_tally_reads: rbg_markers_tally with a flag word; 0 is rbg_markers_tally exactly, unknown bits give RBG_EARG.
+ * rbg_tally_add_reads_dev: rbg_tally_add_dev plus the records' per-read offsets d_rep_off[N + 1] (rbg_report_select_dev's d_rep_off: read i printed
+ * records [d_rep_off[i], d_rep_off[i + 1]), d_rep_off[N] = R), its checks and its reserve rule; R = 0 or N = 0 adds nothing.  tally_flags = 0 is
+ * line mode.  d_tmp: rbg_tally_add_reads_tmp_bytes(N, R), 8-byte aligned.  PRECONDITION: every record's markers [mk_begin, mk_end) are ascending in
+ * rotl64(marker, 4) and unique, as rbg_marker_seeds_canon_dev leaves them.  Markers that are not give an unspecified table, never an access outside
+ * [mk_begin, mk_end).
+ * rbg_tally_read_info: {reads seen by per-read adds, marker elements (of printed records) seen by them, elements that lost to another line of their
+ * read, elements dropped by the site rule -- every copy counted}; seen = added + lost + dropped, where added is what these adds contribute to
+ * rbg_tally_info's `elements` (which counts the elements actually added, in either mode; `records` the printed records handed in).  The counters'
+ * device memory is allocated by the first per-read add (a tally that never sees one stays at its create-time allocations), counted in hbm_bytes,
+ * zeroed by rbg_tally_reset and freed with the tally. */
+#define RBG_TALLY_PER_READ 1u
+#define RBG_TALLY_DROP_SITE_CONFLICTS 2u /* RBG_EARG without RBG_TALLY_PER_READ */
 typedef struct rbg_tally rbg_tally;
 typedef struct rbg_tally_entry { uint64_t marker, n_fwd, n_rev, len_sum; } rbg_tally_entry_t;
 int rbg_tally_create(rbg_index *, uint64_t distinct_hint, rbg_tally **out);
@@ -468,6 +490,12 @@ int rbg_markers_tally(rbg_index *, const uint8_t *seqs, const uint64_t *off, uin
 int rbg_tally_add_entries(rbg_tally *, const rbg_tally_entry_t *entries, uint64_t count);
 int rbg_tally_export(rbg_tally *, uint64_t *count, rbg_tally_entry_t **entries);
 int rbg_tally_info(rbg_tally *, uint64_t out[6]);
+int rbg_markers_tally_reads(rbg_index *, const uint8_t *seqs, const uint64_t *off, uint64_t N, const uint8_t *first_fwd /* nullable */,
+                            const rbg_report_params_t *params, uint32_t tally_flags, rbg_tally *);
+size_t rbg_tally_add_reads_tmp_bytes(uint64_t N, uint64_t R);
+int rbg_tally_add_reads_dev(rbg_tally *, const rbg_report_seed_t *d_recs, uint64_t R, const uint64_t *d_rep_off /* [N+1] */, uint64_t N,
+                            const uint64_t *d_mk, uint64_t M_upper, uint32_t tally_flags, void *d_tmp, size_t tmp_bytes, void *stream);
+int rbg_tally_read_info(rbg_tally *, uint64_t out[4]);
 /* ---- queries, device-resident buffers (HBM in, HBM out; asynchronous on `stream`) ---------- */
 /* d_seqs: the reads back to back as in the host calls, in device memory, 16-BYTE ALIGNED (RBG_EARG otherwise), and the allocation must reach the next
  * multiple of 16 bytes at or past its last read's end: the kernels fetch reads as aligned 16-byte chunks (the bytes beyond a read's end are never used).

@@ -85,6 +85,9 @@ REPORT_SEED = np.dtype([("range_size", "<u8"), ("query_start", "<u8"), ("query_l
 # rbg_tally_entry_t as a numpy record
 TALLY_ENTRY = np.dtype([("marker", "<u8"), ("n_fwd", "<u8"), ("n_rev", "<u8"), ("len_sum", "<u8")])
 TALLY_INFO = ("entries", "capacity", "grows", "records", "elements", "dropped")
+# rbg_markers_tally_reads' / rbg_tally_add_reads_dev's flag word; rbg_tally_read_info's four counters
+TALLY_PER_READ, TALLY_DROP_SITE_CONFLICTS = 1, 2
+TALLY_READ_INFO = ("reads", "elements_seen", "lost", "site_dropped")
 
 
 def report_params(wsize=19, max_range=1000, min_range=0, ftab_k=0, read_len=101, min_seed_len=0, lmem=False, heuristic=False, best_strand=False,
@@ -213,6 +216,10 @@ _PROTOS = [
     ("rbg_tally_add_entries", C.c_int, [VP, VP, U64]),
     ("rbg_tally_export", C.c_int, [VP, C.POINTER(U64), C.POINTER(VP)]),
     ("rbg_tally_info", C.c_int, [VP, VP]),
+    ("rbg_markers_tally_reads", C.c_int, [VP, VP, VP, U64, VP, VP, C.c_uint32, VP]),
+    ("rbg_tally_add_reads_tmp_bytes", C.c_size_t, [U64, U64]),
+    ("rbg_tally_add_reads_dev", C.c_int, [VP, VP, U64, VP, U64, VP, U64, C.c_uint32, VP, C.c_size_t, VP]),
+    ("rbg_tally_read_info", C.c_int, [VP, VP]),
     ("rbg_set_default_option", C.c_int, [C.c_int, C.c_int64]),
     ("rbg_get_default_option", C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
 ]
@@ -388,6 +395,13 @@ class Tally:
         out = np.zeros(6, np.uint64)
         _check(self.L.rbg_tally_info(self.h, _p(out)), "rbg_tally_info")
         return dict(zip(TALLY_INFO, (int(v) for v in out)))
+
+    def read_info(self):
+        """rbg_tally_read_info: what the per-read adds saw -- reads, marker elements, elements that lost to another line of their read, elements the
+        site rule dropped (elements_seen = the elements these adds added + lost + site_dropped)"""
+        out = np.zeros(4, np.uint64)
+        _check(self.L.rbg_tally_read_info(self.h, _p(out)), "rbg_tally_read_info")
+        return dict(zip(TALLY_READ_INFO, (int(v) for v in out)))
 
 
 class RowBowt:
@@ -703,11 +717,15 @@ class RowBowt:
         finally:
             self.L.rbg_release_text(self.h, text)
 
-    def markers_tally(self, seqs, off, params, first_fwd, tally):
+    def markers_tally(self, seqs, off, params, first_fwd, tally, flags=0):
         """rbg_markers_tally: markers_report's inputs; the markers of the lines rb_markers would print are added to `tally` (a Tally of this
-        index) on the device, nothing is returned"""
+        index) on the device, nothing is returned.  flags: TALLY_PER_READ counts a marker once per read (its longest line),
+        | TALLY_DROP_SITE_CONFLICTS leaves out the sites of which a read carries two alleles (rbg_markers_tally_reads)"""
         N = len(off) - 1
         coin = None if first_fwd is None else np.ascontiguousarray(first_fwd, dtype=np.uint8)
+        if flags:
+            _check(self.L.rbg_markers_tally_reads(self.h, _p(seqs), _p(off), N, _p(coin), C.byref(params), flags, tally.h), "rbg_markers_tally_reads")
+            return
         _check(self.L.rbg_markers_tally(self.h, _p(seqs), _p(off), N, _p(coin), C.byref(params), tally.h), "rbg_markers_tally")
 
     def counters(self):

@@ -71,6 +71,7 @@ struct ReportOut {   // where a call's result goes
     size_t text_cap = 0, text_len = 0;
     // tally: the printed records' markers are added on the device, nothing is copied out
     rbg_tally *tally = nullptr;
+    uint32_t tally_flags = 0;   // RBG_TALLY_PER_READ [| RBG_TALLY_DROP_SITE_CONFLICTS]; 0: every line counts
 };
 
 struct ReportPass {   // reads [a, b) of the batch on the device, from step to step
@@ -84,6 +85,7 @@ struct ReportPass {   // reads [a, b) of the batch on the device, from step to s
     const uint8_t *d_coin = nullptr;
     SeedPass seeds;                          // the strands' seed records (canonical after select_records) and markers
     DevBuf dctmp, drep, drecs, dread, dstmp, dmelem, dws;   // select: printed records per read, the records, their reads; the element map of the outputs
+    DevBuf dspan;                            // per-read tally: every record's read as a record range
     size_t stmp_bytes = 0, ws_bytes = 0;
     uint64_t R = 0, M = 0, E = 0;            // printed records, their markers, R + M
 };
@@ -246,7 +248,11 @@ int emit_text(rbg_index *ix, ReportOut &o, ReportPass &p, hipStream_t st) {
 
 // tally: room was reserved between the seed phases; the add is the pass's last launch and nothing comes back
 int emit_tally(ReportOut &o, ReportPass &p, hipStream_t st) {
-    return tally_add_mapped(o.tally, p.drecs.p, p.R, p.seeds.dmk.as<uint64_t>(), p.dmelem.as<uint64_t>(), p.seeds.total_mk, st);
+    if (!o.tally_flags) return tally_add_mapped(o.tally, p.drecs.p, p.R, p.seeds.dmk.as<uint64_t>(), p.dmelem.as<uint64_t>(), p.seeds.total_mk, st);
+    int rc = p.dspan.alloc(tally_span_bytes(p.R));   // per-read mode: drep tells which records are one read's (a pass holds whole reads)
+    if (rc) return rc;
+    return tally_add_mapped(o.tally, p.drecs.p, p.R, p.seeds.dmk.as<uint64_t>(), p.dmelem.as<uint64_t>(), p.seeds.total_mk, st, o.tally_flags, p.drep.as<uint64_t>(), p.n,
+                            p.dspan.p);
 }
 
 // reads [a, b) of the batch: strands -> seeds -> canon -> select -> records, text or tally.  The trace's slots in their order: 0 copy in + strands, 1 plan,
@@ -285,6 +291,8 @@ int report_pass(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, uint64_
             if ((rc = o.want_text ? emit_text(ix, o, p, st) : emit_records(o, p, st))) return rc;
             p.lap(6);
         }
+    } else if (o.tally && (o.tally_flags & RBG_TALLY_PER_READ)) {
+        o.tally->reads += p.n;   // (reads seen, though none of them printed a line)
     }
     p.lap.done(p.n, p.d2h_bytes);
     return RBG_OK;
@@ -381,6 +389,17 @@ int rbg_markers_tally(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, u
     if (!tally || !ix || tally->ix->device != ix->device) return RBG_EARG;
     ReportOut o;
     o.tally = tally;
+    return report_run(ix, seqs, off, N, first_fwd, params, o);
+    });
+}
+
+int rbg_markers_tally_reads(rbg_index *ix, const uint8_t *seqs, const uint64_t *off, uint64_t N, const uint8_t *first_fwd, const rbg_report_params_t *params,
+                            uint32_t tally_flags, rbg_tally *tally) {
+    return guarded([&]() -> int {
+    if (!tally || !ix || tally->ix->device != ix->device || !tally_flags_ok(tally_flags)) return RBG_EARG;
+    ReportOut o;
+    o.tally = tally;
+    o.tally_flags = tally_flags;
     return report_run(ix, seqs, off, N, first_fwd, params, o);
     });
 }

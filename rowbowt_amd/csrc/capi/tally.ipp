@@ -1,5 +1,5 @@
-// capi/tally.ipp -- the marker tally (k_tally.hip): the handle, its reserve rule, add / merge / export.  Part of rbg_capi.hip; rbg_markers_tally, the
-// call that feeds a tally from raw reads, is report_pass's third output and sits beside the other two in capi/report.ipp.
+// capi/tally.ipp -- the marker tally (k_tally.hip): the handle, its reserve rule, add (line mode and per-read mode) / merge / export.  Part of rbg_capi.hip;
+// rbg_markers_tally[_reads], the calls that feed a tally from raw reads, are report_pass's third output and sit beside the other two in capi/report.ipp.
 //
 // THE RESERVE RULE.  The kernels never meet a full table because nothing is launched without room: the host keeps `bound`, an upper bound of the
 // claimed slots (the exact count at the last read plus every element handed to a launch since), and a launch of M elements needs
@@ -11,6 +11,9 @@ struct rbg_tally {
     uint64_t cap = 0, bound = 0, grows = 0;
     void *ws = nullptr;                          // the element -> record map of an add (launch_report_map's workspace), kept from call to call
     size_t ws_bytes = 0;
+    uint64_t *xhdr = nullptr;                    // per-read mode's counters (k_tally_add_reads: four u64), allocated by the first per-read add that has
+                                                 // records: a tally that never sees one keeps its create-time allocations
+    uint64_t reads = 0;                          // reads seen by per-read adds (counted here: reads without printed records launch nothing)
 };
 
 namespace {
@@ -58,9 +61,15 @@ int tally_reserve(rbg_tally *t, uint64_t extra) {
     return RBG_OK;
 }
 
+constexpr uint32_t kTallyFlags = RBG_TALLY_PER_READ | RBG_TALLY_DROP_SITE_CONFLICTS;
+inline bool tally_flags_ok(uint32_t f) { return !(f & ~kTallyFlags) && (!(f & RBG_TALLY_DROP_SITE_CONFLICTS) || (f & RBG_TALLY_PER_READ)); }
+inline size_t tally_span_bytes(uint64_t R) { return (R * 8 + 255) & ~size_t(255); }
+
 // the add behind launch_report_melem: the map over E = R + M_upper elements (M_upper >= melem[R]), then one lane per element.  The caller has checked
-// the room.  Asynchronous on st unless the map's workspace has to grow.
-int tally_add_mapped(rbg_tally *t, const void *d_recs, uint64_t R, const uint64_t *d_mk, const uint64_t *d_melem, uint64_t M_upper, hipStream_t st) {
+// the room.  Asynchronous on st unless the map's workspace has to grow.  flags (checked by the caller): 0 is line mode; per-read mode also takes the
+// records' per-read offsets d_rep_off[N + 1], N >= 1, and d_span, tally_span_bytes(R) of scratch.
+int tally_add_mapped(rbg_tally *t, const void *d_recs, uint64_t R, const uint64_t *d_mk, const uint64_t *d_melem, uint64_t M_upper, hipStream_t st,
+                     uint32_t flags = 0, const uint64_t *d_rep_off = nullptr, uint64_t N = 0, void *d_span = nullptr) {
     const uint64_t E = R + M_upper;
     const size_t need = report_text_ws_bytes(E);
     if (t->ws_bytes < need) {
@@ -70,8 +79,21 @@ int tally_add_mapped(rbg_tally *t, const void *d_recs, uint64_t R, const uint64_
         if (rc) return rc;
         t->ws_bytes = bytes;
     }
+    if ((flags & RBG_TALLY_PER_READ) && !t->xhdr) {
+        void *x = nullptr;
+        int rc = tally_dev_alloc(t->ix, 32, &x);
+        if (rc) return rc;
+        t->xhdr = static_cast<uint64_t *>(x);
+        HIP_TRY(hipMemsetAsync(t->xhdr, 0, 32, st));
+        HIP_TRY(hipStreamSynchronize(st));   // (once per tally: a later add may come on another stream)
+    }
     if (launch_report_map(d_melem, R, E, t->ws, t->ws_bytes, st)) return RBG_ENODEV;
-    if (launch_tally_add(t->slots, t->cap, t->hdr, d_recs, d_melem, d_mk, report_map_erec(t->ws), R, E, tally_combine_default(), st)) return RBG_ENODEV;
+    if (flags & RBG_TALLY_PER_READ) {
+        if (launch_tally_add_reads(t->slots, t->cap, t->hdr, t->xhdr, d_recs, d_melem, d_mk, report_map_erec(t->ws), d_rep_off, N, d_span, R, E, flags,
+                                   tally_combine_default(), st))
+            return RBG_ENODEV;
+        t->reads += N;
+    } else if (launch_tally_add(t->slots, t->cap, t->hdr, d_recs, d_melem, d_mk, report_map_erec(t->ws), R, E, tally_combine_default(), st)) return RBG_ENODEV;
     t->bound += M_upper;
     return RBG_OK;
 }
@@ -116,6 +138,7 @@ void rbg_tally_free(rbg_tally *t) {
     tally_dev_free(t->ix, t->slots);
     tally_dev_free(t->ix, t->hdr);
     tally_dev_free(t->ix, t->ws);
+    tally_dev_free(t->ix, t->xhdr);
     delete t;
     return RBG_OK;
     });
@@ -130,7 +153,9 @@ int rbg_tally_reset(rbg_tally *t) {
     hipStream_t st = hipStreamPerThread;
     if (launch_tally_clear(t->slots, t->cap, st)) return RBG_ENODEV;
     HIP_TRY(hipMemsetAsync(t->hdr, 0, 64, st));
+    if (t->xhdr) HIP_TRY(hipMemsetAsync(t->xhdr, 0, 32, st));
     HIP_TRY(hipStreamSynchronize(st));
+    t->reads = 0;
     t->bound = 0;
     t->grows = 0;
     return RBG_OK;
@@ -160,6 +185,29 @@ int rbg_tally_add_dev(rbg_tally *t, const rbg_report_seed_t *d_recs, uint64_t R,
     uint64_t *melem = static_cast<uint64_t *>(d_tmp);
     if (launch_report_melem(d_recs, R, melem, static_cast<char *>(d_tmp) + tally_melem_bytes(R), tmp_bytes - tally_melem_bytes(R), stream)) return RBG_ENODEV;
     return tally_add_mapped(t, d_recs, R, d_mk, melem, M_upper, static_cast<hipStream_t>(stream));
+    });
+}
+
+size_t rbg_tally_add_reads_tmp_bytes(uint64_t N, uint64_t R) { return tally_melem_bytes(R) + tally_span_bytes(R) + scan_tmp_bytes(R); }
+
+int rbg_tally_add_reads_dev(rbg_tally *t, const rbg_report_seed_t *d_recs, uint64_t R, const uint64_t *d_rep_off, uint64_t N, const uint64_t *d_mk, uint64_t M_upper,
+                            uint32_t tally_flags, void *d_tmp, size_t tmp_bytes, void *stream) {
+    return guarded([&]() -> int {
+    if (!t || !tally_flags_ok(tally_flags)) return RBG_EARG;
+    if (R == 0 || N == 0) {   // nothing to add; reads without printed records are still reads seen
+        if (tally_flags & RBG_TALLY_PER_READ) t->reads += N;
+        return RBG_OK;
+    }
+    if (!d_recs || !d_tmp || (R >> 32) || (M_upper && !d_mk) || tmp_bytes < rbg_tally_add_reads_tmp_bytes(N, R) || (reinterpret_cast<uintptr_t>(d_tmp) & 7)) return RBG_EARG;
+    if ((tally_flags & RBG_TALLY_PER_READ) && !d_rep_off) return RBG_EARG;
+    if (M_upper > tally_room(t)) return RBG_EARG;   // rbg_tally_reserve first, as for rbg_tally_add_dev
+    DeviceScope scope(t->ix->device);
+    if (scope.rc) return scope.rc;
+    char *tmp = static_cast<char *>(d_tmp);   // melem | the records' read spans | the scan's temporaries
+    const size_t used = tally_melem_bytes(R) + tally_span_bytes(R);
+    uint64_t *melem = reinterpret_cast<uint64_t *>(tmp);
+    if (launch_report_melem(d_recs, R, melem, tmp + used, tmp_bytes - used, stream)) return RBG_ENODEV;
+    return tally_add_mapped(t, d_recs, R, d_mk, melem, M_upper, static_cast<hipStream_t>(stream), tally_flags, d_rep_off, N, tmp + tally_melem_bytes(R));
     });
 }
 
@@ -232,6 +280,20 @@ int rbg_tally_info(rbg_tally *t, uint64_t out[6]) {
     out[3] = hdr[6];
     out[4] = hdr[7];
     out[5] = hdr[4];
+    return RBG_OK;
+    });
+}
+
+int rbg_tally_read_info(rbg_tally *t, uint64_t out[4]) {
+    return guarded([&]() -> int {
+    if (!t || !out) return RBG_EARG;
+    out[0] = t->reads;
+    out[1] = out[2] = out[3] = 0;
+    if (!t->xhdr) return RBG_OK;   // (no per-read add with records yet)
+    DeviceScope scope(t->ix->device);
+    if (scope.rc) return scope.rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out + 1, t->xhdr + 1, 24, hipMemcpyDeviceToHost));
     return RBG_OK;
     });
 }

@@ -21,6 +21,8 @@
 //
 // --tally <file> (not in the reference): no lines; the markers of the lines that would be printed are counted on the device
 // (rbg_markers_tally) and written at the end, one "<seq>\t<pos>\t<allele>\t<n_fwd>\t<n_rev>\t<len_sum>" per marker.
+// --tally-per-read: a marker counts once per read, on its longest line; --tally-drop-conflicts: a read with two alleles of a site counts for
+// neither (rbg_markers_tally_reads; include/rbg.h).  Both need --tally, the second needs the first: exit 1 otherwise.
 //
 // Not carried over (each exits 1 with a message, like the reference does for --overlap):
 //   --fbb/-x    other string type, other index file
@@ -70,6 +72,7 @@ struct RbMarkersArgs {  // rb_markers.cpp:22-40
     int device = 0;
     int device_format = 0, host_format = 0;   // --device-format: the lines are made on the device (rbg_markers_report_text); --host-format (the default): on host threads
     std::string tally_file;   // --tally <file>: no lines; per marker the number of lines that carried it, counted on the device (rbg_markers_tally)
+    int tally_per_read = 0, tally_drop_conflicts = 0;   // --tally-per-read, --tally-drop-conflicts: the tally's per-read mode (rbg_markers_tally_reads)
     uint64_t batch = 1u << 18;   // (2^17 kept more batches per window in flight but paid the library call's fixed costs twice as often: 0.32 against 0.25 s per 2 M reads)
 };
 
@@ -90,6 +93,9 @@ void print_help() {  // rb_markers.cpp:44-54
     fprintf(stderr, "    --tally <file>                   print nothing; count on the device, per marker, the lines that would carry it, and write\n");
     fprintf(stderr, "                                     <seq>\\t<pos>\\t<allele>\\t<n_fwd>\\t<n_rev>\\t<len_sum> per marker to <file>, sorted by\n");
     fprintf(stderr, "                                     (seq, pos, allele); works with every mode above, --device-format / --host-format are ignored\n");
+    fprintf(stderr, "    --tally-per-read                 with --tally: count reads, not lines -- of one read's lines that carry a marker only the\n");
+    fprintf(stderr, "                                     longest (the first of equals) counts\n");
+    fprintf(stderr, "    --tally-drop-conflicts           with --tally-per-read: a read whose lines carry two alleles of one site counts for neither\n");
     fprintf(stderr, "    <input_prefix>                   index prefix\n");
     fprintf(stderr, "    <input_fastq>                    input fastq\n");
 }
@@ -116,6 +122,8 @@ RbMarkersArgs parse_args(int argc, char **argv) {  // rb_markers.cpp:56-134
                                            {"gpu", required_argument, 0, 'G'},
                                            {"batch", required_argument, 0, 'B'},
                                            {"tally", required_argument, 0, 'T'},
+                                           {"tally-per-read", no_argument, &args.tally_per_read, 1},
+                                           {"tally-drop-conflicts", no_argument, &args.tally_drop_conflicts, 1},
                                            {0, 0, 0, 0}};
     int c, long_index = 0;
     // "o:" is accepted by the reference's optstring but has no case: it ends in the default branch
@@ -144,6 +152,14 @@ RbMarkersArgs parse_args(int argc, char **argv) {  // rb_markers.cpp:56-134
     }
     if (args.lmem && !args.ftab) {  // without an ftab the reference stops at rowbowt.hpp:346-349
         fprintf(stderr, "ftab must be enabled!\n");
+        exit(1);
+    }
+    if ((args.tally_per_read || args.tally_drop_conflicts) && args.tally_file.empty()) {
+        fprintf(stderr, "rb_markers: --tally-per-read / --tally-drop-conflicts need --tally <file>\n");
+        exit(1);
+    }
+    if (args.tally_drop_conflicts && !args.tally_per_read) {
+        fprintf(stderr, "rb_markers: --tally-drop-conflicts needs --tally-per-read\n");
         exit(1);
     }
     if (args.fbb) {
@@ -425,8 +441,9 @@ void tally_batch(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args, const Bat
     pack_raw_reads(b, slot);
     const auto t1 = std::chrono::steady_clock::now();
     const rbg_report_params_t p = report_params(rb, args);
-    rbwt::detail::check(rbg_markers_tally(rb.handle(), reinterpret_cast<const uint8_t *>(slot.seqs.data()), slot.off.data(), b.size(), slot.first_fwd.data(), &p,
-                                          tally.handle()), "rbg_markers_tally");
+    const uint32_t flags = (args.tally_per_read ? RBG_TALLY_PER_READ : 0u) | (args.tally_drop_conflicts ? RBG_TALLY_DROP_SITE_CONFLICTS : 0u);
+    rbwt::detail::check(rbg_markers_tally_reads(rb.handle(), reinterpret_cast<const uint8_t *>(slot.seqs.data()), slot.off.data(), b.size(), slot.first_fwd.data(), &p,
+                                                flags, tally.handle()), "rbg_markers_tally_reads");
     g_trace[0] += std::chrono::duration<double>(t1 - t0).count();
     g_trace[1] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
 }

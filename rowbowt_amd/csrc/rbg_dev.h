@@ -621,6 +621,10 @@ bool tally_combine_default();   // RBG_TALLY_COMBINE=0: no combining of equal ke
 int launch_tally_clear(uint64_t *slots, uint64_t cap, void *stream);
 int launch_tally_add(uint64_t *slots, uint64_t cap, uint64_t *hdr, const void *recs, const uint64_t *melem, const uint64_t *mk, const uint32_t *erec, uint64_t R,
                      uint64_t E, bool combine, void *stream);
+// per-read mode (RBG_TALLY_PER_READ [| RBG_TALLY_DROP_SITE_CONFLICTS] in flags): the same elements plus the records' per-read offsets rep_off[N + 1], N >= 1;
+// span: room for R x 8 bytes, 8-byte aligned (every record's read as a record range); xhdr: four u64 {-, elements seen, lost, site-dropped}
+int launch_tally_add_reads(uint64_t *slots, uint64_t cap, uint64_t *hdr, uint64_t *xhdr, const void *recs, const uint64_t *melem, const uint64_t *mk,
+                           const uint32_t *erec, const uint64_t *rep_off, uint64_t N, void *span, uint64_t R, uint64_t E, uint32_t flags, bool combine, void *stream);
 int launch_tally_add_entries(uint64_t *slots, uint64_t cap, uint64_t *hdr, const void *entries, uint64_t count, void *stream);
 int launch_tally_rehash(const uint64_t *old_slots, uint64_t old_cap, uint64_t *new_slots, uint64_t new_cap, uint64_t *hdr, void *stream);
 size_t tally_compact_tmp_bytes(uint64_t cap);

@@ -103,6 +103,13 @@ class MarkerTally {
         detail::check(rbg_tally_info(t_.get(), v), "rbg_tally_info");
         return Info{v[0], v[1], v[2], v[3], v[4], v[5]};
     }
+    // what the per-read adds (markers_tally with RBG_TALLY_PER_READ) saw: elements_seen = the elements they added + lost + site_dropped
+    struct ReadInfo { uint64_t reads, elements_seen, lost, site_dropped; };
+    ReadInfo read_info() const {
+        uint64_t v[4];
+        detail::check(rbg_tally_read_info(t_.get(), v), "rbg_tally_read_info");
+        return ReadInfo{v[0], v[1], v[2], v[3]};
+    }
 
    private:
     struct Free { void operator()(rbg_tally *t) const { rbg_tally_free(t); } };
@@ -481,15 +488,19 @@ class RowBowt {
     }
 
     // The same reads and parameters as markers_report_batch, but the printed lines' markers are counted on the device into `tally` (made by
-    // make_tally of this index) instead of coming back: n_fwd / n_rev per strand of the line, len_sum of the lines' query_len.
+    // make_tally of this index) instead of coming back: n_fwd / n_rev per strand of the line, len_sum of the lines' query_len.  tally_flags:
+    // RBG_TALLY_PER_READ counts a marker once per read (its longest line), | RBG_TALLY_DROP_SITE_CONFLICTS leaves out the sites of which a read
+    // carries two alleles (include/rbg.h).
     MarkerTally make_tally(uint64_t distinct_hint = 0) const { return MarkerTally(ix_.get(), distinct_hint); }
-    void markers_tally(const std::vector<std::string> &queries, rbg_report_params_t params, const std::vector<uint8_t> &first_fwd, MarkerTally &tally) const {
+    void markers_tally(const std::vector<std::string> &queries, rbg_report_params_t params, const std::vector<uint8_t> &first_fwd, MarkerTally &tally,
+                       uint32_t tally_flags = 0) const {
         const uint64_t N = queries.size();
         params.ftab_k = disable_ft_ ? 0 : ft_k_;
         detail::Batch b;
         for (const auto &q : queries) b.add(q);
-        detail::check(rbg_markers_tally(ix_.get(), b.data(), b.off.data(), N, first_fwd.size() == N && N ? first_fwd.data() : nullptr, &params, tally.handle()),
-                      "rbg_markers_tally");
+        detail::check(rbg_markers_tally_reads(ix_.get(), b.data(), b.off.data(), N, first_fwd.size() == N && N ? first_fwd.data() : nullptr, &params, tally_flags,
+                                              tally.handle()),
+                      "rbg_markers_tally_reads");
     }
 
     // get_seeds_greedy_w_sample (w_sample) or get_seeds_greedy for many reads: out[i] = the list of queries[i]

@@ -6,7 +6,11 @@ process, over --steps steps after --warmup, for the reads in random order and so
     add (rbg_tally_add_dev on select's records) into an empty table and into one that holds the keys already, with the combining of equal keys
     within a wave on and off (RBG_TALLY_COMBINE);
   - the whole host calls on the same reads: rbg_markers_report (records), rbg_markers_report_text and rbg_markers_tally (combining on and off;
-    one tally fed by every step, so its reserve rule and its grows are part of the time).
+    one tally fed by every step, so its reserve rule and its grows are part of the time);
+  - the per-read mode beside the line mode: the add (rbg_tally_add_reads_dev with RBG_TALLY_PER_READ and with | RBG_TALLY_DROP_SITE_CONFLICTS) next
+    to rbg_tally_add_dev, and the three whole calls (rbg_markers_tally; rbg_markers_tally_reads per read; per read + site rule) on the same reads,
+    three runs each after one warm-up, each into a tally of its own that holds the keys after the warm-up.  The verdict lines compare the SLOWEST
+    of a per-read mode's three with the FASTEST of the line mode's three.
 One JSON line per measurement.  GPU box only."""
 import argparse
 import ctypes as C
@@ -55,6 +59,7 @@ params = capi.report_params(wsize=args.wsize, max_range=args.max_range)
 print(f"marker tally: n={inp['n']} r={inp['r']} {len(markers[0])} marker runs, {N} reads x {m} bp, wsize {args.wsize}, max_range {args.max_range}, "
       f"{args.steps} steps after {args.warmup}", flush=True)
 st = torch.cuda.current_stream().cuda_stream
+MODES = (("line", 0), ("per read", capi.TALLY_PER_READ), ("per read + site rule", capi.TALLY_PER_READ | capi.TALLY_DROP_SITE_CONFLICTS))
 
 
 def timed(step, before=None):
@@ -152,6 +157,18 @@ for order, flat in ORDERS.items():
         tag = "combining on" if on else "combining off"
         rows[f"add into an empty table, {tag}"] = timed(add, empty)
         rows[f"add, keys present, {tag}"] = timed(add, full)
+    rtmp_bytes = L.rbg_tally_add_reads_tmp_bytes(N, R)
+    d_rtmp = new(rtmp_bytes, torch.uint8)
+    combine(True)
+    for tag, flags in MODES[1:]:
+        def add_reads():
+            ok(L.rbg_tally_add_reads_dev(t.h, d_recs.data_ptr(), R, d_rep.data_ptr(), N, d_mk.data_ptr(), M_raw, flags, d_rtmp.data_ptr(), rtmp_bytes, st))
+
+        rows[f"add {tag}, into an empty table"] = timed(add_reads, empty)
+        rows[f"add {tag}, keys present"] = timed(add_reads, full)
+        ri = t.read_info()
+        print(json.dumps({"order": order, "mode": tag, "read_info after the adds": ri}), flush=True)
+    del d_rtmp
     empty()
     add()
     i = t.info()   # (synchronises)
@@ -180,6 +197,29 @@ for order, flat in ORDERS.items():
         print(json.dumps({"order": order, "tally after the calls": i}), flush=True)
         t.close()
     combine(True)
+    three = {}
+    for tag, flags in MODES:   # the same reads, three runs each after one warm-up
+        t = capi.Tally(rb, 0)
+
+        def call_mode():
+            rb.markers_tally(flat, off, params, None, t, flags=flags)
+
+        call_mode()
+        ms = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            call_mode()
+            b.record()
+            b.synchronize()
+            ms.append(a.elapsed_time(b))
+        three[tag] = ms
+        print(json.dumps({"order": order, "whole call, three runs": tag, "ms": [round(x, 4) for x in ms], "info": t.info(), "read_info": t.read_info()}), flush=True)
+        t.close()
+    for tag, _ in MODES[1:]:
+        print(json.dumps({"order": order, "mode": tag, "slowest of three / fastest of three of the line mode": round(max(three[tag]) / min(three["line"]), 4)}),
+              flush=True)
     for what, (med, lo, hi) in rows.items():
         print(json.dumps({"order": order, "step": what, "ms_median": round(med, 4), "ms_min": round(lo, 4), "ms_max": round(hi, 4), "reads": N,
                           "reads_per_s": N / (med * 1e-3)}), flush=True)
