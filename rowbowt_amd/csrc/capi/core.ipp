@@ -5,6 +5,7 @@ static_assert(kMaxRunDepth == kMaxKmerDepth && kLdsRunDepth == kMaxSlotKmerDepth
 
 #include "../rbg_hostpath.hpp"
 #include "../rbg_reloc_check.hpp"
+#include "../rbg_load_plan.hpp"
 
 struct DevAlloc {
     void *p;
@@ -128,14 +129,6 @@ std::atomic<int64_t> g_opt_dense_overflow{1};
 std::atomic<int64_t> g_opt_rank_layout{env_opt("RBG_LAYOUT", RBG_LAYOUT_AUTO, RBG_LAYOUT_AUTO, RBG_LAYOUT_PREFER_SLOTS)};    // RBG_LAYOUT_AUTO / _SLOTS / _RUNS / _PREFER_SLOTS
 // the two automatic settings (include/rbg.h): both take the run-indexed layout when not even the single-symbol slot tables fit the budget;
 // RBG_LAYOUT_AUTO also when the slot tables would have to give up symbols per step for it (rbg_index::auto_runs, decided by options_for)
-// The k-mer depths that get run lists when RBG_OPT_RUN_DEPTHS names none: the deepest K, then K / 2, K / 4, ... and 1 (of eight: 1, 2, 4, 8).
-// A search step consumes the longest stretch a kept depth covers, so whole reads go by K symbols a step and the remainder of a
-// read (or of a seed) takes one step per set bit; every depth kept costs its run lists.
-inline uint32_t default_depth_mask(uint32_t K) {
-    uint32_t mask = 1u;
-    for (uint32_t d = K; d >= 1; d /= 2) mask |= 1u << (d - 1);
-    return mask;
-}
 inline bool layout_automatic() { const int64_t v = g_opt_rank_layout.load(); return v == RBG_LAYOUT_AUTO || v == RBG_LAYOUT_PREFER_SLOTS; }
 std::atomic<int64_t> g_opt_run_depths{env_opt("RBG_RUN_DEPTHS", 0, 0, (1 << kMaxRunDepth) - 1)};    // run-indexed layout: bit d - 1 = keep the k-mer depth d (0 = default_depth_mask: the deepest, half of it, a quarter ..., 1)
 std::atomic<int64_t> g_opt_run_phi{env_opt("RBG_RUN_PHI", 0, 0, 2)};   // run-indexed layout, format 2: 0 = automatic, 1 = phi over the sampled-position list (12-16 bytes per run), 2 = phi SLOTS of about n/r rows (about 54 bytes per run at 8-byte positions; one sector per step instead of two)
@@ -143,34 +136,15 @@ std::atomic<int64_t> g_opt_run_rec_depths{env_opt("RBG_RUN_REC_DEPTHS", 0, 0, (1
 std::atomic<int64_t> g_opt_run_rec{env_opt("RBG_RUN_REC", 0, 0, 2)};   // run-indexed layout, format 2: bucket records (rbg_dev.h RunRec2) -- 0 = automatic (when the replica with them stays within half the budget), 1 = off, 2 = on
 std::atomic<int64_t> g_opt_packed_reads{1};  // host-pointer calls: 0 bytes over PCIe, 1 (default) 2-bit codes for batches >= 4096, 2 always
 
-// The replica's share of the free HBM when no budget is given (RBG_OPT_HBM_BUDGET_MB): A QUARTER.  Until round 3 a default
-// rbg_load took three quarters -- the bench index then got its 5-symbol slot level (218 GB) for the last 10-15 % of K1/K2's
-// speed and left its caller 80 GB of a 288 GB device.  A drop-in library should leave the device to its caller unless told
-// otherwise: with a quarter the same load keeps the 4-symbol level (58 GB), and the budget option is one call away.
-inline size_t default_budget(size_t free_b) { return free_b / 4; }
-// How many symbols per step of the run-indexed layout are worth composing, estimated BEFORE composing: a depth adds at most about 0.62 r runs to
-// the one before it (measured 0.55-0.69 r per depth at r = 1.07e9, n / r = 282; 0.33 r on the bench index), pieces are indexed with 32 bits, the
-// sweeps hold about 70 bytes per piece of the depth being made (profiles/r04_pangenome_stream_r1e9_k5.log), and -- with_budget -- the least the budget
-// rule of upload() keeps of a depth K (the single symbols, K itself, phi) must fit the budget at 18 bytes per entry.
-// RBG_ASSUME_FREE_HBM_MB (tests only): the free HBM the PLANNING of a load assumes (budget, composition depth), capped to this many MiB -- so that
-// the rules an index of r = 1e9 runs meets on a 288 GB device (budget raised, depth planned before composing) are exercised by a test-sized index.
-// Allocation itself is not limited by it.
-inline size_t assumed_free_hbm(size_t free_b) {
+// RBG_ASSUME_FREE_HBM_MB (tests only; rbg_load_plan.hpp assumed_free_hbm): read HERE and nowhere else.  `given`: the variable is set at all -- the budget raise
+// of options_for() then takes the assumed free memory for the whole device
+struct AssumedFree {
+    bool given;
+    long long mb;
+};
+inline AssumedFree assumed_free_env() {
     const char *e = std::getenv("RBG_ASSUME_FREE_HBM_MB");
-    if (!e || std::atoll(e) <= 0) return free_b;
-    return std::min<size_t>(free_b, static_cast<size_t>(std::atoll(e)) << 20);
-}
-inline double est_depth_runs(double r, uint32_t d) { return r * (1.0 + 0.62 * static_cast<double>(d - 1)); }
-inline uint32_t planned_depth(double r, bool samples, uint32_t K0, double free_b, double budget, bool with_budget) {
-    const double per_entry = 8.0 + (samples ? 6.0 : 0.0) + 4.0;
-    uint32_t K = K0;
-    while (K > 1) {
-        bool ok = est_depth_runs(r, K) < 0.9 * 4294967296.0 && 70.0 * est_depth_runs(r, K) <= 0.95 * free_b;
-        if (ok && with_budget) ok = (samples ? 16.0 * r : 0.0) + (est_depth_runs(r, 1) + est_depth_runs(r, K)) * per_entry <= budget;
-        if (ok) break;
-        --K;
-    }
-    return K;
+    return {e != nullptr, e ? std::atoll(e) : 0};
 }
 
 #define HIP_TRY(expr)                                                                             \
@@ -355,6 +329,11 @@ int h2d_big(void *d_dst, const void *h_src, size_t bytes);
 // pre-computed arena (markers attached later) gets its own allocation.
 constexpr size_t kArenaAlign = 64 * 1024;
 inline size_t arena_round(size_t bytes) { return ((bytes ? bytes : 1) + kArenaAlign - 1) & ~(kArenaAlign - 1); }
+// what rbg_load_plan.hpp needs of rbg_dev.h and of the arena
+inline LoadConsts load_consts() {
+    return {kMaxNarrowShift, kMaxWideShift, static_cast<uint32_t>(kLdsSyms), sizeof(RankSlot) + sizeof(uint32_t), kArenaAlign,
+            {RunsFmt<uint32_t>::samp_bytes, RunsFmt<uint64_t>::samp_bytes}, {PhiFmt<uint32_t>::ent_bytes, PhiFmt<uint64_t>::ent_bytes}};
+}
 
 // space for `bytes` in the arena (or its own allocation when the arena is full / absent)
 int dev_reserve(rbg_index *ix, size_t bytes, void **dst) {
@@ -595,46 +574,6 @@ void free_tracked(rbg_index *ix, void *p) {
     for (size_t i = 0; i < ix->allocs.size(); ++i)
         if (ix->allocs[i].p == p) { ix->hbm_bytes -= ix->allocs[i].bytes; ix->allocs.erase(ix->allocs.begin() + static_cast<std::ptrdiff_t>(i)); break; }
     (void)hipFree(p);
-}
-
-// bytes of the run-indexed replica with the k-mer depths of `mask` (bit d - 1) among those h holds (run lists, samples,
-// 1/15 of sampled keys, phi)
-template <typename P>
-size_t runs_replica_bytes(const HostIndex &h, uint32_t mask = ~0u) {
-    size_t total = 0;
-    // 8-byte entries at either width, directory entries of 4 / 8 bytes per (at most) half a run
-    const size_t ent_bytes = 8, dir_per_entry = sizeof(P) == 8 ? 4 : 2;
-    for (uint32_t di = 0; di < static_cast<uint32_t>(kMaxKmerDepth); ++di) {
-        const std::vector<SymTable> *lv = di == 0 ? &h.sym : &h.kmer(di + 1);
-        if (!((mask | 1u) >> di & 1u)) continue;
-        size_t entries = 0;
-        for (const SymTable &t : *lv) entries += t.nruns + 1;
-        total += entries * (ent_bytes + (h.has_tsa ? RunsFmt<P>::samp_bytes : 0)) + entries * dir_per_entry + lv->size() * 8 + 8 * kArenaAlign;
-    }
-    if (h.has_tsa) total += (h.r + 1) * PhiFmt<P>::ent_bytes + h.r * 4;   // (+ the phi directory: at most r entries)
-    return total + 16 * kArenaAlign;
-}
-
-// bucket records of one k-mer depth at `per` entries per bucket on average: their number (a sparse table's bucket shift stops at max_shift)
-inline double runs_record_count(const HostIndex &h, uint32_t depth_index, double per, uint32_t max_shift) {
-    const std::vector<SymTable> &lv = depth_index == 0 ? h.sym : h.kmer(depth_index + 1);
-    double nrec = 0;
-    for (const SymTable &t : lv) {
-        uint32_t sh = 0;
-        const double runs = static_cast<double>(std::max<uint64_t>(1, t.nruns));
-        while (sh < max_shift && runs * static_cast<double>(uint64_t(2) << sh) <= per * static_cast<double>(h.n)) ++sh;
-        nrec += static_cast<double>((h.n >> sh) + 2);
-    }
-    return nrec;
-}
-// phi slots of about n / r rows on the run-indexed layout: their bytes, or 0 where the automatic rule would not build them (more than 2 r buckets)
-inline double runs_phi_slot_bytes(const HostIndex &h) {
-    if (!h.has_tsa) return 0;
-    uint32_t ss = 0;
-    while (ss < 8 && static_cast<double>(uint64_t(2) << ss) <= static_cast<double>(h.n) / static_cast<double>(std::max<uint64_t>(1, h.r))) ++ss;
-    if (ss < h.phi_shift) ss = h.phi_shift;
-    const double nb = static_cast<double>((h.n >> ss) + 2);
-    return nb <= 2.0 * static_cast<double>(h.r) ? nb * (h.pos_bytes == 8 ? 36.0 : 20.0) : 0.0;
 }
 
 void release_kmer_level(rbg_index *ix, uint32_t depth);

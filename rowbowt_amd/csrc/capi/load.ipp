@@ -1,8 +1,19 @@
-// capi/load.ipp -- upload() (layout and budget rules, the slot layout's tables), options_for(), finish(); the loading / converting / building
+// capi/load.ipp -- upload() and options_for() as sequences of named steps (their rules: rbg_load_plan.hpp), finish(); the loading / converting / building
 // entry points, rbg_info and the host-array accessors.  (What the query entry points share -- ReadBatch, the result pool, d2h_result -- is query.ipp.)
 // Part of rbg_capi.hip.
 namespace {
-int upload(rbg_index *ix) {
+// What the steps of upload() hand to each other beside the index itself.
+struct LoadPlan {
+    int compute_units = 0;
+    size_t free_b = 0, budget = 0;   // free HBM and replica budget of this load (as options_for() saw them, where it looked)
+    bool runs_layout = false;
+};
+
+int compose_both_widths(rbg_index *ix) { return ix->H().pos_bytes == 4 ? compose_on_device<uint32_t>(ix) : compose_on_device<uint64_t>(ix); }
+size_t slot_need(const HostIndex &h) { return h.pos_bytes == 4 ? replica_bytes<uint32_t>(h) : replica_bytes<uint64_t>(h); }
+size_t runs_need(const HostIndex &h, uint32_t mask) { return runs_replica_bytes(shape_of(h), load_consts(), mask); }
+
+int check_device(const rbg_index *ix, LoadPlan &p) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ix->device < 0 || ix->device >= ndev) {
         std::fprintf(stderr, "rbg: no usable HIP device %d (found %d); this library has no CPU path\n", ix->device, ndev);
@@ -14,8 +25,12 @@ int upload(rbg_index *ix) {
         std::fprintf(stderr, "rbg: device %d is %s; kernels are built for gfx950 (MI355X) only\n", ix->device, prop.gcnArchName);
         return RBG_ENODEV;
     }
-    DeviceScope scope(ix->device);
-    if (scope.rc) return scope.rc;
+    p.compute_units = prop.multiProcessorCount;
+    return RBG_OK;
+}
+
+// the device's description of the index, and the k-mer depths where flatten() left them to the device
+int compose_if_deferred(rbg_index *ix) {
     HostIndex &h = ix->H();
     DevIndex &d = ix->dev;
     d = DevIndex{};
@@ -26,294 +41,302 @@ int upload(rbg_index *ix) {
     d.has_tsa = h.has_tsa ? 1 : 0;
     d.last_run_sample = h.last_run_sample;
     d.phi_shift = h.phi_shift;
-    if (h.kmer_deferred) {   // depths 2.. composed on the device (flatten() only chose the k-mer alphabet)
-        const int rcc = h.pos_bytes == 4 ? compose_on_device<uint32_t>(ix) : compose_on_device<uint64_t>(ix);
-        if (rcc) return rcc;
-    }
-    // The k-mer tables buy speed with memory: keep the deepest level that fits a quarter of the free HBM
-    // (default_budget above) or RBG_OPT_HBM_BUDGET_MB.
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const int64_t opt_mb = g_opt_hbm_budget_mb.load();
+    if (h.kmer_deferred) return compose_both_widths(ix);   // depths 2.. composed on the device (flatten() only chose the k-mer alphabet)
+    return RBG_OK;
+}
+
+// The k-mer tables buy speed with memory: keep the deepest level that fits a quarter of the free HBM
+// (rbg_load_plan.hpp default_budget) or RBG_OPT_HBM_BUDGET_MB.
+int fix_budget(rbg_index *ix, LoadPlan &p) {
+    size_t total_b = 0;
+    HIP_TRY(hipMemGetInfo(&p.free_b, &total_b));
     // (the budget options_for() fixed before the composition put its levels on the device, where it was taken: VERDICT r4 item 8)
-    const size_t budget = ix->plan_budget ? static_cast<size_t>(ix->plan_budget) : opt_mb > 0 ? static_cast<size_t>(opt_mb) << 20 : default_budget(free_b);
-    if (ix->plan_free) free_b = static_cast<size_t>(ix->plan_free);
-    auto need = [&] { return h.pos_bytes == 4 ? replica_bytes<uint32_t>(h) : replica_bytes<uint64_t>(h); };
-    // Layout: the slot tables cost n/16 bytes per table + n/2 (n at 8-byte positions) for phi, whatever r is.  When
-    // even the single-symbol level does not fit the budget -- or on request -- the run-indexed layout takes over
-    // (space proportional to r; wave-cooperative predecessor search, k_runs.hip).
-    bool runs_layout = g_opt_rank_layout.load() == RBG_LAYOUT_RUNS || ix->auto_runs;
-    if (!runs_layout && layout_automatic()) {
+    p.budget = load_budget(p.free_b, g_opt_hbm_budget_mb.load(), ix->plan_budget);
+    if (ix->plan_free) p.free_b = static_cast<size_t>(ix->plan_free);
+    return RBG_OK;
+}
+
+// Layout: the slot tables cost n/16 bytes per table + n/2 (n at 8-byte positions) for phi, whatever r is.  When
+// even the single-symbol level does not fit the budget -- or on request -- the run-indexed layout takes over
+// (space proportional to r; wave-cooperative predecessor search, k_runs.hip).
+void decide_layout(rbg_index *ix, LoadPlan &p) {
+    HostIndex &h = ix->H();
+    p.runs_layout = runs_certain(g_opt_rank_layout.load(), ix->auto_runs);
+    if (!p.runs_layout && layout_automatic()) {
         size_t lvl1 = 0;  // the single-symbol level alone
         {
             std::vector<SymTable> held[kMaxKmerDepth - 1];
             for (uint32_t d = 2; d <= static_cast<uint32_t>(kMaxKmerDepth); ++d) held[d - 2].swap(h.kmer(d));
-            lvl1 = need();
+            lvl1 = slot_need(h);
             for (uint32_t d = 2; d <= static_cast<uint32_t>(kMaxKmerDepth); ++d) held[d - 2].swap(h.kmer(d));
         }
-        runs_layout = lvl1 > budget;
+        p.runs_layout = lvl1 > p.budget;
     }
-    // RBG_LAYOUT_AUTO, second look (options_for's was an estimate from n alone, before anything was composed): if the slot tables of the
-    // levels at hand exceed the budget, the rule below would give the deep levels wider buckets and then drop levels -- the run-indexed
-    // layout keeps every level at full speed instead, while it fits (about 110 bytes per run at its leanest).  Measured on the bench
-    // index at the default budget: 1.13e9 reads/s from the 70 GB of five symbols in wide buckets, 1.14e9 from the 59 GB of four
-    // symbols, 1.23e9 from the 8.7 GB of this layout (profiles/r04_bench.json space_speed / value_library_default).
-    if (!runs_layout && g_opt_rank_layout.load() == RBG_LAYOUT_AUTO && !h.kmer(2).empty() && h.sigma <= static_cast<uint32_t>(kLdsSyms) &&
-        need() > budget && 110.0 * static_cast<double>(h.r) <= static_cast<double>(budget)) {
-        if (std::getenv("RBG_VERBOSE"))
-            std::fprintf(stderr, "rbg: device %d: the slot tables of all k-mer levels (%.1f GB) exceed the %.1f GB replica budget: the run-indexed layout instead of "
-                                 "wider buckets or fewer symbols per step (RBG_LAYOUT_PREFER_SLOTS keeps slot tables)\n", ix->device, need() / 1e9, budget / 1e9);
-        runs_layout = true;
-        ix->auto_runs = true;
-        // the levels at hand are the slot layout's (at most kMaxSlotKmerDepth, composed before this look could be taken); the run-indexed
-        // layout steps by as many symbols as were asked for: compose again, that deep (rare: options_for's estimate usually decides first)
-        const uint32_t asked = static_cast<uint32_t>(std::min<int64_t>(g_opt_kmer_steps.load(), kMaxKmerDepth));
-        if (asked > h.kmer_levels() && compose_deferred(ix->device) && h.nmajor >= 1) {
-            for (SymTable &t : h.sym) {
-                free_tracked(ix, const_cast<void *>(t.dev_ent));
-                free_tracked(ix, const_cast<void *>(t.dev_samp));
-                t.dev_ent = t.dev_samp = nullptr;
-            }
-            h.kmer_deferred = asked;
-            ix->kmer_steps_requested = asked;
-            const int rcc = h.pos_bytes == 4 ? compose_on_device<uint32_t>(ix) : compose_on_device<uint64_t>(ix);
-            if (rcc) return rcc;
+}
+
+// RBG_LAYOUT_AUTO, second look (options_for's was an estimate from n alone, before anything was composed): if the slot tables of the
+// levels at hand exceed the budget, the rule below would give the deep levels wider buckets and then drop levels -- the run-indexed
+// layout keeps every level at full speed instead, while it fits (about 110 bytes per run at its leanest).  Measured on the bench
+// index at the default budget: 1.13e9 reads/s from the 70 GB of five symbols in wide buckets, 1.14e9 from the 59 GB of four
+// symbols, 1.23e9 from the 8.7 GB of this layout (profiles/r04_bench.json space_speed / value_library_default).
+int second_look_at_layout(rbg_index *ix, LoadPlan &p) {
+    HostIndex &h = ix->H();
+    if (p.runs_layout || g_opt_rank_layout.load() != RBG_LAYOUT_AUTO || h.kmer(2).empty() || h.sigma > static_cast<uint32_t>(kLdsSyms) ||
+        slot_need(h) <= p.budget || !runs_layout_fits(h.r, static_cast<double>(p.budget)))
+        return RBG_OK;
+    if (std::getenv("RBG_VERBOSE"))
+        std::fprintf(stderr, "rbg: device %d: the slot tables of all k-mer levels (%.1f GB) exceed the %.1f GB replica budget: the run-indexed layout instead of "
+                             "wider buckets or fewer symbols per step (RBG_LAYOUT_PREFER_SLOTS keeps slot tables)\n", ix->device, slot_need(h) / 1e9, p.budget / 1e9);
+    p.runs_layout = true;
+    ix->auto_runs = true;
+    // the levels at hand are the slot layout's (at most kMaxSlotKmerDepth, composed before this look could be taken); the run-indexed
+    // layout steps by as many symbols as were asked for: compose again, that deep (rare: options_for's estimate usually decides first)
+    const uint32_t asked = static_cast<uint32_t>(std::min<int64_t>(g_opt_kmer_steps.load(), kMaxKmerDepth));
+    if (asked > h.kmer_levels() && compose_deferred(ix->device) && h.nmajor >= 1) {
+        for (SymTable &t : h.sym) {
+            free_tracked(ix, const_cast<void *>(t.dev_ent));
+            free_tracked(ix, const_cast<void *>(t.dev_samp));
+            t.dev_ent = t.dev_samp = nullptr;
         }
+        h.kmer_deferred = asked;
+        ix->kmer_steps_requested = asked;
+        return compose_both_widths(ix);
     }
-    if (ix->runs_forced) runs_layout = true;
-    if (runs_layout && h.sigma > static_cast<uint32_t>(kLdsSyms)) {
+    return RBG_OK;
+}
+
+void settle_layout(rbg_index *ix, LoadPlan &p) {
+    HostIndex &h = ix->H();
+    if (ix->runs_forced) p.runs_layout = true;
+    if (p.runs_layout && h.sigma > static_cast<uint32_t>(kLdsSyms)) {
         std::fprintf(stderr, "rbg: %u distinct symbols: the run-indexed layout serves at most %d; keeping the slot tables\n", h.sigma, kLdsSyms);
-        runs_layout = false;
+        p.runs_layout = false;
     }
-    ix->runs_layout = runs_layout;
-    if (!runs_layout)   // (the slot layout stages at most kMaxSlotKmerDepth symbols per gather)
+    ix->runs_layout = p.runs_layout;
+    if (!p.runs_layout)   // (the slot layout stages at most kMaxSlotKmerDepth symbols per gather)
         while (levels_of(h) > kMaxSlotKmerDepth) drop_kmer_level(ix, h.kmer(h.kmer_levels()));
-    auto levels = [&] { return static_cast<int>(h.kmer_levels()); };
-    if (runs_layout) {
-        // the k-mer depths stay (their run lists are O(r) too: DevRunTab2, rbg_dev.h); the deepest goes while the replica
-        // exceeds the budget
-        if (ix->kmer_steps_requested == 0) ix->kmer_steps_requested = static_cast<uint64_t>(levels());
-        // RBG_OPT_RUN_DEPTHS: a step needs no table of every depth below the deepest -- a stretch of 4 symbols is a depth-3
-        // step and a single one where depth 4 is left out -- and the deepest lists are the largest (2.4 entries
-        // per run at depth 5 of the H = 200 pangenome, 9.3 over the five).  Over budget the depths between the first and the
-        // deepest go first (deepest of them first), then the deepest itself.
-        // Default: every other depth counted from the deepest (1, 3, 5 of five) -- two thirds of the space and the same
-        // rate on whole reads, a few per cent more steps where stretches are ragged (marker seeds); 0x1F keeps them all.
-        ix->runs_report = rbg_index::RunsReport();
-        ix->runs_report.depth_mask_asked = static_cast<uint32_t>(g_opt_run_depths.load());
-        uint32_t mask = g_opt_run_depths.load() ? static_cast<uint32_t>(g_opt_run_depths.load()) | 1u : default_depth_mask(static_cast<uint32_t>(levels()));
-        auto deepest_of = [&]() -> std::vector<SymTable> & { return h.kmer(static_cast<uint32_t>(std::max(2, levels()))); };
-        while (levels() > 1 && !(mask >> (levels() - 1) & 1u)) drop_kmer_level(ix, deepest_of());   // (nothing steps by a depth above the deepest kept)
-        mask &= (1u << levels()) - 1u;
-        auto need_runs = [&] { return h.pos_bytes == 4 ? runs_replica_bytes<uint32_t>(h, mask) : runs_replica_bytes<uint64_t>(h, mask); };
-        while (need_runs() > budget && levels() > 1) {
-            uint32_t mid = 0;
-            for (int d = levels() - 1; d >= 2 && !mid; --d)
-                if (mask >> (d - 1) & 1u) mid = static_cast<uint32_t>(d);
-            if (mid) {
-                std::fprintf(stderr, "rbg: run-indexed replica of %.1f GB exceeds the %.1f GB budget: leaving out the run lists of depth %u\n", need_runs() / 1e9, budget / 1e9, mid);
-                mask &= ~(1u << (mid - 1));
-                ix->runs_report.depths_dropped_budget |= 1u << (mid - 1);
-                continue;
-            }
-            std::fprintf(stderr, "rbg: run-indexed replica of %.1f GB exceeds the %.1f GB budget: dropping the %zu-table k-mer level\n",
-                         need_runs() / 1e9, budget / 1e9, deepest_of().size());
-            ix->runs_report.depths_dropped_budget |= 1u << (levels() - 1);
-            drop_kmer_level(ix, deepest_of());
-            // (the new deepest depth must still have its lists: a depth the composition gave back early goes too)
-            while (levels() > 1 && !level_has_data(ix, static_cast<uint32_t>(levels()))) drop_kmer_level(ix, deepest_of());
-            mask = (mask & ((1u << levels()) - 1u)) | (1u << (levels() - 1));   // (the new deepest level is stepped by again)
-        }
-        // Records everywhere before depths in between: a depth whose ranks go through a directory pays narrowing rounds in crowded buckets (n = 5e10 under the
-        // default budget: 2.7 rounds and 78 scanned entries per read, K2 13.8 ms against 7 with records; profiles/r05_pangenome_stream_n5e10_default.json),
-        // the depths between the first and the deepest save a step per read.  So when the automatic rules decide (no RBG_OPT_RUN_DEPTHS, no RBG_OPT_RUN_REC) and
-        // bucket records for every kept depth do not fit the budget, but would with the first and the deepest depth alone, the depths between them go.
-        if (g_opt_run_depths.load() == 0 && g_opt_run_rec.load() == 0 && levels() > 2) {
-            const uint32_t ends = 1u | (1u << (levels() - 1));
-            const uint32_t max_shift = h.pos_bytes == 8 ? static_cast<uint32_t>(env_opt("RBG_RUN_FILL_SHIFT", kRunFillShift, 4, kRunFillShift)) : 31u;
-            auto with_records = [&](uint32_t m) {
-                double bytes = static_cast<double>(h.pos_bytes == 4 ? runs_replica_bytes<uint32_t>(h, m) : runs_replica_bytes<uint64_t>(h, m));
-                if (g_opt_run_phi.load() != 1) bytes += runs_phi_slot_bytes(h);
-                for (int d = 0; d < levels(); ++d)
-                    if (m >> d & 1u) bytes += runs_record_count(h, static_cast<uint32_t>(d), 6.0, max_shift) * 64.0;
-                return bytes;
-            };
-            if (mask != ends && with_records(mask) > static_cast<double>(budget) && with_records(ends) <= static_cast<double>(budget)) {
-                std::fprintf(stderr, "rbg: bucket records for every kept depth (%.1f GB with them) exceed the %.1f GB budget: leaving out the depths between 1 and %d "
-                                     "(%.1f GB with records for both)\n", with_records(mask) / 1e9, budget / 1e9, levels(), with_records(ends) / 1e9);
-                ix->runs_report.depths_dropped_budget |= mask & ~ends;
-                mask = ends;
-            }
-        }
-        for (int d = 2; d < levels(); ++d)   // the depths left out give their device arrays back now
-            if (!(mask >> (d - 1) & 1u)) {
-                release_kmer_level(ix, static_cast<uint32_t>(d));
-                for (SymTable &st : kmer_level_tables(h, static_cast<uint32_t>(d))) st.dev_ent = st.dev_samp = nullptr;
-            }
-        ix->run_depth_mask = mask;
+}
+
+// one step of what rbg_load_plan.hpp trim_run_depths / trim_to_ends_for_records decided: said, and applied to the index
+void apply_trim_step(rbg_index *ix, const TrimStep &s, size_t budget) {
+    if (s.kind == TrimStep::kLeaveOutDepth)
+        std::fprintf(stderr, "rbg: run-indexed replica of %.1f GB exceeds the %.1f GB budget: leaving out the run lists of depth %u\n", s.need / 1e9, budget / 1e9, s.depth);
+    if (s.kind == TrimStep::kDropDeepest)
+        std::fprintf(stderr, "rbg: run-indexed replica of %.1f GB exceeds the %.1f GB budget: dropping the %zu-table k-mer level\n", s.need / 1e9, budget / 1e9, s.tables);
+    if (s.kind == TrimStep::kEndsOnly)
+        std::fprintf(stderr, "rbg: bucket records for every kept depth (%.1f GB with them) exceed the %.1f GB budget: leaving out the depths between 1 and %d "
+                             "(%.1f GB with records for both)\n", s.need / 1e9, budget / 1e9, static_cast<int>(s.depth), s.with_ends / 1e9);
+    if (s.drops_level()) drop_kmer_level(ix, ix->H().kmer(s.depth));
+}
+
+// Run-indexed layout: the k-mer depths stay (their run lists are O(r) too: DevRunTab2, rbg_dev.h); RBG_OPT_RUN_DEPTHS or the default set names those that
+// get run lists (default: the deepest, half of it, ... 1 -- 0xFF keeps them all), and over budget depths go in the order of rbg_load_plan.hpp.
+void trim_run_levels(rbg_index *ix, const LoadPlan &p) {
+    HostIndex &h = ix->H();
+    if (ix->kmer_steps_requested == 0) ix->kmer_steps_requested = static_cast<uint64_t>(levels_of(h));
+    ix->runs_report = rbg_index::RunsReport();
+    ix->runs_report.depth_mask_asked = static_cast<uint32_t>(g_opt_run_depths.load());
+    const IndexShape shape = shape_of(h);
+    const LoadConsts consts = load_consts();
+    const uint32_t levels = h.kmer_levels();
+    uint32_t has_data = 1u;
+    for (uint32_t d = 2; d <= levels; ++d)
+        if (level_has_data(ix, d)) has_data |= 1u << (d - 1);
+    RunTrim t = trim_run_depths(shape, consts, asked_depth_mask(g_opt_run_depths.load(), levels), levels, p.budget, has_data);
+    if (ends_only_rule_applies(g_opt_run_depths.load(), g_opt_run_rec.load(), t.levels)) {
+        const uint32_t max_shift = h.pos_bytes == 8 ? static_cast<uint32_t>(env_opt("RBG_RUN_FILL_SHIFT", kRunFillShift, 4, kRunFillShift)) : 31u;
+        trim_to_ends_for_records(shape, consts, t, p.budget, max_shift, g_opt_run_phi.load());
     }
-    ix->kmer_steps_requested = std::max<uint64_t>(ix->kmer_steps_requested, static_cast<uint64_t>(levels()));  // options_for() may have capped the depth already
-    ix->hbm_free_at_load = free_b;
-    ix->hbm_budget = budget;
-    // Over budget: first give the k-mer levels wider buckets, deepest level first (their runs are sparse: a table
-    // goes to the widest bucket that still holds about half a run start on average, at most 4096 rows, in the
-    // wide-slot encoding of rbg_dev.h -- a few per cent slower per step), then drop the deepest level
-    // and try again.  At pangenome scale this keeps a level more than dropping alone.
-    auto widen = [&](std::vector<SymTable> &lvl) {
-        if (h.n >> 40) return;  // wide slots carry 40-bit ranks
-        for (SymTable &t : lvl) {
-            const double rows_per_run = static_cast<double>(h.n) / static_cast<double>(std::max<uint64_t>(1, t.nruns));
-            uint32_t want = 0;
-            while (want < kMaxWideShift && static_cast<double>(uint64_t(2) << want) <= rows_per_run) ++want;   // 2^want <= rows_per_run / 2
-            if (want > t.shift) t.shift = want;
+    for (const TrimStep &s : t.steps) apply_trim_step(ix, s, p.budget);
+    ix->runs_report.depths_dropped_budget = t.depths_dropped_budget;
+    for (uint32_t d = 2; d < t.levels; ++d)   // the depths left out give their device arrays back now
+        if (!(t.mask >> (d - 1) & 1u)) {
+            release_kmer_level(ix, d);
+            for (SymTable &st : kmer_level_tables(h, d)) st.dev_ent = st.dev_samp = nullptr;
         }
-    };
+    ix->run_depth_mask = t.mask;
+}
+
+// Slot layout over budget: first give the k-mer levels wider buckets, deepest level first (their runs are sparse: rbg_load_plan.hpp widened_shift
+// -- a few per cent slower per step), then drop the deepest level and try again.  At pangenome scale this keeps a level more than
+// dropping alone.
+void trim_slot_levels(rbg_index *ix, const LoadPlan &p) {
+    HostIndex &h = ix->H();
+    const LoadConsts consts = load_consts();
     bool widened = false;
-    while (need() > budget && !h.kmer(2).empty() && !runs_layout) {
+    while (slot_need(h) > p.budget && !h.kmer(2).empty()) {
         if (!widened && g_opt_deep_shift.load() < 0 && g_opt_rank_shift.load() < 0) {
             widened = true;
             for (uint32_t wd = static_cast<uint32_t>(kMaxSlotKmerDepth); wd >= 2; --wd) {
-                std::vector<SymTable> *lvl = &h.kmer(wd);
-                if (!lvl->empty() && need() > budget) {
-                    const size_t before = need();
-                    widen(*lvl);
-                    if (need() != before)
-                        std::fprintf(stderr, "rbg: replica of %.1f GB exceeds the %.1f GB budget: wider buckets for the %zu-table k-mer level (%.1f GB)\n",
-                                     before / 1e9, budget / 1e9, lvl->size(), need() / 1e9);
-                }
+                std::vector<SymTable> &lvl = h.kmer(wd);
+                if (lvl.empty() || slot_need(h) <= p.budget) continue;
+                const size_t before = slot_need(h);
+                for (SymTable &t : lvl) t.shift = widened_shift(h.n, t.nruns, t.shift, consts);
+                if (slot_need(h) != before)
+                    std::fprintf(stderr, "rbg: replica of %.1f GB exceeds the %.1f GB budget: wider buckets for the %zu-table k-mer level (%.1f GB)\n",
+                                 before / 1e9, p.budget / 1e9, lvl.size(), slot_need(h) / 1e9);
             }
             continue;
         }
-        std::vector<SymTable> &deepest = h.kmer(static_cast<uint32_t>(levels()));
+        std::vector<SymTable> &deepest = h.kmer(h.kmer_levels());
         std::fprintf(stderr, "rbg: replica of %.1f GB exceeds the %.1f GB budget: dropping the %zu-table k-mer level\n",
-                     need() / 1e9, budget / 1e9, deepest.size());
+                     slot_need(h) / 1e9, p.budget / 1e9, deepest.size());
         drop_kmer_level(ix, deepest);
     }
+}
+
+void say_what_is_kept(const rbg_index *ix, const LoadPlan &p) {
+    const HostIndex &h = ix->H();
+    const int levels = levels_of(h);
     // (the slot layout stages at most kMaxSlotKmerDepth symbols per gather: a default request of eight that became five there is not news)
-    const uint64_t asked_here = runs_layout ? ix->kmer_steps_requested : std::min<uint64_t>(ix->kmer_steps_requested, static_cast<uint64_t>(kMaxSlotKmerDepth));
-    if (std::getenv("RBG_VERBOSE") || static_cast<uint64_t>(levels()) != asked_here)
+    const uint64_t asked_here = p.runs_layout ? ix->kmer_steps_requested : std::min<uint64_t>(ix->kmer_steps_requested, static_cast<uint64_t>(kMaxSlotKmerDepth));
+    if (std::getenv("RBG_VERBOSE") || static_cast<uint64_t>(levels) != asked_here)
         std::fprintf(stderr, "rbg: device %d: %.1f GB free, replica budget %.1f GB: keeping %d of %llu symbol(s) per %s (%.1f GB)\n", ix->device,
-                     free_b / 1e9, budget / 1e9, levels(), static_cast<unsigned long long>(ix->kmer_steps_requested), runs_layout ? "search step" : "gather",
-                     (runs_layout ? (h.pos_bytes == 4 ? runs_replica_bytes<uint32_t>(h, ix->run_depth_mask) : runs_replica_bytes<uint64_t>(h, ix->run_depth_mask)) : need()) / 1e9);
-    if (runs_layout && std::getenv("RBG_VERBOSE")) std::fprintf(stderr, "rbg: device %d: k-mer depths with run lists: mask 0x%x\n", ix->device, ix->run_depth_mask);
-    int rc;
-    d.layout = RBG_LAYOUT_SLOTS;
-    if (runs_layout) {
+                     p.free_b / 1e9, p.budget / 1e9, levels, static_cast<unsigned long long>(ix->kmer_steps_requested), p.runs_layout ? "search step" : "gather",
+                     (p.runs_layout ? runs_need(h, ix->run_depth_mask) : slot_need(h)) / 1e9);
+    if (p.runs_layout && std::getenv("RBG_VERBOSE")) std::fprintf(stderr, "rbg: device %d: k-mer depths with run lists: mask 0x%x\n", ix->device, ix->run_depth_mask);
+}
+
+int upload_layout_tables(rbg_index *ix, const LoadPlan &p) {
+    HostIndex &h = ix->H();
+    ix->dev.layout = RBG_LAYOUT_SLOTS;
+    if (p.runs_layout) {
         if (std::getenv("RBG_VERBOSE")) std::fprintf(stderr, "rbg: device %d: run-indexed layout (space proportional to r)\n", ix->device);
-        rc = h.pos_bytes == 4 ? upload_tables_runs2<uint32_t>(ix) : upload_tables_runs2<uint64_t>(ix);
-        if (rc) return rc;
-    } else {
-        ix->arena_bytes = h.pos_bytes == 4 ? replica_bytes<uint32_t>(h, true) : replica_bytes<uint64_t>(h, true);   // (without the lists that are on the device already)
-        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        if (ix->arena_bytes > free_b) {
-            std::fprintf(stderr, "rbg: index needs %.1f GB of HBM, %.1f GB free\n", ix->arena_bytes / 1e9, free_b / 1e9);
-            return RBG_ENOMEM;
-        }
-        {
-            VStage vs("arena hipMalloc");
-            // (a platform cost: fresh VRAM is mapped and cleared at some 45-70 GB/s when the memory was freed shortly before --
-            //  2.7-7 s for the bench replica's 218 GB -- and next to nothing when it has been idle: tools/alloc_probe.py,
-            //  profiles/r03_load_time.txt.  Asking for the block from a helper thread while the host flattens and the
-            //  device composes was tried: the driver serialises the composition's own allocations behind it, no gain.)
-            HIP_TRY(hipMalloc(&ix->arena, ix->arena_bytes));
-        }
-        ix->allocs.push_back({ix->arena, ix->arena_bytes});
-        ix->hbm_bytes += ix->arena_bytes;
-        ix->arena_used = 0;
-        rc = h.pos_bytes == 4 ? upload_tables<uint32_t>(ix) : upload_tables<uint64_t>(ix);
-        if (rc) return rc;
+        return h.pos_bytes == 4 ? upload_tables_runs2<uint32_t>(ix) : upload_tables_runs2<uint64_t>(ix);
     }
-    const void *p = nullptr;
-    if ((rc = dev_upload(ix, h.lut, 256, &p))) return rc;
-    d.lut = static_cast<const uint8_t *>(p);
+    ix->arena_bytes = h.pos_bytes == 4 ? replica_bytes<uint32_t>(h, true) : replica_bytes<uint64_t>(h, true);   // (without the lists that are on the device already)
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (ix->arena_bytes > free_b) {
+        std::fprintf(stderr, "rbg: index needs %.1f GB of HBM, %.1f GB free\n", ix->arena_bytes / 1e9, free_b / 1e9);
+        return RBG_ENOMEM;
+    }
+    {
+        VStage vs("arena hipMalloc");
+        // (a platform cost: fresh VRAM is mapped and cleared at some 45-70 GB/s when the memory was freed shortly before --
+        //  2.7-7 s for the bench replica's 218 GB -- and next to nothing when it has been idle: tools/alloc_probe.py,
+        //  profiles/r03_load_time.txt.  Asking for the block from a helper thread while the host flattens and the
+        //  device composes was tried: the driver serialises the composition's own allocations behind it, no gain.)
+        HIP_TRY(hipMalloc(&ix->arena, ix->arena_bytes));
+    }
+    ix->allocs.push_back({ix->arena, ix->arena_bytes});
+    ix->hbm_bytes += ix->arena_bytes;
+    ix->arena_used = 0;
+    return h.pos_bytes == 4 ? upload_tables<uint32_t>(ix) : upload_tables<uint64_t>(ix);
+}
+
+int upload_small_arrays(rbg_index *ix, const LoadPlan &p) {
+    HostIndex &h = ix->H();
+    DevIndex &d = ix->dev;
+    int rc;
+    const void *ptr = nullptr;
+    if ((rc = dev_upload(ix, h.lut, 256, &ptr))) return rc;
+    d.lut = static_cast<const uint8_t *>(ptr);
     const unsigned long long zero[4] = {0, 0, 0, 0};
-    if ((rc = dev_upload(ix, zero, sizeof(zero), &p))) return rc;
-    d.counters = const_cast<unsigned long long *>(static_cast<const unsigned long long *>(p));
+    if ((rc = dev_upload(ix, zero, sizeof(zero), &ptr))) return rc;
+    d.counters = const_cast<unsigned long long *>(static_cast<const unsigned long long *>(ptr));
     if (h.has_ma) {
         VStage vs("markers");
         if ((rc = upload_markers(ix))) return rc;
     }
     ix->cfg.block_threads = static_cast<int>(g_opt_block_threads.load());
-    ix->cfg.max_blocks = prop.multiProcessorCount * 32;
-    // ftab (next-row f3): built last, with the finished replica, by searching every word on the GPU
+    ix->cfg.max_blocks = p.compute_units * 32;
+    return RBG_OK;
+}
+
+// ftab (next-row f3): built last, with the finished replica, by searching every word on the GPU
+int build_ftab(rbg_index *ix) {
+    const HostIndex &h = ix->H();
+    DevIndex &d = ix->dev;
     d.ftab = nullptr;
     d.ftab_k = 0;
     int64_t fk = g_opt_ftab_k.load();
-    if (fk < 0) {  // automatic: the longest word <= 12 with nmajor^k <= n/16 (4^12 words x 16 B = 268 MB; DESIGN.md 4 on why not longer)
-        fk = 0;
-        double w = 1;
-        while (d.nmajor >= 2 && fk < 12 && w * d.nmajor <= static_cast<double>(h.n) / 16) { w *= d.nmajor; ++fk; }
-    }
-    if (fk > 0 && d.nmajor >= 2) {
-        VStage vs("ftab");
-        double words = 1;
-        for (int64_t t = 0; t < fk; ++t) words *= d.nmajor;
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        // the table plus the scratch of building it (in chunks) must leave half of the free memory to the queries
-        const size_t entry = h.pos_bytes == 4 ? 16 : 32;
-        if (words < 4.0e9 &&
-            words * static_cast<double>(entry) + static_cast<double>(ftab_build_scratch_bytes(static_cast<uint64_t>(words), static_cast<uint32_t>(fk))) <
-                0.5 * static_cast<double>(free_b)) {
-            const uint64_t W = static_cast<uint64_t>(words);
-            void *tab = nullptr;
-            HIP_TRY(hipMalloc(&tab, W * entry));
-            ix->allocs.push_back({tab, static_cast<size_t>(W * entry)});
-            ix->hbm_bytes += W * entry;
-            if (launch_build_ftab(d, ix->cfg, static_cast<uint32_t>(fk), tab, nullptr)) return RBG_ENODEV;
-            d.ftab = tab;
-            d.ftab_k = static_cast<uint32_t>(fk);
-            HIP_TRY(hipMemset(d.counters, 0, 4 * sizeof(uint64_t)));  // the build's own searches are not user queries
-        }
-    }
-    // jump table (rbg_jump.h, k_jump.hip): built after the ftab and after every decision above -- the lowest priority of the budget, so the
-    // layout is the one the replica has without it (rbg_layout_info identical).  What the budget leaves holds the table or nothing.
+    if (fk < 0) fk = auto_ftab_k(d.nmajor, h.n);
+    if (fk <= 0 || d.nmajor < 2) return RBG_OK;
+    VStage vs("ftab");
+    const double words = ftab_words(d.nmajor, fk);
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    const size_t entry = ftab_entry_bytes(h.pos_bytes);
+    if (!ftab_fits(words, entry, words < 4.0e9 ? ftab_build_scratch_bytes(static_cast<uint64_t>(words), static_cast<uint32_t>(fk)) : 0, free_b)) return RBG_OK;
+    const uint64_t W = static_cast<uint64_t>(words);
+    void *tab = nullptr;
+    HIP_TRY(hipMalloc(&tab, W * entry));
+    ix->allocs.push_back({tab, static_cast<size_t>(W * entry)});
+    ix->hbm_bytes += W * entry;
+    if (launch_build_ftab(d, ix->cfg, static_cast<uint32_t>(fk), tab, nullptr)) return RBG_ENODEV;
+    d.ftab = tab;
+    d.ftab_k = static_cast<uint32_t>(fk);
+    HIP_TRY(hipMemset(d.counters, 0, 4 * sizeof(uint64_t)));  // the build's own searches are not user queries
+    return RBG_OK;
+}
+
+// jump table (rbg_jump.h, k_jump.hip): built after the ftab and after every decision above -- the lowest priority of the budget, so the
+// layout is the one the replica has without it (rbg_layout_info identical).  What the budget leaves holds the table or nothing.
+int build_jump_table(rbg_index *ix) {
+    DevIndex &d = ix->dev;
     d.jump = nullptr;
     d.jump_buckets = 0;
     d.jump_k = 0;
     int64_t jk = g_opt_jump_k.load();
     const bool jump_auto = jk < 0;
-    if (jump_auto) jk = ix->hbm_bytes > kJumpAutoMinBytes ? kJumpDefaultK : 0;
-    if (jk > 0) {
-        VStage vs("jump table");
-        const auto t0 = std::chrono::steady_clock::now();
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        // what the HBM budget leaves after the replica holds the build at its peak (scratch + table), and at most half of the free memory
-        const uint64_t budget = ix->hbm_budget;
-        const uint64_t room = budget > ix->hbm_bytes ? budget - ix->hbm_bytes : 0;
-        const uint64_t peak_budget = std::min<uint64_t>(room, free_b / 2);
-        uint64_t table_budget = std::min<uint64_t>(room, free_b / 4);
-        // (by default the table may add at most half of the replica: on a text of few repeats -- nearly every K-mer distinct -- it would
-        //  outgrow the index it serves; the bench index's is a third)
-        if (jump_auto) table_budget = std::min<uint64_t>(table_budget, ix->hbm_bytes / 2);
-        void *tab = nullptr;
-        uint64_t bytes = 0, nb = 0, keys = 0;
-        const char *why = nullptr;
-        int rc = launch_build_jump(d, ix->cfg, static_cast<uint32_t>(jk), table_budget, peak_budget, &tab, &bytes, &nb, &keys, &why, nullptr);
-        if (rc == static_cast<int>(hipErrorOutOfMemory)) { (void)hipGetLastError(); rc = 0; why = "out of device memory while building it"; }
-        if (rc) return RBG_ENODEV;
-        HIP_TRY(hipMemset(d.counters, 0, 4 * sizeof(uint64_t)));  // (the build's own searches are not user queries)
-        ix->jump_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        if (tab) {
-            ix->allocs.push_back({tab, static_cast<size_t>(bytes)});
-            ix->hbm_bytes += bytes;
-            d.jump = tab;
-            d.jump_buckets = nb;
-            d.jump_k = static_cast<uint32_t>(jk);
-            ix->jump_k = static_cast<uint64_t>(jk);
-            ix->jump_keys = keys;
-            ix->jump_bytes = bytes;
-            ix->jump_buckets = nb;
-            if (std::getenv("RBG_VERBOSE"))
-                std::fprintf(stderr, "rbg: device %d: jump table of %lld-mers: %llu keys, %.2f GB, %.0f ms\n", ix->device, static_cast<long long>(jk),
-                             static_cast<unsigned long long>(keys), bytes / 1e9, ix->jump_build_ms);
-        } else if (std::getenv("RBG_VERBOSE")) {
-            std::fprintf(stderr, "rbg: device %d: no jump table of %lld-mers (%llu occur): %s\n", ix->device, static_cast<long long>(jk),
-                         static_cast<unsigned long long>(keys), why ? why : "skipped");
-        }
+    if (jump_auto) jk = auto_jump_k(ix->hbm_bytes);
+    if (jk <= 0) return RBG_OK;
+    VStage vs("jump table");
+    const auto t0 = std::chrono::steady_clock::now();
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    const JumpBudgets jb = jump_budgets(ix->hbm_budget, ix->hbm_bytes, free_b, jump_auto);
+    void *tab = nullptr;
+    uint64_t bytes = 0, nb = 0, keys = 0;
+    const char *why = nullptr;
+    int rc = launch_build_jump(d, ix->cfg, static_cast<uint32_t>(jk), jb.table_budget, jb.peak_budget, &tab, &bytes, &nb, &keys, &why, nullptr);
+    if (rc == static_cast<int>(hipErrorOutOfMemory)) { (void)hipGetLastError(); rc = 0; why = "out of device memory while building it"; }
+    if (rc) return RBG_ENODEV;
+    HIP_TRY(hipMemset(d.counters, 0, 4 * sizeof(uint64_t)));  // (the build's own searches are not user queries)
+    ix->jump_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (tab) {
+        ix->allocs.push_back({tab, static_cast<size_t>(bytes)});
+        ix->hbm_bytes += bytes;
+        d.jump = tab;
+        d.jump_buckets = nb;
+        d.jump_k = static_cast<uint32_t>(jk);
+        ix->jump_k = static_cast<uint64_t>(jk);
+        ix->jump_keys = keys;
+        ix->jump_bytes = bytes;
+        ix->jump_buckets = nb;
+        if (std::getenv("RBG_VERBOSE"))
+            std::fprintf(stderr, "rbg: device %d: jump table of %lld-mers: %llu keys, %.2f GB, %.0f ms\n", ix->device, static_cast<long long>(jk),
+                         static_cast<unsigned long long>(keys), bytes / 1e9, ix->jump_build_ms);
+    } else if (std::getenv("RBG_VERBOSE")) {
+        std::fprintf(stderr, "rbg: device %d: no jump table of %lld-mers (%llu occur): %s\n", ix->device, static_cast<long long>(jk),
+                     static_cast<unsigned long long>(keys), why ? why : "skipped");
     }
     return RBG_OK;
+}
+
+// A load, step by step: each step is one of the functions above, the rules they apply are rbg_load_plan.hpp's.
+int upload(rbg_index *ix) {
+    LoadPlan p;
+    int rc = check_device(ix, p);
+    if (rc) return rc;
+    DeviceScope scope(ix->device);
+    if (scope.rc) return scope.rc;
+    if ((rc = compose_if_deferred(ix))) return rc;
+    if ((rc = fix_budget(ix, p))) return rc;
+    decide_layout(ix, p);
+    if ((rc = second_look_at_layout(ix, p))) return rc;
+    settle_layout(ix, p);
+    if (p.runs_layout) trim_run_levels(ix, p);
+    ix->kmer_steps_requested = std::max<uint64_t>(ix->kmer_steps_requested, static_cast<uint64_t>(levels_of(ix->H())));  // options_for() may have capped the depth already
+    ix->hbm_free_at_load = p.free_b;
+    ix->hbm_budget = p.budget;
+    if (!p.runs_layout) trim_slot_levels(ix, p);
+    say_what_is_kept(ix, p);
+    if ((rc = upload_layout_tables(ix, p))) return rc;
+    if ((rc = upload_small_arrays(ix, p))) return rc;
+    if ((rc = build_ftab(ix))) return rc;
+    return build_jump_table(ix);
 }
 
 FlattenOptions current_options() {
@@ -326,18 +349,83 @@ FlattenOptions current_options() {
     return o;
 }
 
-// The options of a load that is going to `device`: k-mer levels that cannot fit the replica budget even in their
-// smallest form (every table at the widest bucket, kMaxWideShift) are not composed at all -- upload() would drop them
-// anyway, and composing the deepest level is the most expensive part of flatten() (47 of 76 s at n = 5e10).  The bound
-// is conservative: a level upload() could keep is never excluded.  *requested = the depth asked for when it was
-// capped here (else 0: upload() reports what flatten() composed).
 // the k-mer tables of an index that goes to a device are composed there (RBG_HOST_COMPOSE=1: on the host, the reference
 // statement -- A/B measurements and the test that compares the two)
-bool compose_deferred(int device) {
+bool host_compose_asked() {
     const char *e = std::getenv("RBG_HOST_COMPOSE");
-    return device != RBG_DEVICE_NONE && !(e && e[0] == '1');
+    return e && e[0] == '1';
+}
+bool compose_deferred(int device) { return device != RBG_DEVICE_NONE && !host_compose_asked(); }
+
+// The free HBM and the budget a load to `device` plans with, fixed while nothing of it is on the device (upload() measures again after the composition has
+// taken its share, and a quarter of what is left then is not a quarter of the device): false where the device cannot be asked.
+struct PlanMemory {
+    size_t free_b = 0, whole_b = 0;   // whole_b: the device's memory (the assumed free memory where RBG_ASSUME_FREE_HBM_MB is set)
+    int64_t opt_mb = 0;
+    double budget = 0;
+};
+bool plan_memory(int device, PlanMemory &m) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return false;
+    DeviceScope scope(device);
+    if (scope.rc) return false;
+    size_t total_b = 0;
+    if (hipMemGetInfo(&m.free_b, &total_b) != hipSuccess) return false;
+    const AssumedFree assumed = assumed_free_env();
+    m.free_b = assumed_free_hbm(m.free_b, assumed.mb);
+    m.whole_b = assumed.given ? m.free_b : total_b;
+    m.opt_mb = g_opt_hbm_budget_mb.load();
+    m.budget = static_cast<double>(load_budget(m.free_b, m.opt_mb, /*plan_budget=*/0));
+    return true;
 }
 
+// Not even the single-symbol slot tables fit: the run-indexed layout, certainly (where the alphabet allows it) -- and RBG_LAYOUT_AUTO with no budget
+// given may raise the budget for it (rbg_load_plan.hpp budget_raise): said on stderr, reported by rbg_info (hbm_budget) and rbg_layout_info
+// (budget_raised); RBG_OPT_HBM_BUDGET_MB decides otherwise.
+void plan_runs_of_a_large_index(int device, const RawRle &rle, const FlattenOptions &o, unsigned sigma, const PlanMemory &m, bool *auto_runs, rbg_index *ix) {
+    if (sigma > static_cast<unsigned>(kLdsSyms)) return;
+    *auto_runs = true;
+    const double r = static_cast<double>(rle.heads.size());
+    const BudgetRaise b = budget_raise(r, o.kmer_steps, m.free_b, m.whole_b, m.opt_mb, g_opt_rank_layout.load(), m.budget);
+    if (!b.raise) return;
+    std::fprintf(stderr, "rbg: device %d: r = %.3g runs: a quarter of the free HBM (%.1f GB) would leave fewer than %u symbols per step; RBG_LAYOUT_AUTO takes up to "
+                         "three quarters (%.1f GB) for this index (RBG_OPT_HBM_BUDGET_MB sets the budget explicitly)\n", device, r, m.budget / 1e9, b.want, b.raised / 1e9);
+    ix->plan_budget = static_cast<uint64_t>(b.raised);
+    ix->budget_raised = true;
+}
+
+// The slot layout stages the tables of at most kMaxSlotKmerDepth symbols per gather (more are asked of the run-indexed layout only).  Levels that cannot
+// fit the budget even in their smallest form (every table at the widest bucket) are not composed at all -- upload() would drop them anyway, and composing
+// the deepest level is the most expensive part of flatten() (47 of 76 s at n = 5e10).  The bound is conservative: a level upload() could keep is never excluded.
+void plan_slot_levels(int device, const RawRle &rle, FlattenOptions &o, unsigned sigma, double major, double budget, uint64_t *requested, bool *auto_runs) {
+    const LoadConsts consts = load_consts();
+    const int slot_steps = std::min(o.kmer_steps, kMaxSlotKmerDepth);
+    const int keep = slot_levels_fitting(rle.n, major, slot_steps, kMaxWideShift, budget, consts);
+    if (g_opt_rank_layout.load() == RBG_LAYOUT_AUTO && sigma <= static_cast<unsigned>(kLdsSyms) &&
+        slot_levels_fitting(rle.n, major, slot_steps, kMaxNarrowShift, budget, consts) < slot_steps && runs_layout_fits(rle.heads.size(), budget)) {
+        // RBG_LAYOUT_AUTO: slot tables only while those of every symbol per step fit the budget at their narrow buckets; rather than give up
+        // symbols per step -- or widen the buckets -- the run-indexed layout (all of them, in space proportional to r; deeper steps than the
+        // slot layout has: RBG_OPT_KMER_STEPS up to 8).  On the bench index 1.26e9 reads/s from 8.7 GB against 1.18e9 from the 59 GB of four
+        // symbols per step (profiles/r04_bench.json space_speed); about 110 bytes per run at its leanest.
+        if (std::getenv("RBG_VERBOSE"))
+            std::fprintf(stderr, "rbg: device %d: the slot tables of %d symbols per step exceed the %.1f GB replica budget at narrow buckets: the run-indexed layout "
+                                 "instead, %d symbols per step (RBG_OPT_RANK_LAYOUT = RBG_LAYOUT_PREFER_SLOTS keeps slot tables with fewer symbols)\n", device, slot_steps,
+                         budget / 1e9, o.kmer_steps);
+        *auto_runs = true;
+        return;
+    }
+    if (keep >= o.kmer_steps) return;
+    if (keep < slot_steps) {
+        if (std::getenv("RBG_VERBOSE"))
+            std::fprintf(stderr, "rbg: device %d: %.1f GB replica budget cannot hold k-mer levels beyond %d at n = %.3g: not composing them\n", device,
+                         budget / 1e9, keep, static_cast<double>(rle.n));
+        *requested = static_cast<uint64_t>(slot_steps);   // (what the slot layout could have taken of the depth asked for)
+    }
+    o.kmer_steps = keep;   // (the slot layout: at most kMaxSlotKmerDepth symbols per gather)
+}
+
+// The options of a load that is going to `device`.  *requested = the depth asked for when it was capped here (else 0: upload() reports what flatten()
+// composed); *auto_runs: RBG_LAYOUT_AUTO chose the run-indexed layout already.
 FlattenOptions options_for(int device, const RawRle &rle, uint64_t *requested, bool *auto_runs, rbg_index *ix) {
     FlattenOptions o = current_options();
     *requested = 0;
@@ -346,24 +434,14 @@ FlattenOptions options_for(int device, const RawRle &rle, uint64_t *requested, b
     // tables there: compose none (eight depths on the host cost 3 GB and a second per 3e6 runs, hundreds of GB at pangenome r: ADVICE r5).
     // (RBG_HOST_COMPOSE=1 keeps the host composition -- the serial reference statement of k_compose.hip -- reachable without a device: tests)
     if (device == RBG_DEVICE_NONE) {
-        const char *e = std::getenv("RBG_HOST_COMPOSE");
-        if (!(e && e[0] == '1')) o.kmer_steps = 1;
+        if (!host_compose_asked()) o.kmer_steps = 1;
         return o;
     }
     if (o.kmer_steps < 2) return o;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return o;
-    DeviceScope scope(device);
-    if (scope.rc) return o;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return o;
-    free_b = assumed_free_hbm(free_b);
-    const int64_t opt_mb = g_opt_hbm_budget_mb.load();
-    double budget = static_cast<double>(opt_mb > 0 ? static_cast<size_t>(opt_mb) << 20 : default_budget(free_b));
-    // (the budget of this load is fixed HERE, while nothing of it is on the device: upload() measures again after the composition has
-    //  taken its share, and a quarter of what is left then is not a quarter of the device)
-    ix->plan_free = free_b;
-    ix->plan_budget = static_cast<uint64_t>(budget);
+    PlanMemory m;
+    if (!plan_memory(device, m)) return o;
+    ix->plan_free = m.free_b;
+    ix->plan_budget = static_cast<uint64_t>(m.budget);
     bool seen[256] = {};
     unsigned sigma = 0;
     for (uint8_t c : rle.heads)
@@ -373,79 +451,12 @@ FlattenOptions options_for(int device, const RawRle &rle, uint64_t *requested, b
     // the run-indexed layout keeps its k-mer depths as run lists (space proportional to r): nothing to cap when it is
     // asked for, or when not even the single-symbol slot tables (+ phi at its widest usual bucket) fit
     if (g_opt_rank_layout.load() == RBG_LAYOUT_RUNS) return o;
-    if (layout_automatic()) {
-        const double pos = (o.force_pos_bytes == 8 || rle.n >= 0xFFFFFFF0ull) ? 8 : 4;
-        const double lvl1 = static_cast<double>(sigma) * static_cast<double>((rle.n >> kMaxNarrowShift) + 2) * (sizeof(RankSlot) + sizeof(uint32_t)) +
-                            static_cast<double>((rle.n >> 6) + 2) * (4 * pos + 4);
-        if (lvl1 > budget) {
-            // not even the single-symbol slot tables fit: the run-indexed layout, certainly (where the alphabet allows it)
-            if (sigma <= static_cast<unsigned>(kLdsSyms)) {
-                *auto_runs = true;
-                // An index that large may also be too large for the DEFAULT budget to step by more than a symbol or two (r = 1e9: 36 GB of run lists
-                // and phi before any k-mer depth; profiles/r05_pangenome_stream_r1e9_default.json: 5e7 reads/s from the quarter, 1.4e8 from the fast
-                // form).  RBG_LAYOUT_AUTO with no budget given then takes up to three quarters of the free HBM -- said on stderr, reported by
-                // rbg_info (hbm_budget) and rbg_layout_info (budget_raised); RBG_OPT_HBM_BUDGET_MB decides otherwise.
-                const double r = static_cast<double>(rle.heads.size());
-                const uint32_t want = static_cast<uint32_t>(std::min(o.kmer_steps, 4));
-                // ... and only on a device this load has (almost) to itself: with a tenth of it or more already taken -- the caller's own buffers,
-                // another replica, another process -- the quarter stays (a caller that sized its buffers around the quarter rule).
-                const size_t whole = std::getenv("RBG_ASSUME_FREE_HBM_MB") ? free_b : total_b;
-                const bool device_to_itself = static_cast<double>(free_b) >= 0.9 * static_cast<double>(whole);
-                if (opt_mb == 0 && g_opt_rank_layout.load() == RBG_LAYOUT_AUTO && device_to_itself &&
-                    planned_depth(r, true, static_cast<uint32_t>(o.kmer_steps), static_cast<double>(free_b), budget, true) < want) {
-                    const double raised = 0.75 * static_cast<double>(free_b);
-                    if (planned_depth(r, true, static_cast<uint32_t>(o.kmer_steps), static_cast<double>(free_b), raised, true) >
-                        planned_depth(r, true, static_cast<uint32_t>(o.kmer_steps), static_cast<double>(free_b), budget, true)) {
-                        std::fprintf(stderr, "rbg: device %d: r = %.3g runs: a quarter of the free HBM (%.1f GB) would leave fewer than %u symbols per step; RBG_LAYOUT_AUTO takes up to "
-                                             "three quarters (%.1f GB) for this index (RBG_OPT_HBM_BUDGET_MB sets the budget explicitly)\n", device, r, budget / 1e9, want, raised / 1e9);
-                        budget = raised;
-                        ix->plan_budget = static_cast<uint64_t>(budget);
-                        ix->budget_raised = true;
-                    }
-                }
-            }
-            return o;
-        }
+    const uint32_t pos_bytes = (o.force_pos_bytes == 8 || rle.n >= 0xFFFFFFF0ull) ? 8 : 4;
+    if (layout_automatic() && slot_level1_estimate(rle.n, sigma, pos_bytes, load_consts()) > m.budget) {
+        plan_runs_of_a_large_index(device, rle, o, sigma, m, auto_runs, ix);
+        return o;
     }
-    // the slot layout stages the tables of at most kMaxSlotKmerDepth symbols per gather: more are asked of the run-indexed layout only
-    const int slot_steps = std::min(o.kmer_steps, kMaxSlotKmerDepth);
-    auto slot_levels_fitting = [&](uint32_t shift) {   // the deepest level whose slot tables (every table at this bucket shift) fit the budget with the levels above it
-        const double per_table = static_cast<double>((rle.n >> shift) + 2) * (sizeof(RankSlot) + sizeof(uint32_t));
-        double total = major * per_table, tables = major;
-        int keep = 1;
-        for (int k = 2; k <= slot_steps; ++k) {
-            tables *= major;
-            total += tables * per_table;
-            if (total > budget) break;
-            keep = k;
-        }
-        return keep;
-    };
-    const int keep = slot_levels_fitting(kMaxWideShift);   // conservative: a level upload() could keep is never excluded
-    if (g_opt_rank_layout.load() == RBG_LAYOUT_AUTO && sigma <= static_cast<unsigned>(kLdsSyms) && slot_levels_fitting(kMaxNarrowShift) < slot_steps) {
-        // RBG_LAYOUT_AUTO: slot tables only while those of every symbol per step fit the budget at their narrow buckets; rather than give up
-        // symbols per step -- or widen the buckets -- the run-indexed layout (all of them, in space proportional to r; deeper steps than the
-        // slot layout has: RBG_OPT_KMER_STEPS up to 8).  On the bench index 1.26e9 reads/s from 8.7 GB against 1.18e9 from the 59 GB of four
-        // symbols per step (profiles/r04_bench.json space_speed); about 110 bytes per run at its leanest.
-        const double runs_least = 110.0 * static_cast<double>(rle.heads.size());
-        if (runs_least <= budget) {
-            if (std::getenv("RBG_VERBOSE"))
-                std::fprintf(stderr, "rbg: device %d: the slot tables of %d symbols per step exceed the %.1f GB replica budget at narrow buckets: the run-indexed layout "
-                                     "instead, %d symbols per step (RBG_OPT_RANK_LAYOUT = RBG_LAYOUT_PREFER_SLOTS keeps slot tables with fewer symbols)\n", device, slot_steps,
-                             budget / 1e9, o.kmer_steps);
-            *auto_runs = true;
-            return o;
-        }
-    }
-    if (keep < o.kmer_steps) {
-        if (keep < slot_steps) {
-            if (std::getenv("RBG_VERBOSE"))
-                std::fprintf(stderr, "rbg: device %d: %.1f GB replica budget cannot hold k-mer levels beyond %d at n = %.3g: not composing them\n", device,
-                             budget / 1e9, keep, static_cast<double>(rle.n));
-            *requested = static_cast<uint64_t>(slot_steps);   // (what the slot layout could have taken of the depth asked for)
-        }
-        o.kmer_steps = keep;   // (the slot layout: at most kMaxSlotKmerDepth symbols per gather)
-    }
+    plan_slot_levels(device, rle, o, sigma, major, m.budget, requested, auto_runs);
     return o;
 }
 

@@ -113,50 +113,9 @@ int upload_tables_runs2(rbg_index *ix) {
     // bucket; the one before them is held too).
     const char *e_rp = std::getenv("RBG_RUN_REC_PER");
     const double rec_asked = e_rp && std::atof(e_rp) > 0 ? std::atof(e_rp) : 0.0;
-    // PER DEPTH, deepest first (a search spends its steps at the deepest depth; the shallower ones take a read's ragged ends): rec_per[d] =
-    // entries per bucket on average of depth d's records, 0 = directories.  RBG_OPT_RUN_REC = 2: the depths of RBG_OPT_RUN_REC_DEPTHS
-    // (0 = all kept) at RBG_RUN_REC_PER (2.5).  Automatic: each depth in turn gets the narrowest buckets -- 2.5, 4 or 6 entries (a compact
-    // record holds eleven) -- with which the replica (phi slots included) stays within the budget and the records stay O(r) (at most one per entry).
-    std::vector<double> rec_per(D, 0.0);
-    auto records_of = [&](uint32_t d, double per) { return runs_record_count(h, d, per, max_shift); };
-    if (g_opt_run_rec.load() == 2) {
-        const uint32_t want = g_opt_run_rec_depths.load() ? static_cast<uint32_t>(g_opt_run_rec_depths.load()) : ~0u;
-        for (uint32_t d = 0; d < D; ++d)
-            if ((mask >> d & 1u) && (want >> d & 1u)) rec_per[d] = rec_asked > 0 ? rec_asked : 2.5;
-    } else if (g_opt_run_rec.load() == 0 && ix->hbm_budget) {
-        double total = static_cast<double>(W ? runs_replica_bytes<uint64_t>(h, mask) : runs_replica_bytes<uint32_t>(h, mask));
-        if (g_opt_run_phi.load() != 1) total += runs_phi_slot_bytes(h);   // phi slots come first (decided after the rank tables, below: the same arithmetic): their room is not the records'
-        const double budget = static_cast<double>(ix->hbm_budget);
-        const double pers[3] = {2.5, 4.0, 6.0};
-        // room at the widest buckets (6 entries) for EVERY kept depth?  Then every depth gets records -- a depth left on directories pays narrowing rounds on
-        // its steps -- and a depth takes narrower buckets only with what the shallower ones do not need.  Otherwise: deepest first, while they fit.
-        std::vector<double> widest(D, 0.0), entries(D, 0.0);
-        double all_widest = 0;
-        bool every = true;
-        for (uint32_t d = 0; d < D; ++d) {
-            if (!(mask >> d & 1u)) continue;
-            for (const SymTable &t : *depth[d]) entries[d] += static_cast<double>(t.nruns + 1);
-            widest[d] = records_of(d, rec_asked > 0 ? rec_asked : pers[2]) * 64.0;
-            all_widest += widest[d];
-            every = every && widest[d] <= entries[d] * 64.0;
-        }
-        every = every && total + all_widest <= budget;
-        double shallower_widest = all_widest;
-        for (int d = static_cast<int>(D) - 1; d >= 0; --d) {
-            if (!(mask >> d & 1u)) continue;
-            shallower_widest -= widest[d];
-            for (const double per : pers) {
-                if (rec_asked > 0 && per != pers[0]) break;
-                const double use = rec_asked > 0 ? rec_asked : per;
-                const double bytes = records_of(static_cast<uint32_t>(d), use) * 64.0;
-                if (bytes <= entries[d] * 64.0 && total + bytes + (every ? shallower_widest : 0.0) <= budget) {
-                    rec_per[d] = use;
-                    total += bytes;
-                    break;
-                }
-            }
-        }
-    }
+    // rec_per[d] = entries per bucket on average of depth d's records, 0 = directories (rbg_load_plan.hpp run_record_plan: per depth, deepest first)
+    const std::vector<double> rec_per = run_record_plan(shape_of(h), load_consts(), mask, D, ix->hbm_budget, g_opt_run_rec.load(), g_opt_run_rec_depths.load(), rec_asked,
+                                                        max_shift, g_opt_run_phi.load());
     bool any_recs = false, all_recs = true;
     for (uint32_t d = 0; d < D; ++d)
         if (mask >> d & 1u) { any_recs = any_recs || rec_per[d] > 0; all_recs = all_recs && rec_per[d] > 0; }
@@ -706,11 +665,9 @@ int compose_on_device(rbg_index *ix) {
     {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            free_b = assumed_free_hbm(free_b);
-            const int64_t opt_mb = g_opt_hbm_budget_mb.load();
-            const double budget = ix->plan_budget ? static_cast<double>(ix->plan_budget) : static_cast<double>(opt_mb > 0 ? static_cast<size_t>(opt_mb) << 20 : default_budget(free_b));
-            const bool runs_certain = g_opt_rank_layout.load() == RBG_LAYOUT_RUNS || ix->auto_runs;
-            K_plan = planned_depth(static_cast<double>(h.r), h.has_tsa, K0, static_cast<double>(free_b), budget, runs_certain);
+            free_b = assumed_free_hbm(free_b, assumed_free_env().mb);
+            const double budget = static_cast<double>(load_budget(free_b, g_opt_hbm_budget_mb.load(), ix->plan_budget));
+            K_plan = planned_depth(static_cast<double>(h.r), h.has_tsa, K0, static_cast<double>(free_b), budget, runs_certain(g_opt_rank_layout.load(), ix->auto_runs));
             if (K_plan < K0)
                 std::fprintf(stderr, "rbg: r = %.3g runs, %.1f GB free, %.1f GB replica budget: composing %u symbol(s) per step, not the %u asked for (estimated: depth %u would "
                                      "hold about %.3g runs; RBG_OPT_HBM_BUDGET_MB / RBG_OPT_RUN_DEPTHS change what fits)\n", static_cast<double>(h.r), free_b / 1e9, budget / 1e9,
@@ -786,21 +743,15 @@ int compose_on_device_k(rbg_index *ix, const uint32_t K) {
     // options_for makes) the depths its depth set leaves out give their arrays back as soon as the next depth is made.
     uint32_t keep_mask = 0;
     {
-        bool runs_certain = g_opt_rank_layout.load() == RBG_LAYOUT_RUNS || ix->auto_runs;
-        if (!runs_certain && layout_automatic()) {
+        bool certain = runs_certain(g_opt_rank_layout.load(), ix->auto_runs);
+        if (!certain && layout_automatic()) {
             size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                const int64_t opt_mb = g_opt_hbm_budget_mb.load();
-                const double budget = static_cast<double>(opt_mb > 0 ? static_cast<size_t>(opt_mb) << 20 : default_budget(free_b));
-                const double lvl1 = static_cast<double>(h.sigma) * static_cast<double>((h.n >> kMaxNarrowShift) + 2) * (sizeof(RankSlot) + sizeof(uint32_t)) +
-                                    static_cast<double>((h.n >> 6) + 2) * (4.0 * sizeof(P) + 4);
-                runs_certain = lvl1 > budget;
-            }
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+                // THIS budget differs from the load's (upload(), options_for(), compose_on_device above): the free memory as it is now, no budget planned
+                // before the load and no RBG_ASSUME_FREE_HBM_MB cap.  Whether it should is undecided; the rules were moved, not changed.
+                certain = slot_level1_estimate(h.n, h.sigma, sizeof(P), load_consts()) > static_cast<double>(load_budget(free_b, g_opt_hbm_budget_mb.load(), /*plan_budget=*/0));
         }
-        if (runs_certain && h.sigma <= static_cast<uint32_t>(kLdsSyms)) {
-            keep_mask = g_opt_run_depths.load() ? static_cast<uint32_t>(g_opt_run_depths.load()) | 1u : default_depth_mask(K);
-            keep_mask |= 1u << (K - 1);
-        }
+        if (certain && h.sigma <= static_cast<uint32_t>(kLdsSyms)) keep_mask = asked_depth_mask(g_opt_run_depths.load(), K) | 1u << (K - 1);
     }
     // (with the run-indexed layout certain, the composition also frees its inputs as soon as they have been read: nothing
     //  after it needs the depth-1 lists in this form -- upload_tables_runs2 builds depth 1 from the host tables)

@@ -21,7 +21,7 @@ ALL = ra.LoadRbwtFlag.SA | ra.LoadRbwtFlag.MA
 
 
 def default_depth_mask(K):
-    """rbg_capi.hip default_depth_mask: the deepest depth, half of it, a quarter of it ... and 1"""
+    """rbg_load_plan.hpp default_depth_mask: the deepest depth, half of it, a quarter of it ... and 1"""
     m, d = 1, K
     while d >= 1:
         m |= 1 << (d - 1)
