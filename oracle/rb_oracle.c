@@ -1216,3 +1216,11 @@ void orc_locs_at_batch(const orc_index *x, const uint64_t *lo, const uint64_t *h
     for (int64_t i = 0; i < (int64_t)N; ++i)
         orc_locs_at(x, lo[i], hi[i], k[i], max_hits, locs + loc_off[i]);
 }
+
+void orc_LF_batch(const orc_index *x, const uint64_t *lo, const uint64_t *hi, const uint8_t *c, uint64_t N,
+                  uint64_t *lo_out, uint64_t *hi_out, int nthreads) {
+    if (nthreads < 1) nthreads = 1;
+#pragma omp parallel for schedule(dynamic, 4096) num_threads(nthreads)
+    for (int64_t i = 0; i < (int64_t)N; ++i)
+        orc_LF(x, lo[i], hi[i], c[i], &lo_out[i], &hi_out[i]);
+}

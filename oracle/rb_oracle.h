@@ -122,6 +122,9 @@ void orc_find_range_w_toehold_batch(const orc_index *, const uint8_t *seqs, cons
 /* two-pass variable-length locate: loc_off[N+1] must already hold the exclusive scan of min(occ,max_hits) */
 void orc_locs_at_batch(const orc_index *, const uint64_t *lo, const uint64_t *hi, const uint64_t *k, uint64_t N,
                        uint64_t max_hits, const uint64_t *loc_off, uint64_t *locs, int nthreads);
+/* orc_LF for N triples {lo, hi, c} */
+void orc_LF_batch(const orc_index *, const uint64_t *lo, const uint64_t *hi, const uint8_t *c, uint64_t N,
+                  uint64_t *lo_out, uint64_t *hi_out, int nthreads);
 
 #ifdef __cplusplus
 }

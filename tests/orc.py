@@ -70,6 +70,7 @@ def lib():
         L.orc_find_range_batch.argtypes = [VP, VP, VP, U64, VP, VP, C.c_int]
         L.orc_find_range_w_toehold_batch.argtypes = [VP, VP, VP, U64, VP, VP, VP, C.c_int]
         L.orc_locs_at_batch.argtypes = [VP, VP, VP, VP, U64, U64, VP, VP, C.c_int]
+        L.orc_LF_batch.argtypes = [VP, VP, VP, VP, U64, VP, VP, C.c_int]
         _lib = L
     return _lib
 
@@ -261,6 +262,13 @@ class Oracle:
         lo, hi, k = np.zeros(N, np.uint64), np.zeros(N, np.uint64), np.zeros(N, np.uint64)
         self.L.orc_find_range_w_toehold_batch(self.h, _p(seqs), _p(off), N, _p(lo), _p(hi), _p(k), nthreads)
         return lo, hi, k
+
+    def LF_batch(self, lo, hi, c, nthreads=1):
+        lo, hi = np.ascontiguousarray(lo, dtype=np.uint64), np.ascontiguousarray(hi, dtype=np.uint64)
+        c = np.ascontiguousarray(c, dtype=np.uint8)
+        nlo, nhi = np.zeros(len(lo), np.uint64), np.zeros(len(lo), np.uint64)
+        self.L.orc_LF_batch(self.h, _p(lo), _p(hi), _p(c), len(lo), _p(nlo), _p(nhi), nthreads)
+        return nlo, nhi
 
     def locs_at_batch(self, lo, hi, k, max_hits=MAXU, nthreads=1):
         N = len(lo)
