@@ -32,15 +32,13 @@
 #include "fastx.hpp"
 #include "fastx_index.hpp"
 #include "cli_input.hpp"
-#include "rbg_thread_team.hpp"
+#include "cli_pipeline.hpp"
+#include "rbg_thread_team.hpp"   // cpu_budget()
 
 namespace {
 
-using rbg_cli::put_u64;
-using rbg_cli::RecordSpans;
-
+using rbg_cli::BatchView;
 using rbg_cli::InputSource;
-using rbg_cli::Window;
 
 struct RbAlignArgs {  // rb_align.cpp:17-24
     std::string inpre, fastq_fname, outpre;
@@ -155,16 +153,16 @@ bool device_text(const RbAlignArgs &args) {
     return args.sam && !off;
 }
 
-ShardError query_shard(rbg_index *ix, const RbAlignArgs &args, const Window &b, uint64_t begin, uint64_t end, BatchResult &r) {
+ShardError query_shard(rbg_index *ix, const RbAlignArgs &args, const BatchView &b, uint64_t begin, uint64_t end, BatchResult &r) {
     try {
         r.begin = begin;
         r.end = end;
         const uint64_t N = end - begin;
         if (N == 0) return {};
         // the sequences are read where the scanner found them (rbg_find_range_spans): no copy into a batch
-        const uint8_t *base = reinterpret_cast<const uint8_t *>(b.base);
-        const uint64_t *sb = b.recs.seq_begin.data() + begin;
-        const uint32_t *sl = b.recs.seq_len.data() + begin;
+        const uint8_t *base = reinterpret_cast<const uint8_t *>(b.w->base);
+        const uint64_t *sb = b.w->recs.seq_begin.data() + b.w0 + begin;
+        const uint32_t *sl = b.w->recs.seq_len.data() + b.w0 + begin;
         int rc;
         r.lo.resize(N); r.hi.resize(N);
         if (args.sam) {  // rb_get_range(sa=true), rb_align.cpp:99-103
@@ -172,8 +170,8 @@ ShardError query_shard(rbg_index *ix, const RbAlignArgs &args, const Window &b, 
             if ((rc = rbg_find_range_spans(ix, base, sb, sl, N, r.lo.data(), r.hi.data(), r.k.data()))) return {rc, "rbg_find_range_spans"};
             if (device_text(args)) {   // locations, documents and decimals on the device: the finished text comes back
                 r.text_owner = ix;
-                if ((rc = rbg_align_text(ix, r.lo.data(), r.hi.data(), r.k.data(), N, static_cast<uint64_t>(-1), args.markers ? RBG_TEXT_MARKERS : 0, b.base, b.recs.name_begin.data() + begin,
-                                         b.recs.name_len.data() + begin, &r.text, &r.text_len)))
+                if ((rc = rbg_align_text(ix, r.lo.data(), r.hi.data(), r.k.data(), N, static_cast<uint64_t>(-1), args.markers ? RBG_TEXT_MARKERS : 0, b.w->base, b.w->recs.name_begin.data() + b.w0 + begin,
+                                         b.w->recs.name_len.data() + b.w0 + begin, &r.text, &r.text_len)))
                     return {rc, "rbg_align_text"};
                 return {};
             }
@@ -207,16 +205,16 @@ struct DocView {
 } g_docs;
 
 // the text of rb_report (rb_align.cpp:118-145) for reads [i0, i1)
-void format_range(const rbwt::RowBowt<> &rb, const RbAlignArgs &args, const Window &b, const BatchResult &r, size_t g0,
+void format_range(const rbwt::RowBowt<> &rb, const RbAlignArgs &args, const BatchView &b, const BatchResult &r, size_t g0,
                   size_t g1, rbg_cli::TextBuf &out_s) {
     static const char kNoMarkers[] = "no markers (consider building the marker array with a larger window size)";
     FastOut out(out_s);
-    for (size_t gi = g0; gi < g1; ++gi) {   // gi: index in the window; i: index in the shard's results
+    for (size_t gi = g0; gi < g1; ++gi) {   // gi: index in the batch; i: index in the shard's results
         const size_t i = gi - r.begin;
-        const size_t nl = b.recs.name_len[gi];
+        const size_t nl = b.name_len(gi);
         char *p = out.room(nl + 96);
         char *const p0 = p;
-        p = fmt_lit(p, b.base + b.recs.name_begin[gi], nl);
+        p = fmt_lit(p, b.name(gi), nl);
         p = fmt_lit(p, " (", 2);
         p = fmt_u64(p, r.lo[i]);
         *p++ = ',';
@@ -273,8 +271,6 @@ std::shared_future<void> g_text_writer[2];   // device_text(): the last two of t
 
 // query + format one batch: the batch is sharded over the replicas (contiguous blocks), the shards are
 // queried concurrently, formatting is split over worker threads, pieces concatenated in read order
-// (`pieces` is a pool that keeps its strings -- and their pages -- from window to window: `used` counts the ones of this
-// window; fresh 12 MB strings per batch cost more in page faults than the formatting itself)
 // One batch in flight between the two stages: the shards' results (one BatchResult per replica, kept from batch to batch
 // like the pieces: the lo / hi / k arrays of a 4 M-read batch are 100 MB of pages)
 struct BatchSlot {
@@ -284,8 +280,8 @@ struct BatchSlot {
 };
 
 // stage 1: the batch is sharded over the replicas (contiguous blocks), the shards are queried concurrently
-void query_batch(const std::vector<rbg_index *> &reps, const RbAlignArgs &args, const Window &b, size_t w0, size_t w1, BatchSlot &slot) {
-    const size_t N = w1 - w0;
+void query_batch(const std::vector<rbg_index *> &reps, const RbAlignArgs &args, const BatchView &b, BatchSlot &slot) {
+    const size_t N = b.size();
     const int G = static_cast<int>(reps.size());
     while (slot.res.size() < static_cast<size_t>(G)) slot.res.emplace_back(new BatchResult());
     slot.err.assign(G, ShardError());
@@ -294,7 +290,7 @@ void query_batch(const std::vector<rbg_index *> &reps, const RbAlignArgs &args, 
     auto work = [&](int g) {
         uint64_t s0 = 0, s1 = 0;
         (void)rbg_shard_bounds(N, g, G, &s0, &s1);
-        slot.err[g] = query_shard(reps[g], args, b, w0 + s0, w0 + s1, *slot.res[g]);
+        slot.err[g] = query_shard(reps[g], args, b, s0, s1, *slot.res[g]);
     };
     for (int g = 1; g < G; ++g) th.emplace_back(work, g);
     work(0);
@@ -303,12 +299,8 @@ void query_batch(const std::vector<rbg_index *> &reps, const RbAlignArgs &args, 
 }
 
 // stage 2: formatting is split over worker threads, pieces concatenated in read order
-// (`pieces` is a pool that keeps its strings -- and their pages -- from window to window: `used` counts the ones of this
-// window; fresh 12 MB strings per batch cost more in page faults than the formatting itself)
 struct ShardFailure {};   // a replica's call failed (already reported): leave through main()
-void format_batch(const rbwt::RowBowt<> &rb, const RbAlignArgs &args, const Window &b, size_t w0, size_t w1, BatchSlot &slot,
-                  std::vector<rbg_cli::TextBuf> &pieces, size_t &used) {
-    const size_t N = w1 - w0;
+void format_batch(const rbwt::RowBowt<> &rb, const RbAlignArgs &args, const BatchView &b, BatchSlot &slot, rbg_cli::PiecePool &pool) {
     const int G = static_cast<int>(slot.err.size());
     for (int g = 0; g < G; ++g)
         if (slot.err[g].rc) {   // what the single-replica path says, from the main thread, once every worker is done
@@ -345,28 +337,11 @@ void format_batch(const rbwt::RowBowt<> &rb, const RbAlignArgs &args, const Wind
         }).share();
         return;
     }
-    const size_t T = std::max<size_t>(1, std::min<size_t>({static_cast<size_t>(args.threads), (N + 4095) / 4096, size_t(64)}));
-    // piece (g, t): reads of shard g, t-th slice
-    const size_t first_piece = used;
-    used += static_cast<size_t>(G) * T;
-    if (pieces.size() < used) pieces.resize(used);
-    for (size_t i = first_piece; i < used; ++i) pieces[i].clear();
-    std::vector<std::thread> workers;
-    for (int g = 0; g < G; ++g)
-        for (size_t t = 0; t < T; ++t) {
-            const size_t n = res(g).end - res(g).begin;
-            const size_t a = res(g).begin + n * t / T, z = res(g).begin + n * (t + 1) / T;
-            if (a == z) continue;
-            rbg_cli::TextBuf *dst = &pieces[first_piece + static_cast<size_t>(g) * T + t];
-            const BatchResult *r = &res(g);
-            if (g == 0 && t == 0) continue;  // done on this thread below
-            workers.emplace_back([&rb, &args, &b, r, a, z, dst] { format_range(rb, args, b, *r, a, z, *dst); });
-        }
-    {
-        const size_t n = res(0).end - res(0).begin;
-        format_range(rb, args, b, res(0), res(0).begin, res(0).begin + n / T, pieces[first_piece]);
-    }
-    for (auto &w : workers) w.join();
+    // piece (g, t): reads of shard g, t-th slice; all slices of all shards at once
+    const size_t T = rbg_cli::format_threads(b.size(), static_cast<size_t>(args.threads));
+    std::vector<std::pair<size_t, size_t>> ranges;
+    for (int g = 0; g < G; ++g) rbg_cli::add_slices(res(g).begin, res(g).end - res(g).begin, T, ranges);
+    rbg_cli::format_ranges(ranges, pool, [&](size_t k, size_t i0, size_t i1, rbg_cli::TextBuf &piece) { format_range(rb, args, b, res(k / T), i0, i1, piece); });
     // the text is made: the ragged buffers (3 GB of locations per 10 M reads on a pangenome index) go back now, the
     // fixed-size arrays stay for the next batch
     for (int g = 0; g < G; ++g) {
@@ -444,65 +419,23 @@ int main(int argc, char **argv) {
         for (rbg_index *r : once) (void)rbg_reserve_text(r, (args.batch / reps.size() + 1) * 1100 + (size_t(1) << 20), 4 * S);
     }
     start = std::chrono::high_resolution_clock::now();
-    // three overlapped stages: scan window i+1 | query + format window i (in GPU batches of --batch reads) | write window i-1
+    // the shared loop (cli_pipeline.hpp) in GPU batches of --batch reads: batch j + 1 is queried (library calls: packing, GPU,
+    // results back) while batch j is formatted -- with forty locations per read the text is four fifths of a batch's time
     int err = 0;
-    Window cur, nxt;
-    err = input.next(cur);
-    std::future<void> writer;
-    std::vector<rbg_cli::TextBuf> pieces, writing;
-    size_t used = 0, writing_used = 0;
     BatchSlot slots[2];
+    rbg_cli::PipelineBuffers bufs;
+    rbg_cli::PipelineStats waits;
     try {
-    while (true) {
-        std::future<int> scanner;
-        const bool more = err == 0;
-        if (more) scanner = std::async(std::launch::async, [&input, &nxt] { return input.next(nxt); });
-        used = 0;
-        // two stages over the window's batches: batch j + 1 is queried (library calls: packing, GPU, results back) while
-        // batch j is formatted -- with forty locations per read the text is four fifths of a batch's time
-        {
-            auto bounds = [&](size_t j, size_t &w0, size_t &w1) { w0 = j * args.batch; w1 = std::min<size_t>(cur.size(), w0 + args.batch); };
-            const size_t nb = (cur.size() + args.batch - 1) / args.batch;
-            std::future<void> ahead;
-            size_t a0 = 0, a1 = 0;
-            if (nb) { bounds(0, a0, a1); query_batch(reps, args, cur, a0, a1, slots[0]); }
-            for (size_t j = 0; j < nb; ++j) {
-                if (ahead.valid()) ahead.get();
-                size_t w0, w1;
-                bounds(j, w0, w1);
-                if (j + 1 < nb) {
-                    bounds(j + 1, a0, a1);
-                    BatchSlot *nxt_slot = &slots[(j + 1) & 1];
-                    ahead = std::async(std::launch::async, [&reps, &args, &cur, a0, a1, nxt_slot] { query_batch(reps, args, cur, a0, a1, *nxt_slot); });
-                }
-                format_batch(rb, args, cur, w0, w1, slots[j & 1], pieces, used);
-            }
-        }
-        {
-            const auto tw0 = std::chrono::steady_clock::now();
-            if (writer.valid()) writer.get();
-            g_trace_write_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count();
-        }
-        writing.swap(pieces);
-        writing_used = used;
-        writer = std::async(std::launch::async, [&writing, &writing_used] {
-            for (size_t i = 0; i < writing_used; ++i) fwrite(writing[i].data(), 1, writing[i].size(), stdout);
-        });
-        if (!more) break;
-        {
-            const auto ts0 = std::chrono::steady_clock::now();
-            err = scanner.get();
-            g_trace_scan_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts0).count();
-        }
-        std::swap(cur, nxt);
-    }
-    } catch (const ShardFailure &) {   // (the loop's futures -- scanner, query ahead -- joined while unwinding)
-        if (writer.valid()) writer.get();
+        err = rbg_cli::run_pipeline(
+            input, args.batch, bufs, rbg_cli::no_stage, rbg_cli::no_stage, [&](const BatchView &b, size_t s) { query_batch(reps, args, b, slots[s]); },
+            [&](const BatchView &b, size_t s, rbg_cli::PiecePool &pool) { format_batch(rb, args, b, slots[s], pool); }, &waits);
+    } catch (const ShardFailure &) {   // (the loop's futures -- scanner, query ahead, writer -- joined while unwinding)
         if (g_text_writer[1].valid()) g_text_writer[1].wait();
         fflush(stdout);
         return 1;
     }
-    if (writer.valid()) writer.get();
+    g_trace_scan_wait += waits.scan_wait_s;
+    g_trace_write_wait += waits.write_wait_s;
     {
         const auto tw0 = std::chrono::steady_clock::now();
         if (g_text_writer[1].valid()) g_text_writer[1].wait();
@@ -511,18 +444,7 @@ int main(int argc, char **argv) {
     fflush(stdout);
     stop = std::chrono::high_resolution_clock::now();
     const std::chrono::duration<double> total_query_time = stop - start;
-    switch (err) {  // rb_align.cpp:182-191
-        case -2:
-            fprintf(stderr, "ERROR: truncated quality string\n");
-            exit(1);
-            break;
-        case -3:
-            fprintf(stderr, "ERROR: error reading stream\n");
-            exit(1);
-            break;
-        default:
-            break;
-    }
+    rbg_cli::exit_on_input_error(err);  // rb_align.cpp:182-191
     if (std::getenv("RB_ALIGN_TRACE"))
         fprintf(stderr, "rb_align loop: library calls %.3f s, formatting %.3f s, waiting for the scanner %.3f s, for the writer %.3f s\n", g_trace_query,
                 g_trace_format, g_trace_scan_wait, g_trace_write_wait);

@@ -27,22 +27,12 @@
 #include "../include/rowbowt_gpu.hpp"
 #include "fastx.hpp"
 #include "cli_input.hpp"
-#include "rbg_thread_team.hpp"
+#include "cli_pipeline.hpp"
 
 namespace {
 
 using rbg_cli::InputSource;
-using rbg_cli::Window;
-
-struct BatchView {   // reads [w0, w0 + n) of a window, where the scanner found them
-    const Window *w;
-    size_t w0, n;
-    size_t size() const { return n; }
-    const char *name(size_t i) const { return w->base + w->recs.name_begin[w0 + i]; }
-    size_t name_len(size_t i) const { return w->recs.name_len[w0 + i]; }
-    const char *seq(size_t i) const { return w->base + w->recs.seq_begin[w0 + i]; }
-    uint64_t seq_len(size_t i) const { return w->recs.seq_len[w0 + i]; }
-};
+using rbg_cli::BatchView;
 
 struct RbLocsArgs {  // rb_markers_tsa.cpp:14-20
     std::string inpre, fastq_fname, outpre;
@@ -115,11 +105,7 @@ double g_trace[2] = {0, 0};   // RB_ALIGN_TRACE=1: seconds in the library call, 
 void query_batch(const rbwt::RowBowt<> &rb, const RbLocsArgs &args, const BatchView &b, LocSlot &slot) {
     const size_t N = b.size();
     const auto t0 = std::chrono::steady_clock::now();
-    slot.off.resize(N + 1);
-    slot.off[0] = 0;
-    for (size_t i = 0; i < N; ++i) slot.off[i + 1] = slot.off[i] + b.seq_len(i);
-    slot.seqs.resize(slot.off[N]);
-    for (size_t i = 0; i < N; ++i) std::memcpy(&slot.seqs[slot.off[i]], b.seq(i), b.seq_len(i));
+    rbg_cli::pack_raw_reads(b, slot.seqs, slot.off);
     rbg_free_buffer(slot.locs);
     rbg_free_buffer(slot.mk);
     slot.locs = slot.mk = nullptr;
@@ -156,21 +142,11 @@ void format_range(const BatchView &b, const LocSlot &r, size_t i0, size_t i1, rb
     out.finish();
 }
 
-// stage 2 (`pieces` keeps its buffers from window to window: `used` counts the ones of this window)
-void format_batch(const RbLocsArgs &args, const BatchView &b, LocSlot &slot, std::vector<rbg_cli::TextBuf> &pieces, size_t &used) {
-    const size_t N = b.size();
+// stage 2
+void format_batch(const RbLocsArgs &args, const BatchView &b, LocSlot &slot, rbg_cli::PiecePool &pool) {
     rbwt::detail::check(slot.rc, "rbg_find_loc_markers_greedy_seeding");
     const auto t0 = std::chrono::steady_clock::now();
-    const size_t T = std::max<size_t>(1, std::min<size_t>({static_cast<size_t>(args.threads), (N + 4095) / 4096, size_t(64)}));
-    const size_t first_piece = used;
-    used += T;
-    if (pieces.size() < used) pieces.resize(used);
-    for (size_t i = first_piece; i < used; ++i) pieces[i].clear();
-    std::vector<std::thread> workers;
-    for (size_t t = 1; t < T; ++t)
-        workers.emplace_back([&, t] { format_range(b, slot, N * t / T, N * (t + 1) / T, pieces[first_piece + t]); });
-    format_range(b, slot, 0, N / T, pieces[first_piece]);
-    for (auto &w : workers) w.join();
+    rbg_cli::format_split(b.size(), static_cast<size_t>(args.threads), pool, [&](size_t i0, size_t i1, rbg_cli::TextBuf &piece) { format_range(b, slot, i0, i1, piece); });
     g_trace[0] += slot.t_query;
     g_trace[1] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -204,51 +180,14 @@ int main(int argc, char **argv) {
         fprintf(stderr, "invalid file\n");
         exit(1);
     }
-    // three overlapped stages: scan window i+1 | query + format window i (in batches of --batch reads) | write window i-1
-    int err = 0;
-    Window cur, nxt;
-    err = input.next(cur);
-    std::future<void> writer;
-    std::vector<rbg_cli::TextBuf> pieces, writing;
-    size_t used = 0, writing_used = 0;
+    // the shared loop (cli_pipeline.hpp): batch j + 1 is searched while batch j is printed
     LocSlot slots[2];
-    while (true) {
-        std::future<int> scanner;
-        const bool more = err == 0;
-        if (more) scanner = std::async(std::launch::async, [&input, &nxt] { return input.next(nxt); });
-        used = 0;
-        {   // two stages over the window's batches: batch j + 1 is searched while batch j is printed
-            const size_t nb = (cur.size() + args.batch - 1) / args.batch;
-            auto view = [&](size_t j) { return BatchView{&cur, j * args.batch, std::min<size_t>(cur.size() - j * args.batch, args.batch)}; };
-            std::future<void> ahead;
-            if (nb) query_batch(rb, args, view(0), slots[0]);
-            for (size_t j = 0; j < nb; ++j) {
-                if (ahead.valid()) ahead.get();
-                if (j + 1 < nb) {
-                    LocSlot *ns = &slots[(j + 1) & 1];
-                    const BatchView nv = view(j + 1);
-                    ahead = std::async(std::launch::async, [&rb, &args, nv, ns] { query_batch(rb, args, nv, *ns); });
-                }
-                format_batch(args, view(j), slots[j & 1], pieces, used);
-            }
-        }
-        if (writer.valid()) writer.get();
-        writing.swap(pieces);
-        writing_used = used;
-        writer = std::async(std::launch::async, [&writing, &writing_used] {
-            for (size_t i = 0; i < writing_used; ++i) fwrite(writing[i].data(), 1, writing[i].size(), stdout);
-        });
-        if (!more) break;
-        err = scanner.get();
-        std::swap(cur, nxt);
-    }
-    if (writer.valid()) writer.get();
+    rbg_cli::PipelineBuffers bufs;
+    const int err = rbg_cli::run_pipeline(
+        input, args.batch, bufs, rbg_cli::no_stage, rbg_cli::no_stage, [&](const BatchView &b, size_t s) { query_batch(rb, args, b, slots[s]); },
+        [&](const BatchView &b, size_t s, rbg_cli::PiecePool &pool) { format_batch(args, b, slots[s], pool); });
     fflush(stdout);
-    switch (err) {  // rb_markers_tsa.cpp:114-123
-        case -2: fprintf(stderr, "ERROR: truncated quality string\n"); exit(1);
-        case -3: fprintf(stderr, "ERROR: error reading stream\n"); exit(1);
-        default: break;
-    }
+    rbg_cli::exit_on_input_error(err);  // rb_markers_tsa.cpp:114-123
     diff = std::chrono::high_resolution_clock::now() - start;
     if (std::getenv("RB_ALIGN_TRACE")) fprintf(stderr, "rb_locs loop: library call %.3f s, markers -> text %.3f s\n", g_trace[0], g_trace[1]);
     std::cerr << "locating markers took: " << diff.count() << " seconds" << std::endl;

@@ -42,26 +42,15 @@
 #include "../include/rowbowt_gpu.hpp"
 #include "fastx.hpp"
 #include "cli_input.hpp"
+#include "cli_pipeline.hpp"
 #include <cstdlib>
-#include "rbg_thread_team.hpp"
 
 namespace {
 
 using rbg_cli::FastxReader;
 using rbg_cli::InputSource;
 using rbg_cli::Window;
-
-// reads [w0, w0 + n) of a window, where the scanner found them (names and sequences are spans of the window's buffer)
-struct BatchView {
-    const Window *w;
-    size_t w0, n;
-    size_t size() const { return n; }
-    const char *name(size_t i) const { return w->base + w->recs.name_begin[w0 + i]; }
-    size_t name_len(size_t i) const { return w->recs.name_len[w0 + i]; }
-    const char *seq(size_t i) const { return w->base + w->recs.seq_begin[w0 + i]; }
-    uint64_t seq_len(size_t i) const { return w->recs.seq_len[w0 + i]; }
-};
-using rbg_cli::put_u64;
+using rbg_cli::BatchView;
 
 struct RbMarkersArgs {  // rb_markers.cpp:22-40
     std::string inpre, fastq_fname;
@@ -415,17 +404,7 @@ void draw_coins(const RbMarkersArgs &args, RandomBoolGenerator &booler, size_t N
         for (size_t i = 0; i < N; ++i) slot.first_fwd[i] = booler.get_bool() ? 1 : 0;
 }
 
-// stage 1 with --device-format: the raw reads go to the library, which makes both strands, seeds, sorts, filters and prints on the device
-// (false: the library could not allocate -- the batch goes the host way)
-// the raw reads of a batch back to back, and the tool's options as the library takes them
-void pack_raw_reads(const BatchView &b, SeedSlot &slot) {
-    const size_t N = b.size();
-    slot.off.resize(N + 1);
-    slot.off[0] = 0;
-    for (size_t i = 0; i < N; ++i) slot.off[i + 1] = slot.off[i] + b.seq_len(i);
-    slot.seqs.resize(slot.off[N]);
-    for (size_t i = 0; i < N; ++i) memcpy(&slot.seqs[slot.off[i]], b.seq(i), b.seq_len(i));
-}
+// the tool's options as the library takes them
 rbg_report_params_t report_params(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args) {
     rbg_report_params_t p{};
     p.wsize = args.wsize; p.max_range = args.max_range; p.min_range = args.min_range; p.ftab_k = rb.ftab_k();
@@ -438,7 +417,7 @@ rbg_report_params_t report_params(const rbwt::RowBowt<> &rb, const RbMarkersArgs
 // --tally: the raw reads go to the library, which counts the markers of the lines it would print; nothing comes back
 void tally_batch(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args, const BatchView &b, SeedSlot &slot, rbwt::MarkerTally &tally) {
     const auto t0 = std::chrono::steady_clock::now();
-    pack_raw_reads(b, slot);
+    rbg_cli::pack_raw_reads(b, slot.seqs, slot.off);
     const auto t1 = std::chrono::steady_clock::now();
     const rbg_report_params_t p = report_params(rb, args);
     const uint32_t flags = (args.tally_per_read ? RBG_TALLY_PER_READ : 0u) | (args.tally_drop_conflicts ? RBG_TALLY_DROP_SITE_CONFLICTS : 0u);
@@ -448,10 +427,12 @@ void tally_batch(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args, const Bat
     g_trace[1] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
 }
 
+// stage 1 with --device-format: the raw reads go to the library, which makes both strands, seeds, sorts, filters and prints on the device
+// (false: the library could not allocate -- the batch goes the host way)
 bool query_batch_device(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args, const BatchView &b, SeedSlot &slot) {
     const size_t N = b.size();
     const auto t0 = std::chrono::steady_clock::now();
-    pack_raw_reads(b, slot);
+    rbg_cli::pack_raw_reads(b, slot.seqs, slot.off);
     const auto t1 = std::chrono::steady_clock::now();
     const rbg_report_params_t p = report_params(rb, args);
     slot.text = nullptr;
@@ -487,20 +468,13 @@ void query_batch(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args, const Bat
     slot.t_query = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
 }
 
-// stage 2 (`pieces` is a pool that keeps its buffers from window to window: `used` counts the ones of this window)
-void format_batch(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args, const BatchView &b, SeedSlot &slot, std::vector<rbg_cli::TextBuf> &pieces, size_t &used) {
-    const size_t N = b.size();
+// stage 2
+void format_batch(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args, const BatchView &b, SeedSlot &slot, rbg_cli::PiecePool &pool) {
     if (slot.on_device) {   // the text is made: wait for its copy, hand it to the writer's pieces
         rbwt::detail::check(slot.rc, "rbg_markers_report_text");
         const auto t2 = std::chrono::steady_clock::now();
         rbwt::detail::check(rbg_wait_text(rb.handle(), slot.text), "rbg_wait_text");
-        used += 1;
-        if (pieces.size() < used) pieces.resize(used);
-        rbg_cli::TextBuf &piece = pieces[used - 1];
-        piece.clear();
-        piece.reserve(slot.text_len);
-        if (slot.text_len) memcpy(piece.p.get(), slot.text, slot.text_len);
-        piece.len = slot.text_len;
+        pool.put(slot.text, slot.text_len);
         rbwt::detail::check(rbg_release_text(rb.handle(), slot.text), "rbg_release_text");
         slot.text = nullptr;
         g_trace[0] += slot.t_strands;
@@ -512,16 +486,8 @@ void format_batch(const rbwt::RowBowt<> &rb, const RbMarkersArgs &args, const Ba
     const BatchSeeds &r = slot.r;
     const auto t2 = std::chrono::steady_clock::now();
     const std::vector<uint8_t> &first_fwd = slot.first_fwd;
-    const size_t T = std::max<size_t>(1, std::min<size_t>({static_cast<size_t>(args.threads), (N + 4095) / 4096, size_t(64)}));
-    const size_t first_piece = used;
-    used += T;
-    if (pieces.size() < used) pieces.resize(used);
-    for (size_t i = first_piece; i < used; ++i) pieces[i].clear();
-    std::vector<std::thread> workers;
-    for (size_t t = 1; t < T; ++t)
-        workers.emplace_back([&, t] { format_range(args, b, r, first_fwd, N * t / T, N * (t + 1) / T, pieces[first_piece + t]); });
-    format_range(args, b, r, first_fwd, 0, N / T, pieces[first_piece]);
-    for (auto &w : workers) w.join();
+    rbg_cli::format_split(b.size(), static_cast<size_t>(args.threads), pool,
+                          [&](size_t i0, size_t i1, rbg_cli::TextBuf &piece) { format_range(args, b, r, first_fwd, i0, i1, piece); });
     const auto t3 = std::chrono::steady_clock::now();
     g_trace[0] += slot.t_strands;
     g_trace[1] += slot.t_query;
@@ -560,67 +526,28 @@ int main(int argc, char **argv) {
     rbwt::MarkerTally tally;
     const bool tallying = !args.tally_file.empty();
     if (tallying) tally = rb.make_tally();
-    // three overlapped stages: scan window i+1 | query + format window i (in batches of --batch reads) | write window i-1
-    int err = 0;
-    Window cur, nxt;
-    err = input.next(cur);
-    std::future<void> writer;
-    std::vector<rbg_cli::TextBuf> pieces, writing;
-    size_t used = 0, writing_used = 0;
+    // the shared loop (cli_pipeline.hpp): batch j + 1 is searched while batch j's seeds are sorted and printed
     SeedSlot slots[2];
-    while (true) {
-        std::future<int> scanner;
-        const bool more = err == 0;
-        if (more) scanner = std::async(std::launch::async, [&input, &nxt] { return input.next(nxt); });
-        used = 0;
-        {   // two stages over the window's batches: batch j + 1 is searched while batch j's seeds are sorted and printed
-            const uint64_t ft_k = rb.ftab_k();
-            if (ft_k && !args.lmem)   // (lmem starts a suffix shorter than k from the full range: no substr past the end, :369)
-                for (size_t i = 0; i < cur.size(); ++i)
-                    if (cur.recs.seq_len[i] < ft_k) {  // the reference dies in std::string::substr (rowbowt.hpp:431)
-                        fprintf(stderr, "ERROR: read shorter than the ftab k-mer size (%llu)\n", static_cast<unsigned long long>(ft_k));
-                        exit(1);
-                    }
-            const size_t nb = (cur.size() + args.batch - 1) / args.batch;
-            auto view = [&](size_t j) { return BatchView{&cur, j * args.batch, std::min<size_t>(cur.size() - j * args.batch, args.batch)}; };
-            std::future<void> ahead;
-            if (tallying) {   // one call per batch, the coins drawn in file order as below; no text, nothing to overlap with
-                for (size_t j = 0; j < nb; ++j) {
-                    draw_coins(args, booler, view(j).size(), slots[0]);
-                    tally_batch(rb, args, view(j), slots[0], tally);
+    rbg_cli::PipelineBuffers bufs;
+    const uint64_t ft_k = rb.ftab_k();
+    auto check_lengths = [&](const Window &cur) {
+        if (ft_k && !args.lmem)   // (lmem starts a suffix shorter than k from the full range: no substr past the end, :369)
+            for (size_t i = 0; i < cur.size(); ++i)
+                if (cur.recs.seq_len[i] < ft_k) {  // the reference dies in std::string::substr (rowbowt.hpp:431)
+                    fprintf(stderr, "ERROR: read shorter than the ftab k-mer size (%llu)\n", static_cast<unsigned long long>(ft_k));
+                    exit(1);
                 }
-            } else if (nb) {
-                draw_coins(args, booler, view(0).size(), slots[0]);
-                query_batch(rb, args, view(0), slots[0]);
-            }
-            for (size_t j = 0; j < nb && !tallying; ++j) {
-                if (ahead.valid()) ahead.get();
-                if (j + 1 < nb) {
-                    SeedSlot *ns = &slots[(j + 1) & 1];
-                    const BatchView nv = view(j + 1);
-                    draw_coins(args, booler, nv.size(), *ns);
-                    ahead = std::async(std::launch::async, [&rb, &args, nv, ns] { query_batch(rb, args, nv, *ns); });
-                }
-                format_batch(rb, args, view(j), slots[j & 1], pieces, used);
-            }
-        }
-        if (writer.valid()) writer.get();
-        writing.swap(pieces);
-        writing_used = used;
-        writer = std::async(std::launch::async, [&writing, &writing_used] {
-            for (size_t i = 0; i < writing_used; ++i) fwrite(writing[i].data(), 1, writing[i].size(), stdout);
-        });
-        if (!more) break;
-        err = scanner.get();
-        std::swap(cur, nxt);
-    }
-    if (writer.valid()) writer.get();
+    };
+    auto coins = [&](const BatchView &b, size_t s) { draw_coins(args, booler, b.size(), slots[s]); };
+    int err;
+    if (tallying)   // one call per batch, the coins drawn in file order as for the lines; no text, nothing to overlap with
+        err = rbg_cli::run_in_sequence(input, args.batch, bufs, check_lengths, coins, [&](const BatchView &b, size_t s) { tally_batch(rb, args, b, slots[s], tally); });
+    else
+        err = rbg_cli::run_pipeline(
+            input, args.batch, bufs, check_lengths, coins, [&](const BatchView &b, size_t s) { query_batch(rb, args, b, slots[s]); },
+            [&](const BatchView &b, size_t s, rbg_cli::PiecePool &pool) { format_batch(rb, args, b, slots[s], pool); });
     fflush(stdout);
-    switch (err) {  // rb_markers.cpp:581-590
-        case -2: fprintf(stderr, "ERROR: truncated quality string\n"); exit(1);
-        case -3: fprintf(stderr, "ERROR: error reading stream\n"); exit(1);
-        default: break;
-    }
+    rbg_cli::exit_on_input_error(err);  // rb_markers.cpp:581-590
     if (tallying) {   // one line per marker, in export order
         FILE *f = fopen(args.tally_file.c_str(), "wb");
         if (!f) {

@@ -266,6 +266,7 @@ def test_cli_rb_markers_stdout(data_dir, tmp_path, small):
     for args, kw in ((["--wsize", "10", "--max-range", "3", "--min-range", "2"], dict(wsize=10, max_range=3, min_range=2)),
                      (["-w", "5", "--batch", "7", "--threads", "3"], dict(wsize=5)),
                      (["--heuristic"], dict(heuristic=True)),
+                     (["--heuristic", "--batch", "7"], dict(heuristic=True)),   # the coins are drawn batch by batch, ahead of the printing
                      (["--heuristic", "--best-strand-only", "--min-seed-length", "30", "--read-len", "101"],
                       dict(heuristic=True, best_strand=True, min_seed_len=30, read_len=101)),
                      (["--heuristic", "-y", "25", "--clear-conflicting", "--clear-identical", "-l", "50", "-w", "8"],
