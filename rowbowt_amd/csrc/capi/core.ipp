@@ -162,6 +162,7 @@ struct VStage {
     bool on, sync;
     std::chrono::steady_clock::time_point t0;
     explicit VStage(const char *w, bool sync_ = true) : what(w), on(std::getenv("RBG_VERBOSE") != nullptr), sync(sync_), t0(std::chrono::steady_clock::now()) {}
+    VStage(const char *w, bool sync_, bool on_) : what(w), on(on_), sync(sync_), t0(std::chrono::steady_clock::now()) {}   // (a caller that has read the switch)
     ~VStage() {
         if (!on) return;
         if (sync) (void)hipDeviceSynchronize();
@@ -332,7 +333,10 @@ inline size_t arena_round(size_t bytes) { return ((bytes ? bytes : 1) + kArenaAl
 // what rbg_load_plan.hpp needs of rbg_dev.h and of the arena
 inline LoadConsts load_consts() {
     return {kMaxNarrowShift, kMaxWideShift, static_cast<uint32_t>(kLdsSyms), sizeof(RankSlot) + sizeof(uint32_t), kArenaAlign,
-            {RunsFmt<uint32_t>::samp_bytes, RunsFmt<uint64_t>::samp_bytes}, {PhiFmt<uint32_t>::ent_bytes, PhiFmt<uint64_t>::ent_bytes}};
+            {RunsFmt<uint32_t>::samp_bytes, RunsFmt<uint64_t>::samp_bytes}, {PhiFmt<uint32_t>::ent_bytes, PhiFmt<uint64_t>::ent_bytes},
+            static_cast<uint32_t>(kLdsRunDepth), 27, 5, 24,   // (rbg_runs2_device.hpp load_run_tab: stride | shift << 27, first record | depth << 24)
+            kPhiPackedPosBits, kPhiPackedMaxShift, {sizeof(PhiSlot<uint32_t>), sizeof(PhiSlot<uint64_t>)}, sizeof(PhiSlotPacked),
+            {sizeof(PhiEnt<uint32_t>), sizeof(PhiEnt<uint64_t>)}};
 }
 
 // space for `bytes` in the arena (or its own allocation when the arena is full / absent)

@@ -82,306 +82,401 @@ int add_fillers(rbg_index *ix, bool phi, void **ent, void **samp, bool tracked, 
     return RBG_OK;
 }
 
-template <typename P>
-int upload_tables_runs2(rbg_index *ix) {
-    constexpr bool W = sizeof(P) == 8;
-    HostIndex &h = ix->H();
-    rbg_index::RunsReport &rep = ix->runs_report;
-    rep.fmt = 2;
-    for (SymTable &t : h.sym) {   // (the depth-1 lists compose_on_device left on the device are the slot layout's)
+// ---- upload_tables_runs2: what a load of the run-indexed layout puts on the device, step by step ------------------------------------------------------
+// The geometry rules (bucket shifts, the uniform depth, the phi slots and directory, the stage tables) are rbg_load_plan.hpp's; here are the device
+// allocations, copies and kernel launches, in an order hbm_bytes, the arena's contents and the replicas' allocation list depend on.
+
+// The switches of one load, read ONCE PER LOAD (tests change them between loads) and nowhere below.
+struct RunSwitches {
+    double dir_target;     // RBG_RANK_DIR_RUNS: runs per directory bucket at most this on average (default 4)
+    double rec_asked;      // RBG_RUN_REC_PER: entries per record bucket on average (0: run_record_plan's 2.5 / 4 / 6)
+    int uniform;           // RBG_RUN_UNIFORM: 0 / 1 = never / whenever the depth is deep enough (tests, A/B); -1: unset
+    double phi_per;        // RBG_PHI_DIR_PER: sampled positions per phi directory bucket at least this on average (default 1)
+    uint32_t fill_shift, super_shift;   // RBG_RUN_FILL_SHIFT / RBG_PHI_SUPER_SHIFT: test-only, so that small indexes meet fillers and several super blocks
+    bool verbose;          // RBG_VERBOSE
+};
+inline RunSwitches read_run_switches() {
+    auto positive = [](const char *name, double dflt) { const char *e = std::getenv(name); return e && std::atof(e) > 0 ? std::atof(e) : dflt; };
+    RunSwitches s;
+    s.dir_target = positive("RBG_RANK_DIR_RUNS", 4.0);
+    s.fill_shift = static_cast<uint32_t>(env_opt("RBG_RUN_FILL_SHIFT", kRunFillShift, 4, kRunFillShift));
+    s.super_shift = static_cast<uint32_t>(env_opt("RBG_PHI_SUPER_SHIFT", kPhiSuperShift, 1, 24));
+    s.rec_asked = positive("RBG_RUN_REC_PER", 0.0);
+    const char *e_uni = std::getenv("RBG_RUN_UNIFORM");
+    s.uniform = e_uni ? std::atoi(e_uni) : -1;
+    s.phi_per = positive("RBG_PHI_DIR_PER", 1.0);
+    s.verbose = std::getenv("RBG_VERBOSE") != nullptr;
+    return s;
+}
+
+// what the steps of one load share
+struct RunLoad {
+    rbg_index *ix;
+    HostIndex &h;
+    RunSwitches sw;
+    LoadConsts consts;
+    bool wide;                       // 8-byte positions
+    uint32_t D = 1, mask = 1;        // the depths composed; bit d - 1: depth d keeps its run lists
+    uint32_t max_shift = 31;         // of a bucket (a per-lane shift of the low word: rbg_device.hpp pos_bucket)
+    std::vector<double> rec_per;     // [d]: entries per bucket on average of depth d + 1's records, 0 = directories (rbg_load_plan.hpp run_record_plan)
+    std::vector<DevRunTab2> tabs;    // the table records of every depth so far, each depth closed by one more
+    std::vector<uint64_t> hot;       // rbg_dev.h: dir_off | dir_shift << 56 per table
+    RunLoad(rbg_index *ix_, bool wide_) : ix(ix_), h(ix_->H()), sw(read_run_switches()), consts(load_consts()), wide(wide_) {}
+};
+// the buckets of a depth's tables: table t's shift, and its first bucket (directory entry or record) among the depth's; off[tables]: all of them
+struct TableBuckets {
+    std::vector<uint32_t> shift;
+    std::vector<uint64_t> off;
+};
+// what the steps of one kept depth share
+struct RunDepth {
+    uint32_t d;                                    // the depth's index: k-mer depth d + 1
+    const std::vector<SymTable> &T;
+    std::vector<uint64_t> first, nr;               // table t's first entry among the depth's, and its entries without the sentinel; first[tables]: all of them
+    TableBuckets b;
+    void *abs_ent = nullptr, *abs_samp = nullptr;  // the depth's {start, cum} pairs of P, tables back to back, and its samples (P each)
+    uint64_t E2 = 0, fillers = 0;                  // entries with the fillers; the fillers
+    RunDepth(uint32_t d_, const std::vector<SymTable> &T_) : d(d_), T(T_), first(T_.size() + 1, 0), nr(T_.size()) {
+        for (size_t t = 0; t < T.size(); ++t) { first[t + 1] = first[t] + T[t].nruns + 1; nr[t] = T[t].nruns; }
+        E2 = first[T.size()];
+    }
+    size_t nt() const { return T.size(); }
+    uint64_t buckets() const { return b.off[nt()]; }
+    // per table the widest bucket that still holds at most about `per` entries on average (rbg_load_plan.hpp bucket_shift)
+    void own_buckets(double per, uint64_t n, uint32_t max_shift) {
+        b.shift.assign(nt(), 0);
+        b.off.assign(nt() + 1, 0);
+        for (size_t t = 0; t < nt(); ++t) {
+            b.shift[t] = bucket_shift(static_cast<double>(nr[t]), per, n, max_shift);
+            b.off[t + 1] = b.off[t] + bucket_count(n, b.shift[t]);
+        }
+    }
+};
+
+// the depth-1 lists compose_on_device left on the device are the slot layout's
+void release_slot_lists(rbg_index *ix) {
+    for (SymTable &t : ix->H().sym) {
         free_tracked(ix, const_cast<void *>(t.dev_ent));
         free_tracked(ix, const_cast<void *>(t.dev_samp));
         t.dev_ent = t.dev_samp = nullptr;
     }
-    const std::vector<SymTable> *depth[kMaxRunDepth];
-    depth[0] = &h.sym;
-    for (uint32_t d = 2; d <= static_cast<uint32_t>(kMaxRunDepth); ++d) depth[d - 1] = &h.kmer(d);
-    uint32_t D = 1;
-    while (D < static_cast<uint32_t>(kMaxRunDepth) && !depth[D]->empty()) ++D;
-    rep.depths_composed = D;
-    uint32_t mask = (ix->run_depth_mask ? ix->run_depth_mask : ~0u) & ((1u << D) - 1u);
-    mask |= 1u | (1u << (D - 1));   // (the deepest is always kept: the kernels step by it)
-    const char *e_dt = std::getenv("RBG_RANK_DIR_RUNS");   // runs per directory bucket at most this on average (default 4)
-    const double dir_target = e_dt && std::atof(e_dt) > 0 ? std::atof(e_dt) : 4.0;
-    // RBG_RUN_FILL_SHIFT / RBG_PHI_SUPER_SHIFT: test-only overrides so that small indexes meet fillers and several super blocks
-    ix->dev.run_fill_shift = static_cast<uint32_t>(env_opt("RBG_RUN_FILL_SHIFT", kRunFillShift, 4, kRunFillShift));
-    const uint32_t super_shift = static_cast<uint32_t>(env_opt("RBG_PHI_SUPER_SHIFT", kPhiSuperShift, 1, 24));
-    const uint32_t max_shift = W ? ix->dev.run_fill_shift : 31u;   // (a per-lane shift of the low word: rbg_device.hpp pos_bucket)
+}
+
+// the depths composed, those that keep their run lists, and which of them get bucket records
+void settle_depths(RunLoad &L, const std::vector<SymTable> *depth[kMaxRunDepth]) {
+    rbg_index *ix = L.ix;
+    depth[0] = &L.h.sym;
+    for (uint32_t d = 2; d <= static_cast<uint32_t>(kMaxRunDepth); ++d) depth[d - 1] = &L.h.kmer(d);
+    while (L.D < static_cast<uint32_t>(kMaxRunDepth) && !depth[L.D]->empty()) ++L.D;
+    ix->runs_report.depths_composed = L.D;
+    L.mask = (ix->run_depth_mask ? ix->run_depth_mask : ~0u) & ((1u << L.D) - 1u);
+    L.mask |= 1u | (1u << (L.D - 1));   // (the deepest is always kept: the kernels step by it)
+    ix->dev.run_fill_shift = L.sw.fill_shift;
+    L.max_shift = L.wide ? ix->dev.run_fill_shift : 31u;
     // BUCKET RECORDS (RBG_OPT_RUN_REC; rbg_dev.h RunRec2): one aligned 64-byte record per bucket of about three entries instead of
     // the directory -- a rank is one sector.  Automatic: when all kept depths with their records (about 64 / 3 bytes per entry) and
     // the rest of the replica stay within half the budget.  RBG_RUN_REC_PER: entries per bucket on average (default 2.5 inside the
-    // bucket; the one before them is held too).
-    const char *e_rp = std::getenv("RBG_RUN_REC_PER");
-    const double rec_asked = e_rp && std::atof(e_rp) > 0 ? std::atof(e_rp) : 0.0;
-    // rec_per[d] = entries per bucket on average of depth d's records, 0 = directories (rbg_load_plan.hpp run_record_plan: per depth, deepest first)
-    const std::vector<double> rec_per = run_record_plan(shape_of(h), load_consts(), mask, D, ix->hbm_budget, g_opt_run_rec.load(), g_opt_run_rec_depths.load(), rec_asked,
-                                                        max_shift, g_opt_run_phi.load());
-    bool any_recs = false, all_recs = true;
-    for (uint32_t d = 0; d < D; ++d)
-        if (mask >> d & 1u) { any_recs = any_recs || rec_per[d] > 0; all_recs = all_recs && rec_per[d] > 0; }
-    std::vector<DevRunTab2> tabs;
-    std::vector<uint64_t> hot;      // rbg_dev.h: dir_off | dir_shift << 56 per table
+    // bucket; the one before them is held too).  Per depth, deepest first: rbg_load_plan.hpp run_record_plan.
+    L.rec_per = run_record_plan(shape_of(L.h), L.consts, L.mask, L.D, ix->hbm_budget, g_opt_run_rec.load(), g_opt_run_rec_depths.load(), L.sw.rec_asked, L.max_shift,
+                                g_opt_run_phi.load());
+}
+
+// a depth without run lists: nothing steps by it
+void leave_depth_out(RunLoad &L, uint32_t d) {
+    release_kmer_level(L.ix, d + 1);
+    for (SymTable &st : kmer_level_tables(L.h, d + 1)) st.dev_ent = st.dev_samp = nullptr;
+}
+
+// the depth's lists converted from the host tables and copied to the device
+template <typename P>
+int convert_host_tables(RunLoad &L, RunDepth &R) {
+    const HostIndex &h = L.h;
+    const std::vector<SymTable> &T = R.T;
+    const uint64_t entries = R.E2;
+    HostBuf<RunEnt<P>> ent(entries + 2);
+    HostBuf<P> samp(h.has_tsa ? entries + 2 : 0);
+    const size_t Wk = std::max<size_t>(1, std::min<size_t>({16, std::thread::hardware_concurrency(), T.size()}));
+    std::vector<std::thread> workers;
+    for (size_t w = 0; w < Wk; ++w)
+        workers.emplace_back([&, w] {
+            for (size_t t = w; t < T.size(); t += Wk) {
+                const SymTable &tb = T[t];
+                if (tb.start.size() != tb.nruns + 1) continue;   // (checked below)
+                for (uint64_t k = 0; k <= tb.nruns; ++k) ent[R.first[t] + k] = RunEnt<P>{static_cast<P>(tb.start[k]), static_cast<P>(tb.cum[k])};
+                if (h.has_tsa) {
+                    for (uint64_t k = 0; k < tb.nruns; ++k) samp[R.first[t] + k] = static_cast<P>(tb.samp[k]);
+                    samp[R.first[t] + tb.nruns] = 0;
+                }
+            }
+        });
+    for (auto &w : workers) w.join();
+    for (const SymTable &tb : T)
+        if (tb.start.size() != tb.nruns + 1) return RBG_EARG;   // a table without host arrays and without a device level
+    for (uint64_t x = 0; x < 2; ++x) { ent[entries + x] = ent[entries - 1]; if (h.has_tsa) samp[entries + x] = 0; }
+    const void *up = nullptr;
     int rc;
-    for (uint32_t d = 0; d < D; ++d) {
-        const std::vector<SymTable> &T = *depth[d];
-        ix->dev.run_tab_first[d] = static_cast<uint32_t>(tabs.size());
-        ix->dev.run_samp[d] = nullptr;
-        ix->dev.run_ent2[d] = nullptr; ix->dev.run_dir2[d] = nullptr;
-        if (!(mask >> d & 1u)) {   // no run lists at this depth: nothing steps by it
-            release_kmer_level(ix, d + 1);
-            for (SymTable &st : kmer_level_tables(h, d + 1)) st.dev_ent = st.dev_samp = nullptr;
-            continue;
-        }
-        uint64_t entries = 0;
-        for (const SymTable &t : T) entries += t.nruns + 1;
-        // ---- the depth's {start, cum} pairs of P, tables back to back, and its samples (P each) on the device ----
-        void *abs_ent = nullptr, *abs_samp = nullptr;
-        std::vector<uint64_t> first(T.size() + 1, 0), nr(T.size());
-        for (size_t t = 0; t < T.size(); ++t) { first[t + 1] = first[t] + T[t].nruns + 1; nr[t] = T[t].nruns; }
-        ComposedLevel *L = (d >= 1 && d - 1 < ix->kmer_levels.size() && ix->kmer_levels[d - 1].ent) ? &ix->kmer_levels[d - 1] : nullptr;
-        if (L) {
-            if (L->entries != entries || L->first.size() != T.size()) return RBG_EARG;
-            for (size_t t = 0; t < T.size(); ++t)
-                if (L->first[t] != first[t]) return RBG_EARG;
-            abs_ent = L->ent;
-            abs_samp = h.has_tsa ? L->samp : nullptr;
-            L->ent = L->samp = nullptr;   // (adopted: the index's allocation list keeps them)
-        } else {
-            HostBuf<RunEnt<P>> ent(entries + 2);
-            HostBuf<P> samp(h.has_tsa ? entries + 2 : 0);
-            const size_t Wk = std::max<size_t>(1, std::min<size_t>({16, std::thread::hardware_concurrency(), T.size()}));
-            std::vector<std::thread> workers;
-            for (size_t w = 0; w < Wk; ++w)
-                workers.emplace_back([&, w] {
-                    for (size_t t = w; t < T.size(); t += Wk) {
-                        const SymTable &tb = T[t];
-                        if (tb.start.size() != tb.nruns + 1) continue;   // (checked below)
-                        for (uint64_t k = 0; k <= tb.nruns; ++k) ent[first[t] + k] = RunEnt<P>{static_cast<P>(tb.start[k]), static_cast<P>(tb.cum[k])};
-                        if (h.has_tsa) {
-                            for (uint64_t k = 0; k < tb.nruns; ++k) samp[first[t] + k] = static_cast<P>(tb.samp[k]);
-                            samp[first[t] + tb.nruns] = 0;
-                        }
-                    }
-                });
-            for (auto &w : workers) w.join();
-            for (const SymTable &tb : T)
-                if (tb.start.size() != tb.nruns + 1) return RBG_EARG;   // a table without host arrays and without a device level
-            for (uint64_t x = 0; x < 2; ++x) { ent[entries + x] = ent[entries - 1]; if (h.has_tsa) samp[entries + x] = 0; }
-            const void *up = nullptr;
-            if ((rc = dev_upload(ix, ent.data(), (entries + 2) * sizeof(RunEnt<P>), &up))) return rc;
-            abs_ent = const_cast<void *>(up);
-            if (h.has_tsa) {
-                if ((rc = dev_upload(ix, samp.data(), (entries + 2) * sizeof(P), &up))) return rc;
-                abs_samp = const_cast<void *>(up);
-            }
-        }
-        uint64_t E2 = entries, fillers = 0;
-        if constexpr (W) {
-            std::vector<uint64_t> at;
-            for (size_t t = 0; t < T.size(); ++t) { at.push_back(first[t]); at.push_back(first[t] + nr[t]); }
-            if ((rc = add_fillers(ix, false, &abs_ent, &abs_samp, true, &E2, h.n, at, &fillers))) return rc;
-            if (fillers) {
-                for (size_t t = 0; t < T.size(); ++t) { first[t] = at[2 * t]; nr[t] = at[2 * t + 1] - at[2 * t]; }
-                first[T.size()] = E2;
-            }
-        }
-        for (size_t t = 0; t < T.size(); ++t)
-            if (nr[t] >= 0xFFFFFFF0ull) {
-                std::fprintf(stderr, "rbg: a table of k-mer depth %u has %llu entries: the run-indexed layout holds fewer than 2^32 - 16 per table\n", d + 1,
-                             static_cast<unsigned long long>(nr[t]));
-                return RBG_EARG;
-            }
-        rep.entries[d] = E2;
-        rep.fillers[d] = fillers;
-        {   // every cum becomes a ROW of the F column: + the table's F (rbg_dev.h kRunHotShiftBit; k_build.hip k_fold_F)
-            TmpDev tf;
-            const size_t nt = T.size();
-            if ((rc = tf.alloc((2 * nt + 1) * 8))) return rc;
-            std::vector<uint64_t> Fv(nt);
-            for (size_t t = 0; t < nt; ++t) Fv[t] = T[t].F;
-            uint64_t *t_first = tf.as<uint64_t>(), *t_F = t_first + nt + 1;
-            HIP_TRY(hipMemcpy(t_first, first.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(t_F, Fv.data(), nt * 8, hipMemcpyHostToDevice));
-            HIP_TRY(static_cast<hipError_t>(launch_fold_F(sizeof(P), abs_ent, t_first, t_F, static_cast<uint32_t>(nt), E2 + (W ? 0 : 2), nullptr)));   // (4-byte positions: the two spare entries are final too)
-            HIP_TRY(hipDeviceSynchronize());
-        }
-        // ---- directories: per table the widest bucket that still holds at most about dir_target entries on average ----
-        std::vector<uint32_t> dshift(T.size(), 0);
-        std::vector<uint64_t> doff(T.size() + 1, 0);
-        for (size_t t = 0; t < T.size(); ++t) {
-            uint32_t sh = 0;
-            const double runs = static_cast<double>(std::max<uint64_t>(1, nr[t]));
-            while (sh < max_shift && runs * static_cast<double>(uint64_t(2) << sh) <= dir_target * static_cast<double>(h.n)) ++sh;
-            dshift[t] = sh;
-            doff[t + 1] = doff[t] + (h.n >> sh) + 2;
-        }
-        void *dirp = nullptr;
-        const size_t dir_ent = W ? sizeof(RunDir64) : 4;
-        ix->dev.run_rec2[d] = nullptr;
-        const bool use_recs = rec_per[d] > 0;
-        const double rec_target = rec_per[d];
-        if (d == 0) { ix->dev.run_uni_depth = static_cast<uint32_t>(kMaxRunDepth); ix->dev.run_uni_stride = ix->dev.run_uni_shift = 0; }
-        if (use_recs) {
-            // the records' buckets: the widest with at most rec_target entries starting inside on average
-            auto widest = [&](double runs) {
-                uint32_t sh = 0;
-                runs = std::max(1.0, runs);
-                while (sh < max_shift && runs * static_cast<double>(uint64_t(2) << sh) <= rec_target * static_cast<double>(h.n)) ++sh;
-                return sh;
-            };
-            for (size_t t = 0; t < T.size(); ++t) {
-                dshift[t] = widest(static_cast<double>(nr[t]));
-                doff[t + 1] = doff[t] + (h.n >> dshift[t]) + 2;
-            }
-            // UNIFORM geometry (DevIndex::run_uni) for a depth whose hot words a step would read from global memory: one shift -- the widest for the
-            // depth's AVERAGE table -- and one record count for every table, so that a step computes its table's hot word.  Taken when it costs no more
-            // than a tenth more records than the tables' own shifts, and kept when the buckets that then overflow their record (more than eleven entries:
-            // pivots + a scan of the run list) stay rare -- a depth with a few very frequent k-mers keeps per-table shifts.  RBG_RUN_UNIFORM=0 / 1: never /
-            // whenever the depth is deep enough (tests, A/B).
-            const int uni_env = [] { const char *e = std::getenv("RBG_RUN_UNIFORM"); return e ? std::atoi(e) : -1; }();   // (read per load: tests switch it)
-            bool uniform = false;
-            std::vector<uint32_t> own_shift = dshift;
-            std::vector<uint64_t> own_off = doff;
-            bool deepest = true;   // (one uniform depth: the deepest kept one with records -- DevIndex::run_uni_*)
-            for (uint32_t d2 = d + 1; d2 < D; ++d2) deepest = deepest && !((mask >> d2 & 1u) && rec_per[d2] > 0);
-            if (deepest && d >= static_cast<uint32_t>(kLdsRunDepth) && uni_env != 0 && T.size() > 1) {
-                double total_runs = 0;
-                for (size_t t = 0; t < T.size(); ++t) total_runs += static_cast<double>(nr[t]);
-                const uint32_t su = widest(total_runs / static_cast<double>(T.size()));
-                const uint64_t stride = (h.n >> su) + 2;
-                if (!(stride >> 27) && su < 32 && tabs.size() + T.size() < (1u << 24) && (uni_env == 1 || static_cast<double>(stride) * static_cast<double>(T.size()) <= 1.1 * static_cast<double>(own_off[T.size()]))) {
-                    uniform = true;
-                    for (size_t t = 0; t < T.size(); ++t) { dshift[t] = su; doff[t + 1] = doff[t] + stride; }
-                }
-            }
-            void *recp = nullptr;
-            unsigned long long novf = 0;
-            // the depth's bucket records under the geometry (dshift, doff) as they stand: recp, novf
-            auto build_recs = [&]() -> int {
-                int rc2;
-                if ((rc2 = dev_reserve(ix, doff[T.size()] * sizeof(RunRec2) + 64, &recp))) return rc2;
-                TmpDev tmp, ovf;
-                const size_t nt = T.size(), bytes = (3 * nt + 1) * 8 + nt * 4;
-                if ((rc2 = tmp.alloc(bytes)) || (rc2 = ovf.alloc(8))) return rc2;
-                HIP_TRY(hipMemset(ovf.p, 0, 8));
-                uint64_t *t_first = tmp.as<uint64_t>(), *t_nr = t_first + nt, *t_doff = t_nr + nt;
-                uint32_t *t_sh = reinterpret_cast<uint32_t *>(t_doff + nt + 1);
-                HIP_TRY(hipMemcpy(t_first, first.data(), nt * 8, hipMemcpyHostToDevice));
-                HIP_TRY(hipMemcpy(t_nr, nr.data(), nt * 8, hipMemcpyHostToDevice));
-                HIP_TRY(hipMemcpy(t_doff, doff.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
-                HIP_TRY(hipMemcpy(t_sh, dshift.data(), nt * 4, hipMemcpyHostToDevice));
-                HIP_TRY(static_cast<hipError_t>(launch_run_recs2(sizeof(P), abs_ent, t_first, t_nr, t_doff, t_sh, static_cast<uint32_t>(nt), doff[nt], recp, ovf.as<unsigned long long>(), nullptr)));
-                HIP_TRY(hipMemcpy(&novf, ovf.p, 8, hipMemcpyDeviceToHost));
-                return 0;
-            };
-            if ((rc = build_recs())) return rc;
-            // Overflowing records (more than eleven entries: pivots + a scan of the run list, two or three sectors instead of one) come from how a locus's runs
-            // cluster, whatever the geometry: on the bench index 4.9 % of the uniform depth-8 records against 4.7 % under the tables' own shifts.  So a uniform
-            // depth with MANY of them is measured against the tables' own shifts, not against zero: it stays when it overflows at most a quarter more often.
-            if (uniform && uni_env != 1 && static_cast<double>(novf) * 256.0 > static_cast<double>(doff[T.size()])) {
-                const std::vector<uint32_t> uni_shift = dshift;
-                const std::vector<uint64_t> uni_off = doff;
-                const unsigned long long novf_uni = novf;
-                free_tracked(ix, recp);
-                recp = nullptr;
-                dshift = own_shift;
-                doff = own_off;
-                if ((rc = build_recs())) return rc;
-                const unsigned long long novf_own = novf;
-                if (static_cast<double>(novf_uni) <= 1.25 * static_cast<double>(novf_own) + static_cast<double>(uni_off[T.size()]) / 256.0) {
-                    free_tracked(ix, recp);
-                    recp = nullptr;
-                    dshift = uni_shift;
-                    doff = uni_off;
-                    if ((rc = build_recs())) return rc;
-                } else {
-                    uniform = false;
-                    if (std::getenv("RBG_VERBOSE"))
-                        std::fprintf(stderr, "rbg:   depth %u: uniform directories would leave %llu records overflowing, the tables' own shifts %llu: the tables keep their own shifts\n",
-                                     d + 1, novf_uni, novf_own);
-                }
-            }
-            if (uniform) {
-                const uint64_t stride = doff[1] - doff[0];
-                if (stride >> 27) return RBG_EARG;   // (load_run_tab's packed constants: a 27-bit stride, a 5-bit shift, a 24-bit first record)
-                ix->dev.run_uni_depth = d; ix->dev.run_uni_stride = static_cast<uint32_t>(stride); ix->dev.run_uni_shift = dshift[0];
-                if (std::getenv("RBG_VERBOSE"))
-                    std::fprintf(stderr, "rbg:   depth %u: uniform directories (shift %u, %llu records per table, %llu of %llu overflowing): hot words computed\n", d + 1, dshift[0],
-                                 static_cast<unsigned long long>(stride), novf, static_cast<unsigned long long>(doff[T.size()]));
-            }
-            ix->dev.run_rec2[d] = static_cast<const RunRec2 *>(recp);
-            rep.rec_bytes[d] = doff[T.size()] * sizeof(RunRec2);
-            rep.rec_overflow[d] = novf;
-        } else {
-        if ((rc = dev_reserve(ix, doff[T.size()] * dir_ent + 16, &dirp))) return rc;
-        {
-            TmpDev tmp;
-            const size_t nt = T.size(), bytes = (3 * nt + 1) * 8 + nt * 4;
-            if ((rc = tmp.alloc(bytes))) return rc;
-            uint64_t *t_first = tmp.as<uint64_t>(), *t_nr = t_first + nt, *t_doff = t_nr + nt;
-            uint32_t *t_sh = reinterpret_cast<uint32_t *>(t_doff + nt + 1);
-            HIP_TRY(hipMemcpy(t_first, first.data(), nt * 8, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(t_nr, nr.data(), nt * 8, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(t_doff, doff.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(t_sh, dshift.data(), nt * 4, hipMemcpyHostToDevice));
-            if constexpr (W) HIP_TRY(static_cast<hipError_t>(launch_run_dirs2(abs_ent, t_first, t_nr, t_doff, t_sh, static_cast<uint32_t>(nt), doff[nt], dirp, nullptr)));
-            else HIP_TRY(static_cast<hipError_t>(launch_run_dirs(4, abs_ent, t_first, t_nr, t_doff, t_sh, static_cast<uint32_t>(nt), doff[nt], static_cast<uint32_t *>(dirp), nullptr)));
-            HIP_TRY(hipDeviceSynchronize());
-        }
-        rep.dir_bytes[d] = doff[T.size()] * dir_ent;
-        }
-        ix->dev.run_dir2[d] = dirp;
-        // ---- the entries and samples in their final form ----
-        if constexpr (W) {
-            void *e2 = nullptr, *s6 = nullptr;
-            if ((rc = dev_reserve(ix, (E2 + 2) * 8, &e2))) return rc;
-            HIP_TRY(static_cast<hipError_t>(launch_pack_pairs32(abs_ent, E2, 2, e2, nullptr)));
-            if (abs_samp) {
-                if ((rc = dev_reserve(ix, E2 * RunsFmt<P>::samp_bytes + 8, &s6))) return rc;
-                HIP_TRY(static_cast<hipError_t>(launch_pack_samp48(static_cast<const uint64_t *>(abs_samp), E2, s6, nullptr)));
-            }
-            HIP_TRY(hipDeviceSynchronize());
-            free_tracked(ix, abs_ent);
-            if (abs_samp) free_tracked(ix, abs_samp);
-            ix->dev.run_ent2[d] = e2;
-            ix->dev.run_samp[d] = s6;
-        } else {
-            ix->dev.run_ent2[d] = abs_ent;
-            ix->dev.run_samp[d] = abs_samp;
-        }
-        if (std::getenv("RBG_VERBOSE")) {
-            size_t f = 0, tt = 0;
-            (void)hipMemGetInfo(&f, &tt);
-            std::fprintf(stderr, "rbg:   run lists of depth %u in their final form: %llu entries (%llu fillers), directories %.2f GB; HBM in use %.1f GB\n", d + 1,
-                         static_cast<unsigned long long>(E2), static_cast<unsigned long long>(fillers), rep.dir_bytes[d] / 1e9, static_cast<double>(tt - f) / 1e9);
-        }
-        for (size_t t = 0; t < T.size(); ++t) {
-            tabs.push_back(DevRunTab2{T[t].F, first[t], doff[t], dshift[t], 0u});
-            if (doff[t] >> kRunHotShiftBit) return RBG_EARG;   // (2^56 buckets: no index that fits a device comes near)
-            hot.push_back(doff[t] | static_cast<uint64_t>(dshift[t]) << kRunHotShiftBit);
-        }
-        tabs.push_back(DevRunTab2{0, E2, 0, 0u, 0u});   // closing record
-        hot.push_back(0);
+    if ((rc = dev_upload(L.ix, ent.data(), (entries + 2) * sizeof(RunEnt<P>), &up))) return rc;
+    R.abs_ent = const_cast<void *>(up);
+    if (h.has_tsa) {
+        if ((rc = dev_upload(L.ix, samp.data(), (entries + 2) * sizeof(P), &up))) return rc;
+        R.abs_samp = const_cast<void *>(up);
     }
+    return RBG_OK;
+}
+
+// the depth's {start, cum} pairs and samples on the device: the level composed there is adopted, else the host tables are converted
+template <typename P>
+int depth_lists_on_device(RunLoad &L, RunDepth &R) {
+    rbg_index *ix = L.ix;
+    const uint32_t d = R.d;
+    ComposedLevel *lv = (d >= 1 && d - 1 < ix->kmer_levels.size() && ix->kmer_levels[d - 1].ent) ? &ix->kmer_levels[d - 1] : nullptr;
+    if (!lv) return convert_host_tables<P>(L, R);
+    if (lv->entries != R.E2 || lv->first.size() != R.nt()) return RBG_EARG;
+    for (size_t t = 0; t < R.nt(); ++t)
+        if (lv->first[t] != R.first[t]) return RBG_EARG;
+    R.abs_ent = lv->ent;
+    R.abs_samp = L.h.has_tsa ? lv->samp : nullptr;
+    lv->ent = lv->samp = nullptr;   // (adopted: the index's allocation list keeps them)
+    return RBG_OK;
+}
+
+// fillers (8-byte positions only: add_fillers), then the limit a table's entries must stay under
+template <typename P>
+int depth_fillers(RunLoad &L, RunDepth &R) {
+    if constexpr (sizeof(P) == 8) {
+        std::vector<uint64_t> at;
+        for (size_t t = 0; t < R.nt(); ++t) { at.push_back(R.first[t]); at.push_back(R.first[t] + R.nr[t]); }
+        if (const int rc = add_fillers(L.ix, false, &R.abs_ent, &R.abs_samp, true, &R.E2, L.h.n, at, &R.fillers)) return rc;
+        if (R.fillers) {
+            for (size_t t = 0; t < R.nt(); ++t) { R.first[t] = at[2 * t]; R.nr[t] = at[2 * t + 1] - at[2 * t]; }
+            R.first[R.nt()] = R.E2;
+        }
+    }
+    for (size_t t = 0; t < R.nt(); ++t)
+        if (R.nr[t] >= 0xFFFFFFF0ull) {
+            std::fprintf(stderr, "rbg: a table of k-mer depth %u has %llu entries: the run-indexed layout holds fewer than 2^32 - 16 per table\n", R.d + 1,
+                         static_cast<unsigned long long>(R.nr[t]));
+            return RBG_EARG;
+        }
+    L.ix->runs_report.entries[R.d] = R.E2;
+    L.ix->runs_report.fillers[R.d] = R.fillers;
+    return RBG_OK;
+}
+
+// every cum becomes a ROW of the F column: + the table's F (rbg_dev.h kRunHotShiftBit; k_build.hip k_fold_F)
+template <typename P>
+int fold_F(RunLoad &L, RunDepth &R) {
+    TmpDev tf;
+    const size_t nt = R.nt();
+    if (const int rc = tf.alloc((2 * nt + 1) * 8)) return rc;
+    std::vector<uint64_t> Fv(nt);
+    for (size_t t = 0; t < nt; ++t) Fv[t] = R.T[t].F;
+    uint64_t *t_first = tf.as<uint64_t>(), *t_F = t_first + nt + 1;
+    HIP_TRY(hipMemcpy(t_first, R.first.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(t_F, Fv.data(), nt * 8, hipMemcpyHostToDevice));
+    // (4-byte positions: the two spare entries are final too)
+    HIP_TRY(static_cast<hipError_t>(launch_fold_F(sizeof(P), R.abs_ent, t_first, t_F, static_cast<uint32_t>(nt), R.E2 + (sizeof(P) == 8 ? 0 : 2), nullptr)));
+    HIP_TRY(hipDeviceSynchronize());
+    return RBG_OK;
+}
+
+// the per-table geometry of a depth (first, nr, b.off, b.shift) in device scratch: what the directory and the record kernels read
+struct DevTableGeometry {
+    TmpDev tmp;
+    uint64_t *first = nullptr, *nr = nullptr, *off = nullptr;
+    uint32_t *shift = nullptr;
+    int upload(const RunDepth &R) {
+        const size_t nt = R.nt();
+        if (const int rc = tmp.alloc((3 * nt + 1) * 8 + nt * 4)) return rc;
+        first = tmp.as<uint64_t>(), nr = first + nt, off = nr + nt;
+        shift = reinterpret_cast<uint32_t *>(off + nt + 1);
+        HIP_TRY(hipMemcpy(first, R.first.data(), nt * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(nr, R.nr.data(), nt * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(off, R.b.off.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(shift, R.b.shift.data(), nt * 4, hipMemcpyHostToDevice));
+        return RBG_OK;
+    }
+};
+
+// directories: per table the widest bucket that still holds at most about dir_target entries on average
+template <typename P>
+int build_depth_directory(RunLoad &L, RunDepth &R) {
+    constexpr bool W = sizeof(P) == 8;
+    R.own_buckets(L.sw.dir_target, L.h.n, L.max_shift);
+    void *dirp = nullptr;
+    const size_t dir_ent = W ? sizeof(RunDir64) : 4;
+    const uint32_t nt = static_cast<uint32_t>(R.nt());
+    int rc;
+    if ((rc = dev_reserve(L.ix, R.buckets() * dir_ent + 16, &dirp))) return rc;
+    DevTableGeometry g;
+    if ((rc = g.upload(R))) return rc;
+    if constexpr (W) HIP_TRY(static_cast<hipError_t>(launch_run_dirs2(R.abs_ent, g.first, g.nr, g.off, g.shift, nt, R.buckets(), dirp, nullptr)));
+    else HIP_TRY(static_cast<hipError_t>(launch_run_dirs(4, R.abs_ent, g.first, g.nr, g.off, g.shift, nt, R.buckets(), static_cast<uint32_t *>(dirp), nullptr)));
+    HIP_TRY(hipDeviceSynchronize());
+    L.ix->runs_report.dir_bytes[R.d] = R.buckets() * dir_ent;
+    L.ix->dev.run_dir2[R.d] = dirp;
+    return RBG_OK;
+}
+
+// the depth's bucket records under the buckets R.b as they stand: *recp, and how many overflow their record
+template <typename P>
+int build_records(RunLoad &L, RunDepth &R, void **recp, unsigned long long *novf) {
+    int rc;
+    if ((rc = dev_reserve(L.ix, R.buckets() * sizeof(RunRec2) + 64, recp))) return rc;
+    DevTableGeometry g;
+    TmpDev ovf;
+    if ((rc = g.upload(R)) || (rc = ovf.alloc(8))) return rc;
+    HIP_TRY(hipMemset(ovf.p, 0, 8));
+    HIP_TRY(static_cast<hipError_t>(launch_run_recs2(sizeof(P), R.abs_ent, g.first, g.nr, g.off, g.shift, static_cast<uint32_t>(R.nt()), R.buckets(), *recp,
+                                                     ovf.as<unsigned long long>(), nullptr)));
+    HIP_TRY(hipMemcpy(novf, ovf.p, 8, hipMemcpyDeviceToHost));
+    return RBG_OK;
+}
+
+// A uniform depth whose records overflow often (rbg_load_plan.hpp uniform_needs_comparison) against the tables' own buckets: the records are built under
+// those, counted, and -- when uniform stays -- built a third time.  One record array at a time: two would raise the load's peak.
+template <typename P>
+int compare_uniform_with_own(RunLoad &L, RunDepth &R, const TableBuckets &own, void **recp, unsigned long long *novf, bool *uniform) {
+    const TableBuckets uni = R.b;
+    const unsigned long long novf_uni = *novf;
+    int rc;
+    free_tracked(L.ix, *recp);
+    *recp = nullptr;
+    R.b = own;
+    if ((rc = build_records<P>(L, R, recp, novf))) return rc;
+    const unsigned long long novf_own = *novf;
+    if (uniform_stays(novf_uni, novf_own, uni.off[R.nt()])) {
+        free_tracked(L.ix, *recp);
+        *recp = nullptr;
+        R.b = uni;
+        return build_records<P>(L, R, recp, novf);
+    }
+    *uniform = false;
+    if (L.sw.verbose)
+        std::fprintf(stderr, "rbg:   depth %u: uniform directories would leave %llu records overflowing, the tables' own shifts %llu: the tables keep their own shifts\n",
+                     R.d + 1, novf_uni, novf_own);
+    return RBG_OK;
+}
+
+// bucket records instead of the directory: per table the widest bucket with at most rec_per[d] entries starting inside on average -- or, for the deepest
+// depth beyond the LDS-staged ones, one shift and one record count for all its tables (rbg_load_plan.hpp uniform_candidate and the verdict after counting)
+template <typename P>
+int build_depth_records(RunLoad &L, RunDepth &R) {
+    rbg_index *ix = L.ix;
+    const uint32_t d = R.d;
+    const size_t nt = R.nt();
+    R.own_buckets(L.rec_per[d], L.h.n, L.max_shift);
+    const TableBuckets own = R.b;
+    double total_runs = 0;
+    for (size_t t = 0; t < nt; ++t) total_runs += static_cast<double>(R.nr[t]);
+    const UniformCandidate cand = uniform_candidate(deepest_with_records(L.rec_per, L.mask, d, L.D), d, nt, L.tabs.size(), total_runs, own.off[nt], L.rec_per[d], L.h.n,
+                                                    L.max_shift, L.sw.uniform, L.consts);
+    bool uniform = cand.eligible;
+    if (uniform)
+        for (size_t t = 0; t < nt; ++t) { R.b.shift[t] = cand.shift; R.b.off[t + 1] = R.b.off[t] + cand.stride; }
+    void *recp = nullptr;
+    unsigned long long novf = 0;
+    int rc;
+    if ((rc = build_records<P>(L, R, &recp, &novf))) return rc;
+    if (uniform && uniform_needs_comparison(novf, R.buckets(), L.sw.uniform) && (rc = compare_uniform_with_own<P>(L, R, own, &recp, &novf, &uniform))) return rc;
+    if (uniform) {
+        const uint64_t stride = R.b.off[1] - R.b.off[0];
+        if (!uniform_stride_fits(stride, L.consts)) return RBG_EARG;   // (load_run_tab's packed constants: a 27-bit stride, a 5-bit shift, a 24-bit first record)
+        ix->dev.run_uni_depth = d; ix->dev.run_uni_stride = static_cast<uint32_t>(stride); ix->dev.run_uni_shift = R.b.shift[0];
+        if (L.sw.verbose)
+            std::fprintf(stderr, "rbg:   depth %u: uniform directories (shift %u, %llu records per table, %llu of %llu overflowing): hot words computed\n", d + 1, R.b.shift[0],
+                         static_cast<unsigned long long>(stride), novf, static_cast<unsigned long long>(R.buckets()));
+    }
+    ix->dev.run_rec2[d] = static_cast<const RunRec2 *>(recp);
+    ix->runs_report.rec_bytes[d] = R.buckets() * sizeof(RunRec2);
+    ix->runs_report.rec_overflow[d] = novf;
+    return RBG_OK;
+}
+
+// the entries and samples in their final form: at 8-byte positions the low-word pairs and the 6-byte samples, and the lists of P go back
+template <typename P>
+int pack_depth_final(RunLoad &L, RunDepth &R) {
+    rbg_index *ix = L.ix;
+    if constexpr (sizeof(P) == 8) {
+        void *e2 = nullptr, *s6 = nullptr;
+        int rc;
+        if ((rc = dev_reserve(ix, (R.E2 + 2) * 8, &e2))) return rc;
+        HIP_TRY(static_cast<hipError_t>(launch_pack_pairs32(R.abs_ent, R.E2, 2, e2, nullptr)));
+        if (R.abs_samp) {
+            if ((rc = dev_reserve(ix, R.E2 * RunsFmt<P>::samp_bytes + 8, &s6))) return rc;
+            HIP_TRY(static_cast<hipError_t>(launch_pack_samp48(static_cast<const uint64_t *>(R.abs_samp), R.E2, s6, nullptr)));
+        }
+        HIP_TRY(hipDeviceSynchronize());
+        free_tracked(ix, R.abs_ent);
+        if (R.abs_samp) free_tracked(ix, R.abs_samp);
+        ix->dev.run_ent2[R.d] = e2;
+        ix->dev.run_samp[R.d] = s6;
+    } else {
+        ix->dev.run_ent2[R.d] = R.abs_ent;
+        ix->dev.run_samp[R.d] = R.abs_samp;
+    }
+    if (L.sw.verbose) {
+        size_t f = 0, tt = 0;
+        (void)hipMemGetInfo(&f, &tt);
+        std::fprintf(stderr, "rbg:   run lists of depth %u in their final form: %llu entries (%llu fillers), directories %.2f GB; HBM in use %.1f GB\n", R.d + 1,
+                     static_cast<unsigned long long>(R.E2), static_cast<unsigned long long>(R.fillers), ix->runs_report.dir_bytes[R.d] / 1e9, static_cast<double>(tt - f) / 1e9);
+    }
+    return RBG_OK;
+}
+
+// the depth's DevRunTab2 records and hot words, closed by one more
+int append_depth_tables(RunLoad &L, const RunDepth &R) {
+    for (size_t t = 0; t < R.nt(); ++t) {
+        L.tabs.push_back(DevRunTab2{R.T[t].F, R.first[t], R.b.off[t], R.b.shift[t], 0u});
+        if (R.b.off[t] >> kRunHotShiftBit) return RBG_EARG;   // (2^56 buckets: no index that fits a device comes near)
+        L.hot.push_back(R.b.off[t] | static_cast<uint64_t>(R.b.shift[t]) << kRunHotShiftBit);
+    }
+    L.tabs.push_back(DevRunTab2{0, R.E2, 0, 0u, 0u});   // closing record
+    L.hot.push_back(0);
+    return RBG_OK;
+}
+
+// one kept depth: its lists, fillers, folded F, directory or records, final form, table records
+template <typename P>
+int upload_run_depth(RunLoad &L, uint32_t d, const std::vector<SymTable> &T) {
+    RunDepth R(d, T);
+    L.ix->dev.run_rec2[d] = nullptr;
+    int rc;
+    if ((rc = depth_lists_on_device<P>(L, R))) return rc;
+    if ((rc = depth_fillers<P>(L, R))) return rc;
+    if ((rc = fold_F<P>(L, R))) return rc;
+    if ((rc = L.rec_per[d] > 0 ? build_depth_records<P>(L, R) : build_depth_directory<P>(L, R))) return rc;
+    if ((rc = pack_depth_final<P>(L, R))) return rc;
+    return append_depth_tables(L, R);
+}
+
+// the table index: syms, run_tabs2, run_hot and the scalar fields of the layout
+int upload_table_index(RunLoad &L) {
+    rbg_index *ix = L.ix;
+    HostIndex &h = L.h;
+    const uint32_t D = L.D;
     for (uint32_t d = 2; d <= static_cast<uint32_t>(kMaxKmerDepth); ++d) release_kmer_level(ix, d);   // (levels beyond D, or left over: nothing points at them)
-    for (uint32_t d = D; d <= static_cast<uint32_t>(kMaxRunDepth); ++d) ix->dev.run_tab_first[d] = static_cast<uint32_t>(tabs.size());
+    for (uint32_t d = D; d <= static_cast<uint32_t>(kMaxRunDepth); ++d) ix->dev.run_tab_first[d] = static_cast<uint32_t>(L.tabs.size());
     if (ix->dev.run_tab_first[std::min<uint32_t>(D, kLdsRunDepth)] > static_cast<uint32_t>(kMaxLdsRunTabs)) return RBG_EARG;
     const void *p = nullptr;
+    int rc;
     std::vector<DevSym> syms(h.sym.size());   // (no kernel reads a symbol record on this format: F only, for rbg_get_f-style readers)
     for (size_t t = 0; t < syms.size(); ++t) { syms[t] = DevSym{}; syms[t].F = h.sym[t].F; syms[t].nruns = static_cast<uint32_t>(std::min<uint64_t>(h.sym[t].nruns, 0xFFFFFFFFull)); }
     if ((rc = dev_upload(ix, syms.data(), syms.size() * sizeof(DevSym), &p))) return rc;
     ix->dev.syms = static_cast<const DevSym *>(p);
-    if ((rc = dev_upload(ix, tabs.data(), tabs.size() * sizeof(DevRunTab2), &p))) return rc;
+    if ((rc = dev_upload(ix, L.tabs.data(), L.tabs.size() * sizeof(DevRunTab2), &p))) return rc;
     ix->dev.run_tabs2 = static_cast<const DevRunTab2 *>(p);
-    if ((rc = dev_upload(ix, hot.data(), hot.size() * 8, &p))) return rc;
+    if ((rc = dev_upload(ix, L.hot.data(), L.hot.size() * 8, &p))) return rc;
     ix->dev.run_hot = static_cast<const uint64_t *>(p);
-    ix->dev.run_ntabs = static_cast<uint32_t>(tabs.size());
+    ix->dev.run_ntabs = static_cast<uint32_t>(L.tabs.size());
     ix->dev.run_ksteps = D;
-    ix->dev.run_depth_mask = mask;
-    ix->run_depth_mask = mask;
-    rep.depth_mask_kept = mask;
-    rep.rank_dirs = all_recs ? 0 : 1;   // (1: some kept depth answers its ranks through a directory)
-    (void)any_recs;
+    ix->dev.run_depth_mask = L.mask;
+    ix->run_depth_mask = L.mask;
+    ix->runs_report.depth_mask_kept = L.mask;
+    bool all_recs = true;
+    for (uint32_t d = 0; d < D; ++d)
+        if (L.mask >> d & 1u) all_recs = all_recs && L.rec_per[d] > 0;
+    ix->runs_report.rank_dirs = all_recs ? 0 : 1;   // (1: some kept depth answers its ranks through a directory)
     ix->dev.layout = RBG_LAYOUT_RUNS;
     ix->dev.kmer_steps = 1;
     ix->dev.nmajor = 0;
@@ -390,140 +485,170 @@ int upload_tables_runs2(rbg_index *ix) {
         ix->dev.lut2 = static_cast<const uint8_t *>(p);
         ix->dev.nmajor = h.nmajor;
     }
-    // the register tables of the in-kernel read staging (rbg_dev.h stage_*): a shift under which the four major bytes hash to four different
-    // three-bit values
-    ix->dev.stage_ok = 0;
-    if (h.nmajor == 4) {
-        for (uint32_t sh = 0; sh <= 5 && !ix->dev.stage_ok; ++sh) {
-            uint8_t code[8] = {0, 0, 0, 0, 0, 0, 0, 0}, byte[8];
-            bool used[8] = {false, false, false, false, false, false, false, false}, distinct = true;
-            for (uint32_t m = 0; m < 4; ++m) {
-                const uint32_t t = (h.major_byte[m] >> sh) & 7u;
-                if (used[t]) distinct = false;
-                used[t] = true;
-                code[t] = static_cast<uint8_t>(m);
-                byte[t] = h.major_byte[m];
-            }
-            if (!distinct) continue;
-            // an unused place must never equal the byte that hashes to it: a byte whose own hash is another place
-            for (uint32_t t = 0; t < 8; ++t)
-                if (!used[t]) byte[t] = static_cast<uint8_t>(((t ^ 1u) & 7u) << sh);
-            ix->dev.stage_ok = 1;
-            ix->dev.stage_shift = sh;
-            std::memcpy(ix->dev.stage_code, code, 8);
-            std::memcpy(ix->dev.stage_byte, byte, 8);
-        }
-    }
+    return RBG_OK;
+}
+
+// the register tables of the in-kernel read staging (rbg_dev.h stage_*; rbg_load_plan.hpp stage_tables)
+void set_stage_tables(RunLoad &L) {
+    DevIndex &dev = L.ix->dev;
+    dev.stage_ok = 0;
+    if (L.h.nmajor != 4) return;
+    const StageTables s = stage_tables(L.h.major_byte);
+    if (!s.ok) return;
+    dev.stage_ok = 1;
+    dev.stage_shift = s.shift;
+    std::memcpy(dev.stage_code, s.code, 8);
+    std::memcpy(dev.stage_byte, s.byte, 8);
+}
+
+// PHI SLOTS (rbg_load_plan.hpp phi_slot_geometry, phi_by_slots): the slot layout's direct-addressed phi records (rbg_dev.h PhiSlot) answer a phi step from ONE
+// sector where the list takes two (directory, entries); at pangenome scale K3 is bound by exactly that sector count.  Cost: about 54 bytes per run at
+// 8-byte positions against 16.
+template <typename P>
+int upload_phi_slots(RunLoad &L, const PhiSlotGeometry &g) {
+    rbg_index *ix = L.ix;
+    HostIndex &h = L.h;
+    rbg_index::RunsReport &rep = ix->runs_report;
+    VStage vs("phi slots of the run-indexed layout", true, L.sw.verbose);
+    HostBuf<PhiEnt<P>> pe(h.r + 1);
+    parallel_for(h.r, [&](uint64_t a, uint64_t b, unsigned) {
+        for (uint64_t j = a; j < b; ++j) { pe[j].pos = static_cast<P>(h.pred_pos[j]); pe[j].base = static_cast<P>(h.phi_base[j]); }
+    });
+    pe[h.r].pos = static_cast<P>(h.n); pe[h.r].base = 0;
+    int rc;
+    if ((rc = dev_upload(ix, pe.data(), (h.r + 1) * sizeof(PhiEnt<P>), &ix->dev.phi_ent))) return rc;
+    const uint64_t nb = g.buckets;
+    void *slots = nullptr, *ord = nullptr;
+    if ((rc = dev_reserve(ix, nb * g.slot_bytes(), &slots)) || (rc = dev_reserve(ix, nb * sizeof(uint32_t), &ord))) return rc;
+    TmpDev ovf;
+    if ((rc = ovf.alloc(8))) return rc;
+    HIP_TRY(hipMemset(ovf.p, 0, 8));
+    ix->dev.phi_packed = g.packed ? 1 : 0;
+    ix->dev.phi_shift = g.shift;
+    if (launch_build_phi_slots(sizeof(P), g.packed, ix->dev.phi_ent, h.r, h.n, g.shift, slots, static_cast<uint32_t *>(ord), ovf.as<unsigned long long>(), nullptr))
+        return RBG_ENODEV;
+    unsigned long long novf = 0;
+    HIP_TRY(hipMemcpy(&novf, ovf.p, 8, hipMemcpyDeviceToHost));
+    ix->phi_slots = nb;
+    ix->phi_slots_overflow = novf;
+    ix->dev.phi_slots = slots;
+    ix->dev.phi_ord = static_cast<const uint32_t *>(ord);
+    ix->dev.phi_m = h.r;
+    ix->dev.phi_last_pos = h.pred_pos[h.r - 1];
+    ix->dev.phi_last_base = h.phi_base[h.r - 1];
+    rep.phi_entries = h.r; rep.phi_dir = 0; rep.phi_dir_shift = g.shift; rep.phi_slots = nb; rep.phi_slot_bytes = nb * g.bucket_bytes;
+    return RBG_OK;
+}
+
+// the phi list at 8-byte positions: fillers, 12-byte entries of low words, the directory with 64-bit super counts under its 32-bit ones
+int upload_phi_list_wide(RunLoad &L, uint32_t ds, uint64_t nd, void *dirp, uint64_t *m2, uint64_t *fillers) {
+    rbg_index *ix = L.ix;
+    HostIndex &h = L.h;
+    HostBuf<uint64_t> pe((h.r + 1) * 2);
+    parallel_for(h.r, [&](uint64_t a, uint64_t b, unsigned) {
+        for (uint64_t j = a; j < b; ++j) { pe[2 * j] = h.pred_pos[j]; pe[2 * j + 1] = h.phi_base[j]; }
+    });
+    pe[2 * h.r] = h.n; pe[2 * h.r + 1] = 0;   // sentinel: never below a query
+    void *abs = nullptr, *none = nullptr;
+    HIP_TRY(hipMalloc(&abs, (h.r + 1 + 2) * 16));
+    int rc;
+    if ((rc = h2d_big(abs, pe.data(), (h.r + 1) * 16))) { (void)hipFree(abs); return rc; }
+    uint64_t m_all = h.r + 1;
+    std::vector<uint64_t> at;
+    rc = add_fillers(ix, true, &abs, &none, false, &m_all, h.n, at, fillers);
+    if (rc) { (void)hipFree(abs); return rc; }
+    *m2 = m_all - 1;
+    void *e12 = nullptr, *sup = nullptr;
+    const uint64_t nsup = (nd >> L.sw.super_shift) + 2;
+    rc = dev_reserve(ix, (*m2 + 1 + 3) * sizeof(PhiEnt12), &e12);
+    if (!rc) rc = dev_reserve(ix, nsup * 8, &sup);
+    hipError_t e = hipSuccess;
+    if (!rc) e = static_cast<hipError_t>(launch_pack_phi12(abs, *m2 + 1, 3, e12, nullptr));
+    if (!rc && e == hipSuccess) e = static_cast<hipError_t>(launch_phi_dir(8, abs, *m2, ds, nd, static_cast<uint32_t *>(dirp), L.sw.super_shift, static_cast<uint64_t *>(sup), nullptr));
+    if (!rc && e == hipSuccess) e = hipDeviceSynchronize();
+    (void)hipFree(abs);
+    if (rc) return rc;
+    HIP_TRY(e);
+    ix->dev.phi_ent = e12;
+    ix->dev.phi_super = static_cast<const uint64_t *>(sup);
+    ix->dev.phi_super_shift = L.sw.super_shift;
+    return RBG_OK;
+}
+
+// the phi list at 4-byte positions: the host's entries as they are, and the directory
+int upload_phi_list_narrow(RunLoad &L, uint32_t ds, uint64_t nd, void *dirp) {
+    rbg_index *ix = L.ix;
+    HostIndex &h = L.h;
+    typedef PhiFmt<uint32_t> Fmt;
+    HostBuf<unsigned char> pe((h.r + 1 + Fmt::spare) * Fmt::ent_bytes);
+    parallel_for(h.r, [&](uint64_t a, uint64_t b, unsigned) {
+        for (uint64_t j = a; j < b; ++j) Fmt::put_ent(pe.data(), j, h.pred_pos[j], h.phi_base[j]);
+    });
+    for (size_t x = 0; x <= Fmt::spare; ++x) Fmt::put_ent(pe.data(), h.r + x, h.n, 0);
+    if (const int rc = dev_upload(ix, pe.data(), pe.size(), &ix->dev.phi_ent)) return rc;
+    HIP_TRY(static_cast<hipError_t>(launch_phi_dir(4, ix->dev.phi_ent, h.r, ds, nd, static_cast<uint32_t *>(dirp), 0, nullptr, nullptr)));
+    HIP_TRY(hipDeviceSynchronize());
+    return RBG_OK;
+}
+
+// phi over the list of sampled positions and its directory (rbg_load_plan.hpp phi_dir_shift)
+template <typename P>
+int upload_phi_list(RunLoad &L) {
+    rbg_index *ix = L.ix;
+    HostIndex &h = L.h;
+    rbg_index::RunsReport &rep = ix->runs_report;
+    const uint32_t ds = phi_dir_shift(h.r, h.n, L.sw.phi_per, L.max_shift);
+    const uint64_t nd = (h.n >> ds) + 2;
+    void *dirp = nullptr;
+    int rc;
+    if ((rc = dev_reserve(ix, nd * 4 + 16, &dirp))) return rc;
+    uint64_t m2 = h.r, fillers = 0;
+    if constexpr (sizeof(P) == 8) rc = upload_phi_list_wide(L, ds, nd, dirp, &m2, &fillers);
+    else rc = upload_phi_list_narrow(L, ds, nd, dirp);
+    if (rc) return rc;
+    ix->dev.phi_dir = static_cast<const uint32_t *>(dirp);
+    ix->dev.phi_dir_shift = ds;
+    ix->dev.phi_m = m2;
+    ix->dev.phi_last_pos = h.pred_pos[h.r - 1];
+    ix->dev.phi_last_base = h.phi_base[h.r - 1];
+    rep.phi_entries = m2; rep.phi_fillers = fillers; rep.phi_dir_bytes = nd * 4; rep.phi_dir_shift = ds; rep.phi_dir = 1;
+    return RBG_OK;
+}
+
+// phi as slots, or as list + directory
+template <typename P>
+int upload_phi(RunLoad &L) {
+    rbg_index *ix = L.ix;
     ix->dev.phi_slots = nullptr;
     ix->dev.phi_ord = nullptr;
     ix->dev.phi_dir = nullptr;
     ix->dev.phi_super = nullptr;
     ix->dev.phi_super_shift = 0;
-    // PHI SLOTS on this layout (RBG_OPT_RUN_PHI = 2; automatic when the whole replica then stays within the budget -- the bucket records of the
-    // rank tables, decided before, have left room for them: K3 is the larger kernel at pangenome scale): the slot
-    // layout's direct-addressed phi records (rbg_dev.h PhiSlot) with buckets of about n / r rows instead of 32-64 -- so their
-    // number is proportional to r, not n -- answer a phi step from ONE sector where the list takes two (directory, entries); at
-    // pangenome scale K3 is bound by exactly that sector count.  Cost: about 54 bytes per run at 8-byte positions against 16.
-    bool phi_by_slots = false;
-    uint32_t slot_shift = 0;
-    if (h.has_tsa) {
-        const double rows_per_sample = static_cast<double>(h.n) / static_cast<double>(std::max<uint64_t>(1, h.r));
-        while (slot_shift < 8 && static_cast<double>(uint64_t(2) << slot_shift) <= rows_per_sample) ++slot_shift;   // the widest bucket with at most one sampled position on average
-        if (slot_shift < h.phi_shift) slot_shift = h.phi_shift;
-        const bool packed = sizeof(P) == 8 && (h.n >> kPhiPackedPosBits) == 0 && slot_shift <= kPhiPackedMaxShift;
-        const size_t slot_b = packed ? sizeof(PhiSlotPacked) : sizeof(PhiSlot<P>);
-        const size_t need = ((h.n >> slot_shift) + 2) * (slot_b + 4) + (h.r + 1) * sizeof(PhiEnt<P>);
-        const int64_t mode = g_opt_run_phi.load();
-        // automatic: only while the slots are O(r) -- at most two buckets per sampled position (the bucket shift stops at 8: an index with
-        // n / r far beyond 256 would get n / 256 of them) -- and the whole replica stays within the budget
-        phi_by_slots = mode == 2 || (mode == 0 && ix->hbm_budget && ((h.n >> slot_shift) + 2) <= 2 * h.r && ix->hbm_bytes + need <= ix->hbm_budget);
-        if (phi_by_slots) {
-            VStage vs("phi slots of the run-indexed layout");
-            HostBuf<PhiEnt<P>> pe(h.r + 1);
-            parallel_for(h.r, [&](uint64_t a, uint64_t b, unsigned) {
-                for (uint64_t j = a; j < b; ++j) { pe[j].pos = static_cast<P>(h.pred_pos[j]); pe[j].base = static_cast<P>(h.phi_base[j]); }
-            });
-            pe[h.r].pos = static_cast<P>(h.n); pe[h.r].base = 0;
-            if ((rc = dev_upload(ix, pe.data(), (h.r + 1) * sizeof(PhiEnt<P>), &ix->dev.phi_ent))) return rc;
-            const uint64_t nb = (h.n >> slot_shift) + 2;
-            void *slots = nullptr, *ord = nullptr;
-            if ((rc = dev_reserve(ix, nb * slot_b, &slots)) || (rc = dev_reserve(ix, nb * sizeof(uint32_t), &ord))) return rc;
-            TmpDev ovf;
-            if ((rc = ovf.alloc(8))) return rc;
-            HIP_TRY(hipMemset(ovf.p, 0, 8));
-            ix->dev.phi_packed = packed ? 1 : 0;
-            ix->dev.phi_shift = slot_shift;
-            if (launch_build_phi_slots(sizeof(P), packed, ix->dev.phi_ent, h.r, h.n, slot_shift, slots, static_cast<uint32_t *>(ord), ovf.as<unsigned long long>(), nullptr))
-                return RBG_ENODEV;
-            unsigned long long novf = 0;
-            HIP_TRY(hipMemcpy(&novf, ovf.p, 8, hipMemcpyDeviceToHost));
-            ix->phi_slots = nb;
-            ix->phi_slots_overflow = novf;
-            ix->dev.phi_slots = slots;
-            ix->dev.phi_ord = static_cast<const uint32_t *>(ord);
-            ix->dev.phi_m = h.r;
-            ix->dev.phi_last_pos = h.pred_pos[h.r - 1];
-            ix->dev.phi_last_base = h.phi_base[h.r - 1];
-            rep.phi_entries = h.r; rep.phi_dir = 0; rep.phi_dir_shift = slot_shift; rep.phi_slots = nb; rep.phi_slot_bytes = nb * (slot_b + 4);
-        }
+    if (!L.h.has_tsa) return RBG_OK;
+    const PhiSlotGeometry g = phi_slot_geometry(L.h.n, L.h.r, L.h.phi_shift, sizeof(P), L.consts);
+    return phi_by_slots(g_opt_run_phi.load(), g, L.h.r, ix->hbm_bytes, ix->hbm_budget) ? upload_phi_slots<P>(L, g) : upload_phi_list<P>(L);
+}
+
+template <typename P>
+int upload_tables_runs2(rbg_index *ix) {
+    RunLoad L(ix, sizeof(P) == 8);   // (reads the switches)
+    ix->runs_report.fmt = 2;
+    release_slot_lists(ix);
+    const std::vector<SymTable> *depth[kMaxRunDepth];
+    settle_depths(L, depth);
+    ix->dev.run_uni_depth = static_cast<uint32_t>(kMaxRunDepth);   // (no uniform depth, until build_depth_records makes one)
+    ix->dev.run_uni_stride = ix->dev.run_uni_shift = 0;
+    int rc;
+    for (uint32_t d = 0; d < L.D; ++d) {
+        ix->dev.run_tab_first[d] = static_cast<uint32_t>(L.tabs.size());
+        ix->dev.run_samp[d] = nullptr;
+        ix->dev.run_ent2[d] = nullptr; ix->dev.run_dir2[d] = nullptr;
+        if (!(L.mask >> d & 1u)) leave_depth_out(L, d);
+        else if ((rc = upload_run_depth<P>(L, d, *depth[d]))) return rc;
     }
-    if (h.has_tsa && !phi_by_slots) {
-        // sampled positions per directory bucket: between per and 2 * per on average (RBG_PHI_DIR_PER, default 1: the scan's
-        // first four requests then cover the bucket and its predecessor nineteen times in twenty)
-        const char *e_pp = std::getenv("RBG_PHI_DIR_PER");
-        const double per = e_pp && std::atof(e_pp) > 0 ? std::atof(e_pp) : 1.0;
-        uint32_t ds = 2;
-        while (ds < max_shift && ds < 30 && (static_cast<double>(h.r) * static_cast<double>(uint64_t(1) << ds)) / static_cast<double>(h.n) < per) ++ds;
-        const uint64_t nd = (h.n >> ds) + 2;
-        void *dirp = nullptr;
-        if ((rc = dev_reserve(ix, nd * 4 + 16, &dirp))) return rc;
-        uint64_t m2 = h.r, fillers = 0;
-        if constexpr (W) {
-                    HostBuf<uint64_t> pe((h.r + 1) * 2);
-            parallel_for(h.r, [&](uint64_t a, uint64_t b, unsigned) {
-                for (uint64_t j = a; j < b; ++j) { pe[2 * j] = h.pred_pos[j]; pe[2 * j + 1] = h.phi_base[j]; }
-            });
-            pe[2 * h.r] = h.n; pe[2 * h.r + 1] = 0;   // sentinel: never below a query
-            void *abs = nullptr, *none = nullptr;
-            HIP_TRY(hipMalloc(&abs, (h.r + 1 + 2) * 16));
-            if ((rc = h2d_big(abs, pe.data(), (h.r + 1) * 16))) { (void)hipFree(abs); return rc; }
-            uint64_t m_all = h.r + 1;
-            std::vector<uint64_t> at;
-            rc = add_fillers(ix, true, &abs, &none, false, &m_all, h.n, at, &fillers);
-            if (rc) { (void)hipFree(abs); return rc; }
-            m2 = m_all - 1;
-            void *e12 = nullptr, *sup = nullptr;
-            const uint64_t nsup = (nd >> super_shift) + 2;
-            rc = dev_reserve(ix, (m2 + 1 + 3) * sizeof(PhiEnt12), &e12);
-            if (!rc) rc = dev_reserve(ix, nsup * 8, &sup);
-            hipError_t e = hipSuccess;
-            if (!rc) e = static_cast<hipError_t>(launch_pack_phi12(abs, m2 + 1, 3, e12, nullptr));
-            if (!rc && e == hipSuccess) e = static_cast<hipError_t>(launch_phi_dir(8, abs, m2, ds, nd, static_cast<uint32_t *>(dirp), super_shift, static_cast<uint64_t *>(sup), nullptr));
-            if (!rc && e == hipSuccess) e = hipDeviceSynchronize();
-            (void)hipFree(abs);
-            if (rc) return rc;
-            HIP_TRY(e);
-            ix->dev.phi_ent = e12;
-            ix->dev.phi_super = static_cast<const uint64_t *>(sup);
-            ix->dev.phi_super_shift = super_shift;
-        } else {
-            typedef PhiFmt<P> Fmt;
-            HostBuf<unsigned char> pe((h.r + 1 + Fmt::spare) * Fmt::ent_bytes);
-            parallel_for(h.r, [&](uint64_t a, uint64_t b, unsigned) {
-                for (uint64_t j = a; j < b; ++j) Fmt::put_ent(pe.data(), j, h.pred_pos[j], h.phi_base[j]);
-            });
-            for (size_t x = 0; x <= Fmt::spare; ++x) Fmt::put_ent(pe.data(), h.r + x, h.n, 0);
-            if ((rc = dev_upload(ix, pe.data(), pe.size(), &ix->dev.phi_ent))) return rc;
-            HIP_TRY(static_cast<hipError_t>(launch_phi_dir(4, ix->dev.phi_ent, h.r, ds, nd, static_cast<uint32_t *>(dirp), 0, nullptr, nullptr)));
-            HIP_TRY(hipDeviceSynchronize());
-        }
-        ix->dev.phi_dir = static_cast<const uint32_t *>(dirp);
-        ix->dev.phi_dir_shift = ds;
-        ix->dev.phi_m = m2;
-        ix->dev.phi_last_pos = h.pred_pos[h.r - 1];
-        ix->dev.phi_last_base = h.phi_base[h.r - 1];
-        rep.phi_entries = m2; rep.phi_fillers = fillers; rep.phi_dir_bytes = nd * 4; rep.phi_dir_shift = ds; rep.phi_dir = 1;
-    }
+    if ((rc = upload_table_index(L))) return rc;
+    set_stage_tables(L);
+    if ((rc = upload_phi<P>(L))) return rc;
     HIP_TRY(hipDeviceSynchronize());
     return RBG_OK;
 }

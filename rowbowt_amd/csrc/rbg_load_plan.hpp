@@ -1,6 +1,7 @@
 // rbg_load_plan.hpp -- what a load puts on the device, decided from plain numbers: the replica budget and its raise, the slot or run-indexed layout, the
-// k-mer depths planned, kept and left out, which depths get bucket records, the ftab and the jump table's share.  capi/load.ipp
-// (upload(), options_for()) and capi/upload_runs.ipp call these; nothing here reads the environment, an option, the device or an rbg_index, and nothing
+// k-mer depths planned, kept and left out, which depths get bucket records, the ftab and the jump table's share -- and the GEOMETRY of the run-indexed
+// layout: bucket shifts of directories and records, the uniform geometry of the deepest depth, the phi slots and the phi directory, the read-staging
+// register tables.  capi/load.ipp (upload(), options_for()) and capi/upload_runs.ipp call these; nothing here reads the environment, an option, the device or an rbg_index, and nothing
 // prints: the callers read those once, pass values in and say on stderr what was decided.  Plain host C++: tests/cpp/load_plan_check.cpp drives it alone.
 #ifndef RBG_LOAD_PLAN_HPP
 #define RBG_LOAD_PLAN_HPP
@@ -23,6 +24,10 @@ struct LoadConsts {
     size_t slot_bytes;                           // a rank slot and its ordinal: sizeof(RankSlot) + sizeof(uint32_t)
     size_t arena_align;                          // kArenaAlign
     size_t runs_samp_bytes[2], phi_ent_bytes[2]; // RunsFmt<P>::samp_bytes, PhiFmt<P>::ent_bytes at [0] 4-byte, [1] 8-byte positions
+    uint32_t lds_run_depth;                      // kLdsRunDepth: the depths whose hot words are staged in LDS (a deeper one may be uniform)
+    uint32_t uni_stride_bits, uni_shift_bits, uni_first_bits;   // rbg_runs2_device.hpp load_run_tab's packed constants of the uniform depth: 27, 5, 24
+    uint32_t phi_packed_pos_bits, phi_packed_max_shift;         // kPhiPackedPosBits, kPhiPackedMaxShift
+    size_t phi_slot_bytes[2], phi_slot_packed_bytes, phi_pair_bytes[2];   // sizeof(PhiSlot<P>), sizeof(PhiSlotPacked), sizeof(PhiEnt<P>)
 };
 
 // ---- the budget ----------------------------------------------------------------------------------------------------------------------------------
@@ -113,6 +118,135 @@ inline BudgetRaise budget_raise(double r, int kmer_steps, size_t free_b, size_t 
     return b;
 }
 
+// ---- the geometry of the run-indexed layout ------------------------------------------------------------------------------------------------------
+// What capi/upload_runs.ipp builds, as functions of plain numbers; the planner below estimates with the same functions.
+// THE BUCKET SHIFT of a directory or of bucket records: the widest bucket that still holds at most `per` entries on average, at most 2^max_shift rows
+// (31 at 4-byte positions; at 8-byte positions the fill shift: a bucket is no wider than the distance the fillers keep).  A table without runs counts as one.
+inline uint32_t bucket_shift(double runs, double per, uint64_t n, uint32_t max_shift) {
+    uint32_t sh = 0;
+    runs = std::max(1.0, runs);
+    while (sh < max_shift && runs * static_cast<double>(uint64_t(2) << sh) <= per * static_cast<double>(n)) ++sh;
+    return sh;
+}
+inline uint64_t bucket_count(uint64_t n, uint32_t shift) { return (n >> shift) + 2; }
+
+// UNIFORM geometry (rbg_dev.h DevIndex::run_uni_*) for a depth whose hot words a step would read from global memory: one shift -- the widest for the
+// depth's AVERAGE table -- and one record count for every table, so that a step computes its table's hot word.  One depth can be uniform: the deepest kept
+// one with records.  uni_switch (RBG_RUN_UNIFORM; tests, A/B): -1 the rules decide, 0 never, 1 whenever the depth is deep enough and the constants pack.
+// (rec_per, mask, D: run_record_plan() below)
+inline bool deepest_with_records(const std::vector<double> &rec_per, uint32_t mask, uint32_t d, uint32_t D) {
+    for (uint32_t d2 = d + 1; d2 < D; ++d2)
+        if ((mask >> d2 & 1u) && rec_per[d2] > 0) return false;
+    return true;
+}
+inline bool uniform_stride_fits(uint64_t stride, const LoadConsts &c) { return !(stride >> c.uni_stride_bits); }
+struct UniformCandidate {
+    bool eligible;
+    uint32_t shift;
+    uint64_t stride;   // records per table
+};
+// The CANDIDATE, before anything is built: eligible when this is the deepest kept depth with records, deeper than the LDS-staged ones, with more than one
+// table; its stride, shift and table ordinals fit load_run_tab's packed constants; and it costs no more than a tenth more records than the tables' own
+// shifts (own_records) -- or the switch forces it.  tables_before: the tables of the shallower depths; total_runs: the entries of this depth's tables.
+inline UniformCandidate uniform_candidate(bool deepest_recs, uint32_t depth_index, size_t tables, size_t tables_before, double total_runs, uint64_t own_records,
+                                          double per, uint64_t n, uint32_t max_shift, int uni_switch, const LoadConsts &c) {
+    UniformCandidate u{false, 0, 0};
+    if (!(deepest_recs && depth_index >= c.lds_run_depth && uni_switch != 0 && tables > 1)) return u;
+    u.shift = bucket_shift(total_runs / static_cast<double>(tables), per, n, max_shift);
+    u.stride = bucket_count(n, u.shift);
+    u.eligible = uniform_stride_fits(u.stride, c) && u.shift < (1u << c.uni_shift_bits) && tables_before + tables < (size_t(1) << c.uni_first_bits) &&
+                 (uni_switch == 1 || static_cast<double>(u.stride) * static_cast<double>(tables) <= 1.1 * static_cast<double>(own_records));
+    return u;
+}
+// The VERDICT, after the uniform records are built and their overflowing buckets counted (more than eleven entries: pivots + a scan of the run list, two
+// or three sectors instead of one).  Those come from how a locus's runs cluster, whatever the geometry: on the bench index 4.9 % of the uniform depth-8
+// records against 4.7 % under the tables' own shifts.  So a uniform depth with MANY of them (more than one record in 256; never when forced) is measured
+// against the tables' own shifts, not against zero: it stays when it overflows at most a quarter more often -- a depth with a few very frequent k-mers
+// keeps per-table shifts.
+inline bool uniform_needs_comparison(uint64_t novf, uint64_t records, int uni_switch) {
+    return uni_switch != 1 && static_cast<double>(novf) * 256.0 > static_cast<double>(records);
+}
+inline bool uniform_stays(uint64_t novf_uni, uint64_t novf_own, uint64_t records_uni) {
+    return static_cast<double>(novf_uni) <= 1.25 * static_cast<double>(novf_own) + static_cast<double>(records_uni) / 256.0;
+}
+
+// PHI SLOTS on this layout (RBG_OPT_RUN_PHI = 2, or automatic): the slot layout's direct-addressed phi records with buckets of about n / r rows -- the
+// widest bucket with at most one sampled position on average, at most 2^8 rows, never narrower than phi's own buckets (phi_shift) -- so that their number
+// is proportional to r, not n.  Packed 16-byte slots at 8-byte positions while n and the shift allow (rbg_dev.h PhiSlotPacked).
+struct PhiSlotBuckets {   // what depends on n, r and phi's own buckets alone: the planner's estimate needs no more
+    uint32_t shift;
+    uint64_t buckets;
+};
+inline PhiSlotBuckets phi_slot_buckets(uint64_t n, uint64_t r, uint32_t phi_shift) {
+    PhiSlotBuckets b{0, 0};
+    const double rows_per_sample = static_cast<double>(n) / static_cast<double>(std::max<uint64_t>(1, r));
+    while (b.shift < 8 && static_cast<double>(uint64_t(2) << b.shift) <= rows_per_sample) ++b.shift;
+    if (b.shift < phi_shift) b.shift = phi_shift;
+    b.buckets = bucket_count(n, b.shift);
+    return b;
+}
+struct PhiSlotGeometry {
+    uint32_t shift;
+    bool packed;
+    size_t bucket_bytes;   // a slot and its 4-byte ordinal
+    uint64_t buckets;
+    size_t reserve;        // what the builder puts on the device: the buckets and the r + 1 {pos, base} pairs
+    size_t slot_bytes() const { return bucket_bytes - 4; }
+};
+inline PhiSlotGeometry phi_slot_geometry(uint64_t n, uint64_t r, uint32_t phi_shift, uint32_t pos_bytes, const LoadConsts &c) {
+    const PhiSlotBuckets b = phi_slot_buckets(n, r, phi_shift);
+    PhiSlotGeometry g{b.shift, false, 0, b.buckets, 0};
+    const bool wide = pos_bytes == 8;
+    g.packed = wide && (n >> c.phi_packed_pos_bits) == 0 && g.shift <= c.phi_packed_max_shift;
+    g.bucket_bytes = (g.packed ? c.phi_slot_packed_bytes : c.phi_slot_bytes[wide]) + 4;
+    g.reserve = g.buckets * g.bucket_bytes + (r + 1) * c.phi_pair_bytes[wide];
+    return g;
+}
+// phi by slots?  run_phi_opt (RBG_OPT_RUN_PHI): 2 yes, 1 no, 0 automatic: only while the slots are O(r) -- at most two buckets per sampled position (the
+// bucket shift stops at 8: an index with n / r far beyond 256 would get n / 256 of them) -- and the whole replica stays within the budget (hbm_bytes: what
+// the load has put on the device so far; the bucket records of the rank tables, decided before, have left room for the slots).
+inline bool phi_by_slots(int64_t run_phi_opt, const PhiSlotGeometry &g, uint64_t r, uint64_t hbm_bytes, uint64_t hbm_budget) {
+    return run_phi_opt == 2 || (run_phi_opt == 0 && hbm_budget && g.buckets <= 2 * r && hbm_bytes + g.reserve <= hbm_budget);
+}
+// THE PHI DIRECTORY over the list of sampled positions: the narrowest bucket (from 4 rows; at most 2^30, and 2^max_shift) with `per` sampled positions
+// or more on average -- between per and 2 per (RBG_PHI_DIR_PER, default 1: the scan's first four requests then cover the bucket and its predecessor
+// nineteen times in twenty).
+inline uint32_t phi_dir_shift(uint64_t r, uint64_t n, double per, uint32_t max_shift) {
+    uint32_t ds = 2;
+    while (ds < max_shift && ds < 30 && (static_cast<double>(r) * static_cast<double>(uint64_t(1) << ds)) / static_cast<double>(n) < per) ++ds;
+    return ds;
+}
+// THE REGISTER TABLES of the in-kernel read staging (rbg_dev.h stage_*): the least shift 0..5 under which the four major bytes hash to four different
+// three-bit places; code[place] = the byte's major index, byte[place] = the byte.  An unused place must never equal the byte that hashes to it: it holds
+// a byte whose own hash is another place.
+struct StageTables {
+    bool ok;
+    uint32_t shift;
+    uint8_t code[8], byte[8];
+};
+inline StageTables stage_tables(const uint8_t major_byte[4]) {
+    StageTables s{false, 0, {0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}};
+    for (uint32_t sh = 0; sh <= 5 && !s.ok; ++sh) {
+        uint8_t code[8] = {0, 0, 0, 0, 0, 0, 0, 0}, byte[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        bool used[8] = {false, false, false, false, false, false, false, false}, distinct = true;
+        for (uint32_t m = 0; m < 4; ++m) {
+            const uint32_t t = (major_byte[m] >> sh) & 7u;
+            if (used[t]) distinct = false;
+            used[t] = true;
+            code[t] = static_cast<uint8_t>(m);
+            byte[t] = major_byte[m];
+        }
+        if (!distinct) continue;
+        for (uint32_t t = 0; t < 8; ++t)
+            if (!used[t]) byte[t] = static_cast<uint8_t>(((t ^ 1u) & 7u) << sh);
+        s.ok = true;
+        s.shift = sh;
+        std::copy(code, code + 8, s.code);
+        std::copy(byte, byte + 8, s.byte);
+    }
+    return s;
+}
+
 // ---- the shape of an index: what the space rules of the run-indexed layout read of a HostIndex ----------------------------------------------------
 struct IndexShape {
     uint64_t n = 0, r = 0;
@@ -150,21 +284,16 @@ inline size_t runs_replica_bytes(const IndexShape &s, const LoadConsts &c, uint3
 // bucket records of one k-mer depth at `per` entries per bucket on average: their number (a sparse table's bucket shift stops at max_shift)
 inline double runs_record_count(const IndexShape &s, uint32_t depth_index, double per, uint32_t max_shift) {
     double nrec = 0;
-    for (const uint64_t nr : s.nruns[depth_index]) {
-        uint32_t sh = 0;
-        const double runs = static_cast<double>(std::max<uint64_t>(1, nr));
-        while (sh < max_shift && runs * static_cast<double>(uint64_t(2) << sh) <= per * static_cast<double>(s.n)) ++sh;
-        nrec += static_cast<double>((s.n >> sh) + 2);
-    }
+    for (const uint64_t nr : s.nruns[depth_index]) nrec += static_cast<double>(bucket_count(s.n, bucket_shift(static_cast<double>(nr), per, s.n, max_shift)));
     return nrec;
 }
-// phi slots of about n / r rows on the run-indexed layout: their bytes, or 0 where the automatic rule would not build them (more than 2 r buckets)
+// phi slots of about n / r rows on the run-indexed layout: their bytes, or 0 where the automatic rule would not build them (more than 2 r buckets).
+// The shift and the bucket count are the builder's (phi_slot_buckets), the bytes are not: THIS estimate differs from what the builder reserves
+// (phi_slot_geometry): 36 / 20 bytes per bucket whatever the form -- where the builder packs (8-byte
+// positions, n < 2^38, shift <= 6: 20 bytes) it is too high -- and without the r + 1 {pos, base} pairs.  The rules were moved, not changed.
 inline double runs_phi_slot_bytes(const IndexShape &s) {
     if (!s.has_tsa) return 0;
-    uint32_t ss = 0;
-    while (ss < 8 && static_cast<double>(uint64_t(2) << ss) <= static_cast<double>(s.n) / static_cast<double>(std::max<uint64_t>(1, s.r))) ++ss;
-    if (ss < s.phi_shift) ss = s.phi_shift;
-    const double nb = static_cast<double>((s.n >> ss) + 2);
+    const double nb = static_cast<double>(phi_slot_buckets(s.n, s.r, s.phi_shift).buckets);
     return nb <= 2.0 * static_cast<double>(s.r) ? nb * (s.pos_bytes == 8 ? 36.0 : 20.0) : 0.0;
 }
 // what bucket records share the budget with: the replica, and the phi slots first (RBG_OPT_RUN_PHI = 1 builds none): their room is not the records'

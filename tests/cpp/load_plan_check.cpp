@@ -1,8 +1,9 @@
-// load_plan_check.cpp -- the load rules of rbg_load_plan.hpp as functions of plain numbers, checked on the CPU (tests/test_load_plan_host.py builds this
+// load_plan_check.cpp -- the load rules of rbg_load_plan.hpp and its geometry of the run-indexed layout as functions of plain numbers, checked on the CPU (tests/test_load_plan_host.py builds this
 // with ASan + UBSan).  Every expectation is worked out by hand from the rule as its comment states it, or comes from a committed record: the arguments are
 // the rows of tools/layout_rules_table.py DEFAULT, six numbers each: n r hbm_free_at_load hbm_budget budget_raised symbols_per_gather.
 #include <cstdio>
 #include <cstdlib>
+#include <random>
 #include <vector>
 
 #include "../../rowbowt_amd/csrc/rbg_load_plan.hpp"
@@ -17,8 +18,9 @@ static int g_checks = 0, g_failed = 0;
     } while (0)
 
 // rbg_dev.h: kMaxNarrowShift 8, kMaxWideShift 12, kLdsSyms 8, a 16-byte slot and its 4-byte ordinal, 64 KB arena alignment, samples of 4 / 6 bytes, phi
-// entries of 8 / 12 bytes
-static const LoadConsts C{8, 12, 8, 20, 65536, {4, 6}, {8, 12}};
+// entries of 8 / 12 bytes; kLdsRunDepth 5, the uniform depth's packed constants of 27, 5 and 24 bits; packed phi slots up to 38-bit positions and shift 6; phi
+// slots of 16 / 32 bytes, 16 packed; {pos, base} pairs of 8 / 16 bytes
+static const LoadConsts C{8, 12, 8, 20, 65536, {4, 6}, {8, 12}, 5, 27, 5, 24, 38, 6, {16, 32}, 16, {8, 16}};
 static const size_t kAlign8 = 8 * 65536, kAlign16 = 16 * 65536;
 
 // n = 2^20, no samples, 4-byte positions; depth 1: tables of 99 and 199 runs (300 entries with their sentinels), depth 2: 49 (50), depth 3: 9 (10),
@@ -235,6 +237,183 @@ static void check_small_rules() {
     CHECK(j.table_budget == 900);
 }
 
+
+// ---- the geometry of the run-indexed layout ----------------------------------------------------------------------------------------------------------
+static void check_bucket_shift() {
+    const uint64_t n = uint64_t(1) << 20;
+    // the shift grows while runs * 2^(shift + 1) <= per * n.  One run, one entry per bucket: 2^(shift + 1) <= 2^20 up to shift 19 -- shift 20; no run counts as one
+    CHECK(bucket_shift(1, 1, n, 31) == 20 && bucket_shift(0, 1, n, 31) == 20 && bucket_shift(0.25, 1, n, 31) == 20);
+    // four runs: 4 x 2^18 = 2^20 is still <= n (shift 18); with a row less it is not (17); five runs: 5 x 2^18 > 2^20 (17)
+    CHECK(bucket_shift(4, 1, n, 31) == 18 && bucket_shift(4, 1, n - 1, 31) == 17 && bucket_shift(5, 1, n, 31) == 17);
+    CHECK(bucket_shift(4, 2, n, 31) == 19 && bucket_shift(n, 1, n, 31) == 0 && bucket_shift(static_cast<double>(n / 2), 1, n, 31) == 1 && bucket_shift(static_cast<double>(n / 2 + 1), 1, n, 31) == 0);   // (n / 2 runs: 2 x n / 2 <= n)
+    // the numbers of the record checks above: 99 runs at 6 per bucket: 15, 199: 14, 19 at 2.5: 17
+    CHECK(bucket_shift(99, 6, n, 31) == 15 && bucket_shift(199, 6, n, 31) == 14 && bucket_shift(19, 2.5, n, 31) == 17);
+    // it stops at max_shift: 31 at 4-byte positions, the fill shift (30, or a test's 5) at 8-byte positions
+    CHECK(bucket_shift(1, 1e12, n, 31) == 31 && bucket_shift(1, 1e12, n, 30) == 30 && bucket_shift(1, 6, n, 5) == 5 && bucket_shift(1, 6, n, 0) == 0);
+    CHECK(bucket_count(n, 15) == 34 && bucket_count(n, 31) == 2 && bucket_count(0, 0) == 2);
+    // runs_record_count: the sum of (n >> shift) + 2 over the tables -- shifts 15 and 14; a table without runs (shift 20 at one per bucket) has 1 + 2
+    IndexShape s = four_depths();
+    CHECK(runs_record_count(s, 0, 6.0, 31) == static_cast<double>(((n >> 15) + 2) + ((n >> 14) + 2)));
+    s.nruns[4] = {0, 1, 4};
+    CHECK(runs_record_count(s, 4, 1.0, 31) == 3 + 3 + 6);
+    CHECK(runs_record_count(s, 4, 1.0, 5) == 3 * ((n >> 5) + 2));
+}
+
+static void check_uniform() {
+    const uint64_t n = uint64_t(1) << 20;
+    // deepest_with_records: no deeper KEPT depth has records
+    const std::vector<double> rec_per{2.5, 0.0, 4.0, 6.0};
+    CHECK(deepest_with_records(rec_per, 0xF, 3, 4) && !deepest_with_records(rec_per, 0xF, 2, 4) && deepest_with_records(rec_per, 0x7, 2, 4) && !deepest_with_records(rec_per, 0xF, 0, 4));
+    CHECK(deepest_with_records({2.5, 0.0, 0.0, 0.0}, 0xF, 0, 4));
+    // four tables of depth index 5 with 16 entries together at one per bucket: the average table's shift is 18 (4 x 2^18 <= 2^20), 4 + 2 records per table,
+    // 24 in all: at most 1.1 x the tables' own records when those are 22 (24.2), not when 21 (23.1)
+    UniformCandidate u = uniform_candidate(true, 5, 4, 100, 16, 22, 1, n, 31, -1, C);
+    CHECK(u.eligible && u.shift == 18 && u.stride == 6);
+    CHECK(!uniform_candidate(true, 5, 4, 100, 16, 21, 1, n, 31, -1, C).eligible);
+    // eleven tables: 66 records = 1.1 x 60 exactly: at most a tenth more; 59: more
+    CHECK(uniform_candidate(true, 5, 11, 100, 44, 60, 1, n, 31, -1, C).eligible && !uniform_candidate(true, 5, 11, 100, 44, 59, 1, n, 31, -1, C).eligible);
+    // each condition off alone: a deeper depth has records; a depth staged in LDS (index 4 = depth 5); forbidden; a single table
+    CHECK(!uniform_candidate(false, 5, 4, 100, 16, 22, 1, n, 31, -1, C).eligible && !uniform_candidate(true, 4, 4, 100, 16, 22, 1, n, 31, -1, C).eligible);
+    CHECK(!uniform_candidate(true, 5, 4, 100, 16, 22, 1, n, 31, 0, C).eligible && !uniform_candidate(true, 5, 1, 100, 4, 22, 1, n, 31, -1, C).eligible);
+    CHECK(!uniform_candidate(true, 5, 4, 100, 16, 1000, 1, n, 31, 0, C).eligible && !uniform_candidate(true, 5, 1, 100, 4, 1, 1, n, 31, 1, C).eligible);
+    CHECK(uniform_candidate(true, 7, 2, 0, 8, 22, 1, n, 31, -1, C).eligible);
+    // forced: whatever the cost ...
+    u = uniform_candidate(true, 5, 4, 100, 16, 1, 1, n, 31, 1, C);
+    CHECK(u.eligible && u.shift == 18 && u.stride == 6 && !uniform_candidate(true, 5, 4, 100, 16, 1, 1, n, 31, -1, C).eligible);
+    CHECK(!uniform_candidate(true, 4, 4, 100, 16, 1, 1, n, 31, 1, C).eligible && !uniform_candidate(false, 5, 4, 100, 16, 1, 1, n, 31, 1, C).eligible);
+    // ... but not whatever the packing.  The stride (shift 0: n + 2 records per table) fits 27 bits at 2^27 - 1, not at 2^27
+    const uint64_t n27 = (uint64_t(1) << 27) - 3;
+    u = uniform_candidate(true, 5, 4, 100, 16, 1, 1, n27, 0, 1, C);
+    CHECK(u.eligible && u.shift == 0 && u.stride == (uint64_t(1) << 27) - 1 && uniform_stride_fits(u.stride, C));
+    u = uniform_candidate(true, 5, 4, 100, 16, 1, 1, n27 + 1, 0, 1, C);
+    CHECK(!u.eligible && u.stride == uint64_t(1) << 27 && !uniform_stride_fits(u.stride, C));
+    CHECK(uniform_candidate(true, 5, 4, 100, 16, uint64_t(1) << 40, 1, n27, 0, -1, C).eligible && !uniform_candidate(true, 5, 4, 100, 16, uint64_t(1) << 40, 1, n27 + 1, 0, -1, C).eligible);
+    // the shift in 5 bits: 31 fits, 32 (no position width has it: a max_shift only this check passes) does not
+    CHECK(uniform_candidate(true, 5, 4, 100, 4, 1, 1e30, n, 31, 1, C).eligible && uniform_candidate(true, 5, 4, 100, 4, 1, 1e30, n, 31, 1, C).shift == 31);
+    CHECK(!uniform_candidate(true, 5, 4, 100, 4, 1, 1e30, n, 32, 1, C).eligible);
+    // the tables up to and with this depth in 24 bits: 2^24 - 1 of them fit, 2^24 do not
+    CHECK(uniform_candidate(true, 5, 4, (size_t(1) << 24) - 5, 16, 22, 1, n, 31, -1, C).eligible && !uniform_candidate(true, 5, 4, (size_t(1) << 24) - 4, 16, 22, 1, n, 31, -1, C).eligible);
+    CHECK(!uniform_candidate(true, 5, 4, (size_t(1) << 24) - 4, 16, 22, 1, n, 31, 1, C).eligible);
+    // the verdict after counting.  Compared at all: more than one record in 256 overflows (4 x 256 = 1024: not of 1024, of 1023 yes), never when forced
+    CHECK(!uniform_needs_comparison(4, 1024, -1) && uniform_needs_comparison(4, 1023, -1) && !uniform_needs_comparison(0, 0, -1) && uniform_needs_comparison(1, 255, -1));
+    CHECK(!uniform_needs_comparison(4, 1023, 1) && !uniform_needs_comparison(1000000, 1, 1));
+    // uniform stays: at most a quarter more overflowing than the tables' own 8, and 512 / 256: 10 + 2 = 12
+    CHECK(uniform_stays(12, 8, 512) && !uniform_stays(13, 8, 512) && uniform_stays(0, 0, 0) && !uniform_stays(1, 0, 255) && uniform_stays(1, 0, 256) && uniform_stays(5, 4, 0) && !uniform_stays(6, 4, 0));
+}
+
+static void check_phi_geometry() {
+    const uint64_t r = 1024;
+    // the shift grows while 2^(shift + 1) <= n / r, up to 8.  n / r = 1: 0; 2: 1; 255: 7 (256 > 255); 256: 8; 1e6: 8
+    PhiSlotGeometry g = phi_slot_geometry(r, r, 0, 4, C);
+    CHECK(g.shift == 0 && !g.packed && g.bucket_bytes == 20 && g.slot_bytes() == 16 && g.buckets == 1026 && g.reserve == 1026 * 20 + 1025 * 8);
+    g = phi_slot_geometry(2 * r, r, 0, 4, C);
+    CHECK(g.shift == 1 && g.buckets == 1026);
+    g = phi_slot_geometry(255 * r, r, 0, 4, C);
+    CHECK(g.shift == 7 && g.buckets == 2040 + 2 && phi_by_slots(0, g, r, 0, uint64_t(1) << 40));
+    g = phi_slot_geometry(256 * r, r, 0, 4, C);
+    CHECK(g.shift == 8 && g.buckets == 1026 && phi_by_slots(0, g, r, 0, uint64_t(1) << 40));
+    g = phi_slot_geometry(1000000 * r, r, 0, 4, C);
+    CHECK(g.shift == 8 && g.buckets == 4000000 + 2 && !phi_by_slots(0, g, r, 0, uint64_t(1) << 40) && phi_by_slots(2, g, r, 0, 0));
+    // at most 2 r buckets: n = 2 r x 256 - 512 has 2 r - 2 + 2 of them, 256 rows more one too many
+    g = phi_slot_geometry(2 * r * 256 - 512, r, 0, 4, C);
+    CHECK(g.shift == 8 && g.buckets == 2 * r && phi_by_slots(0, g, r, 0, uint64_t(1) << 40));
+    g = phi_slot_geometry(2 * r * 256 - 256, r, 0, 4, C);
+    CHECK(g.buckets == 2 * r + 1 && !phi_by_slots(0, g, r, 0, uint64_t(1) << 40));
+    // never narrower than phi's own buckets
+    g = phi_slot_geometry(2 * r, r, 5, 4, C);
+    CHECK(g.shift == 5 && g.buckets == 64 + 2);
+    g = phi_slot_geometry(256 * r, r, 5, 4, C);
+    CHECK(g.shift == 8);
+    // packed: 8-byte positions, n < 2^38, shift <= 6.  n / r = 64: shift 6 -- 16 + 4 bytes per bucket, pairs of 16 bytes
+    g = phi_slot_geometry(64 * r, r, 0, 8, C);
+    CHECK(g.shift == 6 && g.packed && g.bucket_bytes == 20 && g.buckets == 1026 && g.reserve == 1026 * 20 + 1025 * 16);
+    g = phi_slot_geometry(64 * r, r, 0, 4, C);    // 4-byte positions
+    CHECK(g.shift == 6 && !g.packed && g.bucket_bytes == 20 && g.reserve == 1026 * 20 + 1025 * 8);
+    g = phi_slot_geometry(128 * r, r, 0, 8, C);   // shift 7
+    CHECK(g.shift == 7 && !g.packed && g.bucket_bytes == 36 && g.slot_bytes() == 32 && g.buckets == 1026 && g.reserve == 1026 * 36 + 1025 * 16);
+    g = phi_slot_geometry(32 * r, r, 7, 8, C);    // phi's own shift 7
+    CHECK(g.shift == 7 && !g.packed);
+    const uint64_t r33 = uint64_t(1) << 33;       // n = 2^38 - 1 and 2^38 over 2^33 runs: 32 rows per sample (shift 5), phi's own shift 6
+    g = phi_slot_geometry((uint64_t(1) << 38) - 1, r33, 6, 8, C);
+    CHECK(g.shift == 6 && g.packed && g.buckets == (uint64_t(1) << 32) - 1 + 2);
+    g = phi_slot_geometry(uint64_t(1) << 38, r33, 6, 8, C);
+    CHECK(g.shift == 6 && !g.packed && g.bucket_bytes == 36 && g.buckets == (uint64_t(1) << 32) + 2);
+    // phi_by_slots: 2 always, 1 never; automatic: a budget known, the buckets O(r), and what is on the device with the slots within the budget
+    g = phi_slot_geometry(64 * r, r, 0, 8, C);
+    CHECK(phi_by_slots(2, g, r, uint64_t(1) << 40, 1) && !phi_by_slots(1, g, r, 0, uint64_t(1) << 40) && !phi_by_slots(0, g, r, 0, 0));
+    CHECK(phi_by_slots(0, g, r, 5000, 5000 + g.reserve) && !phi_by_slots(0, g, r, 5001, 5000 + g.reserve));
+    // the planner's estimate for this shape, where the builder packs: 36 bytes per bucket, not the builder's 20, and no pairs
+    IndexShape w;
+    w.n = 64 * r; w.r = r; w.has_tsa = true; w.pos_bytes = 8; w.phi_shift = 0;
+    CHECK(runs_phi_slot_bytes(w) == 1026 * 36.0 && g.buckets * g.bucket_bytes == 1026 * 20);
+    w.pos_bytes = 4;
+    CHECK(runs_phi_slot_bytes(w) == 1026 * 20.0);
+    w.n = 2 * r * 256 - 256;   // one bucket more than 2 r: none
+    CHECK(runs_phi_slot_bytes(w) == 0);
+    w.n = 2 * r * 256 - 512;
+    CHECK(runs_phi_slot_bytes(w) == 2048 * 20.0);
+
+    // the phi directory: from shift 2, while r 2^shift / n < per; at most 30 and max_shift
+    const uint64_t n = uint64_t(1) << 20;
+    CHECK(phi_dir_shift(n, n, 1, 31) == 2 && phi_dir_shift(4 * n, n, 1, 31) == 2 && phi_dir_shift(n / 4, n, 1, 31) == 2 && phi_dir_shift(n / 4 - 1, n, 1, 31) == 3);
+    CHECK(phi_dir_shift(1024, n, 1, 31) == 10 && phi_dir_shift(1023, n, 1, 31) == 11 && phi_dir_shift(1024, n, 2, 31) == 11 && phi_dir_shift(1024, n, 0.5, 31) == 9);
+    CHECK(phi_dir_shift(1, uint64_t(1) << 40, 1, 31) == 30 && phi_dir_shift(1, uint64_t(1) << 40, 1, 12) == 12 && phi_dir_shift(1, uint64_t(1) << 40, 1, 5) == 5);
+    CHECK(phi_dir_shift(1, uint64_t(1) << 40, 1, 1) == 2 && phi_dir_shift(1, uint64_t(1) << 40, 1, 2) == 2 && phi_dir_shift(1, uint64_t(1) << 29, 1, 31) == 29);
+}
+
+// the least shift 0..5 under which the four bytes' three-bit places differ, by brute force; -1: none
+static int separating_shift(const uint8_t b[4]) {
+    for (int sh = 0; sh <= 5; ++sh) {
+        bool distinct = true;
+        for (int i = 0; i < 4; ++i)
+            for (int j = i + 1; j < 4; ++j) distinct = distinct && ((b[i] >> sh) & 7) != ((b[j] >> sh) & 7);
+        if (distinct) return sh;
+    }
+    return -1;
+}
+static bool stage_tables_right(const uint8_t b[4]) {
+    const StageTables s = stage_tables(b);
+    const int want = separating_shift(b);
+    if (!s.ok) return want < 0;
+    if (want < 0 || s.shift != static_cast<uint32_t>(want)) return false;
+    for (int v = 0; v < 256; ++v) {   // byte[place of v] == v exactly for the four major bytes, and code[...] is then the byte's major index
+        int major = -1;
+        for (int m = 0; m < 4; ++m)
+            if (b[m] == v) major = m;
+        const uint32_t place = (static_cast<uint32_t>(v) >> s.shift) & 7u;
+        if ((s.byte[place] == v) != (major >= 0)) return false;
+        if (major >= 0 && s.code[place] != major) return false;
+    }
+    return true;
+}
+static void check_stage_tables() {
+    const uint8_t ACGT[4] = {'A', 'C', 'G', 'T'}, acgt[4] = {'a', 'c', 'g', 't'}, TGCA[4] = {'T', 'G', 'C', 'A'};
+    CHECK(stage_tables_right(ACGT) && stage_tables(ACGT).ok && stage_tables(ACGT).shift == 0);   // A, C, G, T & 7: 1, 3, 7, 4
+    CHECK(stage_tables(ACGT).code[1] == 0 && stage_tables(ACGT).code[3] == 1 && stage_tables(ACGT).code[7] == 2 && stage_tables(ACGT).code[4] == 3);
+    CHECK(stage_tables_right(acgt) && stage_tables(acgt).ok && stage_tables(acgt).shift == 0 && stage_tables_right(TGCA) && stage_tables(TGCA).code[4] == 0);
+    // 0x00, 0x08, 0x10, 0x18: the same place at shift 0, 0 4 0 4 at shift 1, 0 2 4 6 at shift 2
+    const uint8_t later[4] = {0x00, 0x08, 0x10, 0x18};
+    CHECK(stage_tables_right(later) && stage_tables(later).ok && stage_tables(later).shift == 2);
+    // 0x00, 0x01, 0x80, 0x81: 0 1 0 1 at shift 0, four zeros at shifts 1..4, 0 0 4 4 at shift 5
+    const uint8_t none[4] = {0x00, 0x01, 0x80, 0x81};
+    CHECK(stage_tables_right(none) && !stage_tables(none).ok && separating_shift(none) < 0);
+    std::mt19937 rng(20240229);
+    int ok = 0, not_ok = 0, wrong = 0;
+    for (int i = 0; i < 20000; ++i) {
+        uint8_t b[4];
+        for (int k = 0; k < 4;) {   // four different bytes
+            b[k] = static_cast<uint8_t>(rng() & 0xFF);
+            bool fresh = true;
+            for (int j = 0; j < k; ++j) fresh = fresh && b[j] != b[k];
+            if (fresh) ++k;
+        }
+        if (!stage_tables_right(b)) ++wrong;
+        ++(stage_tables(b).ok ? ok : not_ok);
+    }
+    CHECK(wrong == 0);
+    CHECK(ok > 1000 && not_ok > 1000);   // (both outcomes are common among random subsets)
+}
+
 int main(int argc, char **argv) {
     check_rows(argc, argv);
     check_budget_and_layout();
@@ -242,6 +421,10 @@ int main(int argc, char **argv) {
     check_trimming();
     check_records();
     check_small_rules();
+    check_bucket_shift();
+    check_uniform();
+    check_phi_geometry();
+    check_stage_tables();
     if (g_failed) return 1;
     std::printf("load_plan ok rows %d checks %d\n", (argc - 1) / 6, g_checks);
     return 0;

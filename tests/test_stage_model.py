@@ -128,5 +128,5 @@ def test_staged_codes_equal_plain_packing_for_every_alignment():
 def test_the_constants_in_the_source_are_the_ones_modelled_here():
     src = open(os.path.join(ROOT, "rowbowt_amd", "csrc", "rbg_runs_device.hpp")).read()
     assert "0x40100401u" in src and "0x00204081u" in src and "0x07070707u" in src and re.search(r"kStageCap = 256u", src)
-    up = open(os.path.join(ROOT, "rowbowt_amd", "csrc", "capi", "upload_runs.ipp")).read()
+    up = open(os.path.join(ROOT, "rowbowt_amd", "csrc", "rbg_load_plan.hpp")).read()   # stage_tables(): what capi/upload_runs.ipp puts into DevIndex::stage_*
     assert "((t ^ 1u) & 7u) << sh" in up and "sh <= 5" in up

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """DESIGN.md 2c's table "what a default rbg_load builds", generated from what the loads themselves reported (rbg_info / rbg_layout_info as the
 committed JSON lines of bench.py and tools/pangenome_stream.py carry them): input (n, r, free HBM) -> budget -> depths kept, records per depth, phi form,
-replica bytes, and the rate measured from that replica.  A rule edit (rbg_load_plan.hpp, where the rules live as functions of plain numbers; capi/load.ipp options_for / upload() and capi/upload_runs.ipp apply them) shows in the driver-run sizes
+replica bytes, and the rate measured from that replica.  A rule edit (rbg_load_plan.hpp, where the rules live as functions of plain numbers -- budget, depths, records, and the geometry of the run-indexed layout:
+bucket shifts, the uniform depth, the phi form; capi/load.ipp options_for / upload() and capi/upload_runs.ipp upload_tables_runs2 apply them) shows in the driver-run sizes
 -- the bench line's config.index.layout_info and tests/test_gpu_scale.py::test_pangenome_shape_r_above_1e8_default_load -- without a builder-side full-size run;
 the two largest rows need one (60 s loads of 100-200 GB).
 
