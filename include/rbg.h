@@ -651,6 +651,49 @@ int rbg_loc_markers_plan_dev(rbg_index *, const uint64_t *d_locs, const uint64_t
 int rbg_loc_markers_fill_dev(rbg_index *, const uint64_t *d_locs, const uint64_t *d_loc_off, const uint64_t *d_off, uint64_t N,
                              const uint64_t *d_mk_off, uint64_t *d_mk, void *stream);
 
+/* ---- document hits: which documents a read's locations fall in, answered where the locations are ------------------------------------
+ * On an index with one document per haplotype (rbg_set_docs, doclist.hpp:57-73) the question a location list answers is "which haplotypes carry this
+ * read, and how many reads does each haplotype carry".  These calls answer it from K3's output on the device: a set of 50 documents is 8 bytes per read
+ * where the locations are 37 x 8 on the bench index.  The rule is rbg_resolve_offset's (DocList::doc_and_offset_at doclist.hpp:46-50 over doc_bounds_rank :77-79): for a
+ * position l, q = min(l + 1, size) with l + 1 wrapping at 2^64 and size = the LAST start given + 1 (doclist.hpp:66); j = # sorted starts < q; j == 0: no
+ * document, else document j - 1 -- entry j - 1 of rbg_doc_table -- at offset l - sorted_starts[j - 1].
+ * The device table holds at most RBG_DOCS_MAX documents (rbg_docs_prepare: RBG_EARG beyond). */
+#define RBG_DOCS_MAX 65536u
+#define RBG_DOC_NONE 0xFFFFFFFFu
+/* doclist.hpp:46-50, :77-79.  Uploads the sorted starts and their directory (rowbowt_amd/csrc/rbg_docdir.hpp) to the handle's device; idempotent.
+ * RBG_ENOTLOADED without documents.  A later rbg_set_docs drops the copy (prepare again; the *_dev calls below answer RBG_ENOTLOADED until then, on the
+ * primary and on every replica of it).  A replica prepares its own copy from its primary's table.  Must not overlap queries on the handle, like
+ * rbg_set_docs. */
+int rbg_docs_prepare(rbg_index *);
+/* doclist.hpp:46-50, :77-79.  W = ceil(ndocs / 64): the u64 words of one read's document set (bit d % 64 of word d / 64 = document d); 0 without documents */
+size_t rbg_doc_hits_words(const rbg_index *);
+/* doclist.hpp:46-50, :77-79 for M locations on the device, one per lane: d_doc[j] = the document of d_locs[j] or RBG_DOC_NONE, d_offset[j] (nullable) = its
+ * offset in that document, or the location itself when it has none.  _dev32: locations as rbg_locate_fill_dev32 writes them; 0xFFFFFFFF stands for the
+ * toehold that wrapped below zero, 2^64 - 1 (no document; its offset reads 2^64 - 1).  Asynchronous on `stream`, nothing allocated or synchronised;
+ * RBG_ENOTLOADED without a prior rbg_docs_prepare. */
+int rbg_resolve_offsets_dev(rbg_index *, const uint64_t *d_locs, uint64_t M, uint32_t *d_doc, uint64_t *d_offset /* nullable */, void *stream);
+int rbg_resolve_offsets_dev32(rbg_index *, const uint32_t *d_locs32, uint64_t M, uint32_t *d_doc, uint64_t *d_offset /* nullable */, void *stream);
+/* doclist.hpp:46-50, :77-79 reduced per read: read i has the locations d_locs[d_loc_off[i], d_loc_off[i + 1]) (K3's output).  d_sets[i * W ...]: the SET of their
+ * documents; d_ndocs[i]: the number of distinct documents; d_nodoc[i]: the number of its locations that have no document; d_doc_reads[d] += 1 for every
+ * document d of the set -- reads per document, a read counting once per document; it ACCUMULATES over calls (zero it first).  Every output is nullable.
+ * A group of 4, 16 or 64 lanes walks one read; the width is chosen on the device from d_loc_off[N] / N, or forced by the environment variable
+ * RBG_DOCS_GROUP (tests, A/Bs): the outputs do not depend on it.  Asynchronous on `stream`, nothing allocated or synchronised; RBG_ENOTLOADED without a
+ * prior rbg_docs_prepare. */
+int rbg_doc_hits_dev(rbg_index *, const uint64_t *d_locs, const uint64_t *d_loc_off, uint64_t N, uint64_t *d_sets /* [N * W] nullable */,
+                     uint32_t *d_ndocs /* [N] nullable */, uint32_t *d_nodoc /* [N] nullable */, uint64_t *d_doc_reads /* [ndocs] nullable, ACCUMULATES */,
+                     void *stream);
+/* doclist.hpp:46-50, :77-79 over the output of rbg_locate_fill_dev32; 0xFFFFFFFF = the wrapped toehold = no document (counted in d_nodoc) */
+int rbg_doc_hits_dev32(rbg_index *, const uint32_t *d_locs32, const uint64_t *d_loc_off, uint64_t N, uint64_t *d_sets /* [N * W] nullable */,
+                       uint32_t *d_ndocs /* [N] nullable */, uint32_t *d_nodoc /* [N] nullable */, uint64_t *d_doc_reads /* [ndocs] nullable, ACCUMULATES */,
+                       void *stream);
+/* doclist.hpp:46-50, :77-79 for a batch of reads in host memory: rbg_find_range_w_toehold (lo, hi as that call writes them), rbg_locs_at with max_hits, and
+ * the reduction above over its locations, which never leave the device -- per read 16 + 8 W + 4 (+ 4) bytes come back instead of 8 per location.  The batch
+ * is searched in chunks of reads and located in pieces of a bounded number of locations, so the scratch on the device stays bounded; rbg_counters sees every
+ * read and every location once.  Prepares the table itself if needed.  doc_reads accumulates into the
+ * caller's array.  RBG_ENOTLOADED without the toehold SA or documents. */
+int rbg_doc_hits(rbg_index *, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t max_hits, uint64_t *lo, uint64_t *hi, uint64_t *sets /* [N * W] */,
+                 uint32_t *ndocs /* [N] */, uint32_t *nodoc /* [N] nullable */, uint64_t *doc_reads /* [ndocs] nullable, accumulates */);
+
 /* ---- global counters (the values the 8-GPU run reduces over RCCL) -------------------------- */
 /* {reads processed, reads matched (non-empty range), sum of occ, sum of located positions}
  * accumulated on the device by every query since load / the last reset. */

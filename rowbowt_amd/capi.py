@@ -88,6 +88,8 @@ TALLY_INFO = ("entries", "capacity", "grows", "records", "elements", "dropped")
 # rbg_markers_tally_reads' / rbg_tally_add_reads_dev's flag word; rbg_tally_read_info's four counters
 TALLY_PER_READ, TALLY_DROP_SITE_CONFLICTS = 1, 2
 TALLY_READ_INFO = ("reads", "elements_seen", "lost", "site_dropped")
+DOCS_MAX = 1 << 16        # RBG_DOCS_MAX: documents a device table holds (rbg_docs_prepare)
+DOC_NONE = 0xFFFFFFFF     # RBG_DOC_NONE: the document of a position that has none
 
 
 def report_params(wsize=19, max_range=1000, min_range=0, ftab_k=0, read_len=101, min_seed_len=0, lmem=False, heuristic=False, best_strand=False,
@@ -220,6 +222,13 @@ _PROTOS = [
     ("rbg_tally_add_reads_tmp_bytes", C.c_size_t, [U64, U64]),
     ("rbg_tally_add_reads_dev", C.c_int, [VP, VP, U64, VP, U64, VP, U64, C.c_uint32, VP, C.c_size_t, VP]),
     ("rbg_tally_read_info", C.c_int, [VP, VP]),
+    ("rbg_docs_prepare", C.c_int, [VP]),
+    ("rbg_doc_hits_words", C.c_size_t, [VP]),
+    ("rbg_resolve_offsets_dev", C.c_int, [VP, VP, U64, VP, VP, VP]),
+    ("rbg_resolve_offsets_dev32", C.c_int, [VP, VP, U64, VP, VP, VP]),
+    ("rbg_doc_hits_dev", C.c_int, [VP, VP, VP, U64, VP, VP, VP, VP, VP]),
+    ("rbg_doc_hits_dev32", C.c_int, [VP, VP, VP, U64, VP, VP, VP, VP, VP]),
+    ("rbg_doc_hits", C.c_int, [VP, VP, VP, U64, U64, VP, VP, VP, VP, VP, VP]),
     ("rbg_set_default_option", C.c_int, [C.c_int, C.c_int64]),
     ("rbg_get_default_option", C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
 ]
@@ -665,6 +674,56 @@ class RowBowt:
         name, off = C.c_char_p(), U64()
         _check(self.L.rbg_resolve_offset(self.h, i, C.byref(name), C.byref(off)), "rbg_resolve_offset")
         return name.value.decode(), off.value
+
+    def docs_prepare(self):
+        """rbg_docs_prepare: the document table and its directory on this handle's device (idempotent; again after every set_docs)"""
+        _check(self.L.rbg_docs_prepare(self.h), "rbg_docs_prepare")
+
+    def doc_hits_words(self):
+        """W = ceil(ndocs / 64): the u64 words of one read's document set"""
+        return int(self.L.rbg_doc_hits_words(self.h))
+
+    def resolve_offsets(self, locs):
+        """resolve_offset for an array of text positions, on the device (rbg_resolve_offsets_dev): -> (doc[M] uint32, DOC_NONE where a position has
+        no document, offset[M] uint64).  doc indexes rbg_doc_table's names.  The arrays cross to the device and back through torch"""
+        import torch
+        locs = _u64(locs)
+        M = len(locs)
+        self.docs_prepare()
+        info = self.info()
+        with torch.cuda.device(info.device):
+            d_locs = torch.from_numpy(locs.view(np.int64)).cuda()
+            d_doc = torch.empty(max(M, 1), dtype=torch.int32, device="cuda")
+            d_off = torch.empty(max(M, 1), dtype=torch.int64, device="cuda")
+            st = torch.cuda.current_stream().cuda_stream
+            _check(self.L.rbg_resolve_offsets_dev(self.h, d_locs.data_ptr() if M else None, M, d_doc.data_ptr(), d_off.data_ptr(), st), "rbg_resolve_offsets_dev")
+            torch.cuda.synchronize()
+            return d_doc[:M].cpu().numpy().view(np.uint32), d_off[:M].cpu().numpy().view(np.uint64)
+
+    def doc_hits(self, seqs, off, max_hits=MAXU):
+        """rbg_doc_hits: per read its range and the SET of documents its locations (locs_at with max_hits) fall in, the locations staying on the
+        device -> (lo, hi, sets[N, W] uint64 -- bit d % 64 of word d / 64 = document d --, ndocs[N], nodoc[N] uint32, doc_reads[ndocs] uint64 = the
+        reads of this batch that hit each document)"""
+        seqs, off = np.ascontiguousarray(seqs, dtype=np.uint8), _u64(off)
+        N = len(off) - 1
+        self.docs_prepare()
+        W = self.doc_hits_words()
+        nd = self.doc_table(names=False)[0]
+        lo, hi = np.zeros(N, np.uint64), np.zeros(N, np.uint64)
+        sets = np.zeros((N, W), np.uint64)
+        ndocs, nodoc = np.zeros(N, np.uint32), np.zeros(N, np.uint32)
+        doc_reads = np.zeros(nd, np.uint64)
+        _check(self.L.rbg_doc_hits(self.h, _p(seqs), _p(off), N, max_hits, _p(lo), _p(hi), _p(sets), _p(ndocs), _p(nodoc), _p(doc_reads)), "rbg_doc_hits")
+        return lo, hi, sets, ndocs, nodoc, doc_reads
+
+    def doc_table(self, names=True):
+        """rbg_doc_table: (ndocs, sorted_starts uint64[ndocs], names (None when not asked for), size)"""
+        nd, size, ps, pn = U64(), U64(), VP(), VP()
+        _check(self.L.rbg_doc_table(self.h, C.byref(nd), C.byref(ps), C.byref(pn), C.byref(size)), "rbg_doc_table")
+        n = int(nd.value)
+        starts = np.ctypeslib.as_array(C.cast(ps, C.POINTER(U64)), shape=(n,)).copy()
+        got = [C.cast(pn, C.POINTER(C.c_char_p))[j].decode() for j in range(n)] if names else None
+        return n, starts, got, int(size.value)
 
     def align_text(self, lo, hi, k, names, max_hits=MAXU, markers=False):
         """rbg_align_text: the `rb_align -s` text of a batch (bytes), made on the device; names = list of bytes"""

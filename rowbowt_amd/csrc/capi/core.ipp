@@ -82,6 +82,11 @@ struct rbg_index {
     // the marker table keyed by text position (rbg_set_text_markers; DevIndex::tmk_*): per handle -- a replica has the table its primary had when it was made
     bool has_tmk = false;
     std::vector<void *> tmk_allocs;   // its device arrays (each also in `allocs`): given back when another table replaces it
+    // rbg_docs_prepare: sorted starts and directory (rbg_docdir.hpp) on THIS handle's device, two allocations of their own (each also in `allocs`).  Per handle and
+    // not in DevIndex: a replica prepares its own copy from the root's host table.  gen = the root's docs_gen the copy was made from: a later rbg_set_docs
+    // (which counts docs_gen up on the root) makes every handle's copy stale, and the *_dev calls answer RBG_ENOTLOADED until the next prepare
+    struct DocDev { const uint64_t *sorted = nullptr; const uint32_t *dir = nullptr; uint64_t size = 0, gen = 0; uint32_t ndocs = 0, shift = 0, ndir = 0; } doc_dev;
+    uint64_t docs_gen = 0;
     std::mutex mu;               // guards marker/doc attachment only; queries are lock-free
 };
 
@@ -578,6 +583,15 @@ void free_tracked(rbg_index *ix, void *p) {
     for (size_t i = 0; i < ix->allocs.size(); ++i)
         if (ix->allocs[i].p == p) { ix->hbm_bytes -= ix->allocs[i].bytes; ix->allocs.erase(ix->allocs.begin() + static_cast<std::ptrdiff_t>(i)); break; }
     (void)hipFree(p);
+}
+
+// give back the device copy of the document table (rbg_docs_prepare)
+void drop_doc_dev(rbg_index *ix) {
+    if (!ix->doc_dev.sorted && !ix->doc_dev.dir) return;
+    DeviceScope scope(ix->device);
+    free_tracked(ix, const_cast<uint64_t *>(ix->doc_dev.sorted));
+    free_tracked(ix, const_cast<uint32_t *>(ix->doc_dev.dir));
+    ix->doc_dev = rbg_index::DocDev();
 }
 
 void release_kmer_level(rbg_index *ix, uint32_t depth);

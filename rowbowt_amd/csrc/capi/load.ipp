@@ -1042,6 +1042,8 @@ int rbg_set_docs(rbg_index *ix, const char *names_joined, const uint64_t *starts
         std::lock_guard<std::mutex> g2(ix->text_mu);
         ix->text_docs = rbg_index::TextDocs();
     }
+    drop_doc_dev(ix);   // rbg_docs_prepare's copy is of the table before: prepare again (a replica's copy goes stale by the count)
+    ++ix->docs_gen;
     return upload_order_docs(ix);   // (K3's chain order by locus: attach the documents BEFORE replicating, like the markers)
     });
 }

@@ -28,6 +28,7 @@
 #include "../../include/rbg.h"
 #include "rbg_dev.h"
 #include "rbg_jump.h"
+#include "rbg_docdir.hpp"
 #include "rbg_host.hpp"
 
 
@@ -44,4 +45,5 @@
 #include "capi/tally.ipp"         // the marker tally: per-marker counts of the report's lines, accumulated on the device (rbg_markers_tally: report.ipp)
 #include "capi/report.ipp"        // rb_markers' report on the device, pass by pass: strands, the seed pass, canonical records, selection; records, text or tally
 #include "capi/loc_markers.ipp"   // the text-position marker table, markers at located positions (rb_locs' path)
+#include "capi/docs.ipp"          // the document table on the device, documents of located positions (rbg_doc_hits*, rbg_resolve_offsets_dev*)
 #include "capi/replicas.ipp"      // replicas in one process, counters, RCCL

@@ -593,6 +593,16 @@ int launch_loc_markers_plan(const DevIndex &ix, const LaunchCfg &cfg, const uint
                             uint64_t *mk_off, void *tmp, size_t tmp_bytes, int group, void *stream);
 int launch_loc_markers_fill(const DevIndex &ix, const LaunchCfg &cfg, const uint64_t *locs, const uint64_t *loc_off, const uint64_t *off, uint64_t N,
                             const uint64_t *mk_off, uint64_t *mk, int group, void *stream);
+// documents of located text positions (k_docs.hip; rbg_docdir.hpp holds the rule and the directory): the table is sorted[ndocs], dir[ndir], size, shift on the
+// device; locs are u64, or u32 when locs32 (0xFFFFFFFF = the wrapped toehold).  launch_resolve_offsets: doc[M] and offset[M] (nullable).  launch_doc_hits: per
+// read its set of documents (sets[N * ceil(ndocs / 64)]), their number, its locations without a document, and +1 per document of the set in doc_reads[ndocs]
+// (every output nullable).  group: lanes per read, 4 / 16 / 64, or 0 = chosen on the device from loc_off[N] / N (docs_group(): what RBG_DOCS_GROUP forces)
+int docs_group();
+int launch_resolve_offsets(const uint64_t *sorted, const uint32_t *dir, uint64_t size, uint32_t ndocs, uint32_t shift, uint32_t ndir, const void *locs,
+                           bool locs32, uint64_t M, uint32_t *doc, uint64_t *offset, void *stream);
+int launch_doc_hits(const uint64_t *sorted, const uint32_t *dir, uint64_t size, uint32_t ndocs, uint32_t shift, uint32_t ndir, const void *locs, bool locs32,
+                    const uint64_t *loc_off, uint64_t N, uint64_t *sets, uint32_t *ndocs_out, uint32_t *nodoc_out, uint64_t *doc_reads, int group,
+                    void *stream);
 // rb_markers' report on the device (k_report.hip; rbg_markers_report[_text]): both strands of raw reads, the canonical form of the seeding kernels' records
 // (min_range gate, marker_cmp sort, unique, the two per-seed filters; group: lanes per short segment, 4 / 16 / 64, or 0 = chosen on the device --
 // report_canon_group(): what RBG_REPORT_GROUP forces), the per-read choice of printed records, and the lines by elements as in k_text.hip

@@ -18,6 +18,7 @@
 // (the reference refuses it itself).
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -28,6 +29,7 @@
 #include <vector>
 
 #include "../../include/rbg.h"
+#include "../csrc/rbg_docdir.hpp"   // the document lookup rule, stated once for library, kernels and this header
 
 // pfbwt-f marker_array.hpp helpers used at rb_align.cpp:142 (bit layout: SURVEY.md 8b-format)
 using MarkerT = uint64_t;
@@ -203,6 +205,60 @@ class RowBowt {
         uint64_t off = 0;
         detail::check(rbg_resolve_offset(ix_.get(), i, &name, &off), "rbg_resolve_offset");
         return std::make_pair(std::string(name), off);
+    }
+
+    // resolve_offset for many positions that are in HOST memory: one fetch of the table (rbg_doc_table) and the rule of doclist.hpp:46-50, :77-79 (rbg_docdir.hpp) per position,
+    // instead of a call through the ABI each.  doc[i] = the document's index into names() of rbg_doc_table, RBG_DOC_NONE where position i has none (the single
+    // call exits there; the offset is then the position itself).  Positions that are on the device go through rbg_resolve_offsets_dev and never come here.
+    struct DocOffsets { std::vector<uint32_t> doc; std::vector<uint64_t> offset; std::vector<std::string> names; };
+    DocOffsets resolve_offsets(const std::vector<uint64_t> &positions) const {
+        uint64_t nd = 0, size = 0;
+        const uint64_t *sorted = nullptr;
+        const char *const *names = nullptr;
+        detail::check(rbg_doc_table(ix_.get(), &nd, &sorted, &names, &size), "rbg_doc_table");
+        DocOffsets r;
+        r.names.assign(names, names + nd);
+        r.doc.resize(positions.size());
+        r.offset.resize(positions.size());
+        for (size_t i = 0; i < positions.size(); ++i) {
+            const uint64_t l = positions[i], j = rbg::doc_rank_search(sorted, nd, size, l);
+            r.doc[i] = j ? static_cast<uint32_t>(j - 1) : RBG_DOC_NONE;
+            r.offset[i] = j ? l - sorted[j - 1] : l;
+        }
+        return r;
+    }
+    // Which documents each read's locations fall in (rbg_doc_hits): find_range_w_toehold + locs_at(max_hits) + resolve_offset reduced per read on the device,
+    // the locations never crossing to the host.  sets[i * words + d / 64] bit d % 64 = read i has a location in document d; doc_reads[d] = reads of this batch
+    // with a location in document d (a read counts once per document).
+    struct DocHits {
+        std::vector<range_t> ranges;
+        uint64_t words = 0;                 // u64 words per read in `sets`: ceil(documents / 64)
+        std::vector<uint64_t> sets;         // [reads * words]
+        std::vector<uint32_t> ndocs, nodoc; // distinct documents per read; its locations that have no document
+        std::vector<uint64_t> doc_reads;    // [documents]
+        bool hit(uint64_t read, uint64_t d) const { return (sets[read * words + d / 64] >> (d % 64)) & 1u; }
+    };
+    DocHits doc_hits(const std::vector<std::string> &queries, uint64_t max_hits = static_cast<uint64_t>(-1)) const {
+        detail::Batch b;
+        for (const auto &q : queries) b.add(q);
+        const uint64_t N = b.size();
+        detail::check(rbg_docs_prepare(ix_.get()), "rbg_docs_prepare");
+        uint64_t nd = 0, size = 0;
+        const uint64_t *sorted = nullptr;
+        const char *const *names = nullptr;
+        detail::check(rbg_doc_table(ix_.get(), &nd, &sorted, &names, &size), "rbg_doc_table");
+        DocHits r;
+        r.words = rbg_doc_hits_words(ix_.get());
+        std::vector<uint64_t> lo(N), hi(N);
+        r.sets.assign(N * r.words, 0);
+        r.ndocs.assign(N, 0);
+        r.nodoc.assign(N, 0);
+        r.doc_reads.assign(nd, 0);
+        detail::check(rbg_doc_hits(ix_.get(), b.data(), b.off.data(), N, max_hits, lo.data(), hi.data(), r.sets.data(), r.ndocs.data(), r.nodoc.data(),
+                                   r.doc_reads.data()), "rbg_doc_hits");
+        r.ranges.resize(N);
+        for (uint64_t i = 0; i < N; ++i) r.ranges[i] = {lo[i], hi[i]};
+        return r;
     }
 
     // rowbowt.hpp:272-290 ("WARNING: does not clear markers!")
