@@ -693,6 +693,28 @@ int rbg_doc_hits_dev32(rbg_index *, const uint32_t *d_locs32, const uint64_t *d_
  * caller's array.  RBG_ENOTLOADED without the toehold SA or documents. */
 int rbg_doc_hits(rbg_index *, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t max_hits, uint64_t *lo, uint64_t *hi, uint64_t *sets /* [N * W] */,
                  uint32_t *ndocs /* [N] */, uint32_t *nodoc /* [N] nullable */, uint64_t *doc_reads /* [ndocs] nullable, accumulates */);
+/* toehold_sa.hpp:37-49 walked, doclist.hpp:46-50 / :77-79 applied to every position, nothing stored per location: the outputs of rbg_locate_plan_dev +
+ * rbg_locate_fill_dev + rbg_doc_hits_dev for the same arguments, bit for bit, from ONE kernel that walks each read's phi chain (one lane per read, as the fill)
+ * and keeps the chain's document set in LDS.  d_lo, d_hi, d_k: rbg_find_range_w_toehold_dev's outputs; read i has min(hi - lo + 1, max_hits) locations.
+ * d_order (nullable): the workspace rbg_locate_order_dev filled for the same d_k and N.  d_k must stay valid and UNCHANGED between rbg_locate_order_dev and this
+ * call, as for the fill (the ordered walk reads d_k[i] itself for a toehold that wrapped below zero), and rbg_set_docs must not fall between the two (the
+ * order's keys are made from the table attached when it ran).  d_sets, d_ndocs, d_nodoc, d_doc_reads: as rbg_doc_hits_dev.  d_doc_locs[d] += the number of
+ * walked positions whose document is d (ACCUMULATES): over one call the sum of its increments plus the sum of d_nodoc is what rbg_counters' fourth value grows
+ * by, which is what the fill would have added.  Every output is nullable; with every output NULL the walk still runs (the counters see it).  Asynchronous on
+ * `stream`, nothing allocated or synchronised.  RBG_ENOTLOADED without the toehold SA or without a current rbg_docs_prepare (as rbg_doc_hits_dev; replicas
+ * included); RBG_EARG above RBG_LOCATE_DOCS_MAX documents (the table must fit LDS: use the three calls above) and on a null d_lo / d_hi / d_k with N > 0. */
+#define RBG_LOCATE_DOCS_MAX 1024u
+int rbg_locate_doc_hits_dev(rbg_index *, const uint64_t *d_lo, const uint64_t *d_hi, const uint64_t *d_k, uint64_t N, uint64_t max_hits,
+                            const void *d_order /* nullable */, uint64_t *d_sets /* [N*W] nullable */, uint32_t *d_ndocs /* [N] nullable */,
+                            uint32_t *d_nodoc /* [N] nullable */, uint64_t *d_doc_reads /* [ndocs] nullable, ACCUMULATES */,
+                            uint64_t *d_doc_locs /* [ndocs] nullable, ACCUMULATES */, void *stream);
+/* rbg_doc_hits with one more output: doc_locs[d] += the locations of this batch that fall in document d (nullable, accumulates).  Both calls take the
+ * same path: with at most RBG_LOCATE_DOCS_MAX documents each chunk of reads is searched, ordered and walked by rbg_locate_doc_hits_dev's kernel -- no
+ * locations stored, no plan, no pieces.  Larger tables, RBG_DOC_HITS_FUSED=0 (A/B) and any setting of RBG_DOC_HITS_CHUNK_LOCS (it bounds the location
+ * scratch, which only that path has) take the two-step path described above; the outputs and rbg_counters are the same either way. */
+int rbg_doc_hits_locs(rbg_index *, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t max_hits, uint64_t *lo, uint64_t *hi,
+                      uint64_t *sets /* [N * W] */, uint32_t *ndocs /* [N] */, uint32_t *nodoc /* [N] nullable */,
+                      uint64_t *doc_reads /* [ndocs] nullable, accumulates */, uint64_t *doc_locs /* [ndocs] nullable, accumulates */);
 
 /* ---- global counters (the values the 8-GPU run reduces over RCCL) -------------------------- */
 /* {reads processed, reads matched (non-empty range), sum of occ, sum of located positions}

@@ -89,6 +89,7 @@ TALLY_INFO = ("entries", "capacity", "grows", "records", "elements", "dropped")
 TALLY_PER_READ, TALLY_DROP_SITE_CONFLICTS = 1, 2
 TALLY_READ_INFO = ("reads", "elements_seen", "lost", "site_dropped")
 DOCS_MAX = 1 << 16        # RBG_DOCS_MAX: documents a device table holds (rbg_docs_prepare)
+LOCATE_DOCS_MAX = 1024    # RBG_LOCATE_DOCS_MAX: documents up to which rbg_locate_doc_hits_dev runs (the table in LDS)
 DOC_NONE = 0xFFFFFFFF     # RBG_DOC_NONE: the document of a position that has none
 
 
@@ -229,6 +230,8 @@ _PROTOS = [
     ("rbg_doc_hits_dev", C.c_int, [VP, VP, VP, U64, VP, VP, VP, VP, VP]),
     ("rbg_doc_hits_dev32", C.c_int, [VP, VP, VP, U64, VP, VP, VP, VP, VP]),
     ("rbg_doc_hits", C.c_int, [VP, VP, VP, U64, U64, VP, VP, VP, VP, VP, VP]),
+    ("rbg_locate_doc_hits_dev", C.c_int, [VP, VP, VP, VP, U64, U64, VP, VP, VP, VP, VP, VP, VP]),
+    ("rbg_doc_hits_locs", C.c_int, [VP, VP, VP, U64, U64, VP, VP, VP, VP, VP, VP, VP]),
     ("rbg_set_default_option", C.c_int, [C.c_int, C.c_int64]),
     ("rbg_get_default_option", C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
 ]
@@ -700,10 +703,35 @@ class RowBowt:
             torch.cuda.synchronize()
             return d_doc[:M].cpu().numpy().view(np.uint32), d_off[:M].cpu().numpy().view(np.uint64)
 
-    def doc_hits(self, seqs, off, max_hits=MAXU):
+    def locate_doc_hits(self, d_lo, d_hi, d_k, max_hits=MAXU, order=True, doc_locs=False):
+        """rbg_locate_doc_hits_dev on device tensors (int64 [N]: what rbg_find_range_w_toehold_dev wrote): the chains walked and reduced in one kernel, no
+        location stored -> (sets[N, W] int64, ndocs[N] int32, nodoc[N] int32, doc_reads[ndocs] int64[, doc_locs[ndocs] int64]) on the same device, the bit
+        patterns of rbg_doc_hits' outputs.  order: sort the chains by toehold first (rbg_locate_order_dev).  The table must be prepared (docs_prepare)"""
+        import torch
+        N = int(d_lo.numel())
+        W = self.doc_hits_words()
+        nd = self.doc_table(names=False)[0]
+        with torch.cuda.device(d_lo.device):
+            st = torch.cuda.current_stream().cuda_stream
+            ws = None
+            if order and N:
+                ws_bytes = int(self.L.rbg_locate_order_ws_bytes(N))
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=d_lo.device)
+                _check(self.L.rbg_locate_order_dev(self.h, d_k.data_ptr(), N, ws.data_ptr(), ws_bytes, st), "rbg_locate_order_dev")
+            sets = torch.zeros((N, W), dtype=torch.int64, device=d_lo.device)
+            ndocs, nodoc = (torch.zeros(N, dtype=torch.int32, device=d_lo.device) for _ in range(2))
+            reads = torch.zeros(nd, dtype=torch.int64, device=d_lo.device)
+            locs = torch.zeros(nd, dtype=torch.int64, device=d_lo.device) if doc_locs else None
+            _check(self.L.rbg_locate_doc_hits_dev(self.h, d_lo.data_ptr(), d_hi.data_ptr(), d_k.data_ptr(), N, max_hits, ws.data_ptr() if ws is not None else None,
+                                                  sets.data_ptr(), ndocs.data_ptr(), nodoc.data_ptr(), reads.data_ptr(),
+                                                  locs.data_ptr() if doc_locs else None, st), "rbg_locate_doc_hits_dev")
+        return (sets, ndocs, nodoc, reads, locs) if doc_locs else (sets, ndocs, nodoc, reads)
+
+    def doc_hits(self, seqs, off, max_hits=MAXU, doc_locs=False):
         """rbg_doc_hits: per read its range and the SET of documents its locations (locs_at with max_hits) fall in, the locations staying on the
         device -> (lo, hi, sets[N, W] uint64 -- bit d % 64 of word d / 64 = document d --, ndocs[N], nodoc[N] uint32, doc_reads[ndocs] uint64 = the
-        reads of this batch that hit each document)"""
+        reads of this batch that hit each document).  doc_locs=True (rbg_doc_hits_locs): one more array, doc_locs[ndocs] uint64 = the locations of this
+        batch in each document"""
         seqs, off = np.ascontiguousarray(seqs, dtype=np.uint8), _u64(off)
         N = len(off) - 1
         self.docs_prepare()
@@ -713,6 +741,11 @@ class RowBowt:
         sets = np.zeros((N, W), np.uint64)
         ndocs, nodoc = np.zeros(N, np.uint32), np.zeros(N, np.uint32)
         doc_reads = np.zeros(nd, np.uint64)
+        if doc_locs:
+            dl = np.zeros(nd, np.uint64)
+            _check(self.L.rbg_doc_hits_locs(self.h, _p(seqs), _p(off), N, max_hits, _p(lo), _p(hi), _p(sets), _p(ndocs), _p(nodoc), _p(doc_reads), _p(dl)),
+                   "rbg_doc_hits_locs")
+            return lo, hi, sets, ndocs, nodoc, doc_reads, dl
         _check(self.L.rbg_doc_hits(self.h, _p(seqs), _p(off), N, max_hits, _p(lo), _p(hi), _p(sets), _p(ndocs), _p(nodoc), _p(doc_reads)), "rbg_doc_hits")
         return lo, hi, sets, ndocs, nodoc, doc_reads
 

@@ -176,6 +176,28 @@ __global__ __launch_bounds__(kDocBlock) void k_doc_hits_wide(const DocTab t, con
                                   nodoc_out);
 }
 
+// locations per document from stored locations (the two-step path of rbg_doc_hits_locs): one location per lane, grid-stride, the table read from global
+// memory as in k_resolve_offsets; the counts per workgroup in LDS while ndocs <= kDocLdsDocs (launched with ndocs * 8 bytes), global atomics above
+template <typename L>
+__global__ __launch_bounds__(kDocBlock) void k_doc_locs(const DocTab t, const L *__restrict__ locs, const uint64_t M, unsigned long long *__restrict__ doc_locs) {
+    const bool lds = t.ndocs <= kDocLdsDocs;   // (the same for every lane)
+    if (lds) {
+        for (uint32_t k = threadIdx.x; k < t.ndocs; k += kDocBlock) doc_lds[k] = 0;
+        __syncthreads();
+    }
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t j = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; j < M; j += stride) {
+        const uint32_t r = doc_rank(t.sorted, t.dir, t.size, t.shift, widen(locs[j]));
+        if (r) atomicAdd(lds ? &doc_lds[r - 1] : &doc_locs[r - 1], 1ull);
+    }
+    if (!lds) return;
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < t.ndocs; k += kDocBlock) {
+        const unsigned long long c = doc_lds[k];
+        if (c) atomicAdd(&doc_locs[k], c);
+    }
+}
+
 inline int doc_grid(const uint64_t lanes) {
     const uint64_t blocks = (lanes + kDocBlock - 1) / kDocBlock;
     return static_cast<int>(blocks > kDocMaxBlocks ? kDocMaxBlocks : (blocks ? blocks : 1));
@@ -229,6 +251,18 @@ int launch_resolve_offsets(const uint64_t *sorted, const uint32_t *dir, uint64_t
     hipStream_t st = static_cast<hipStream_t>(stream);
     return locs32 ? resolve_offsets_launch(t, static_cast<const uint32_t *>(locs), M, doc, offset, st)
                   : resolve_offsets_launch(t, static_cast<const uint64_t *>(locs), M, doc, offset, st);
+}
+
+int launch_doc_locs(const uint64_t *sorted, const uint32_t *dir, uint64_t size, uint32_t ndocs, uint32_t shift, uint32_t ndir, const void *locs, bool locs32,
+                    uint64_t M, uint64_t *doc_locs, void *stream) {
+    if (M == 0) return 0;
+    const DocTab t = doc_tab(sorted, dir, size, ndocs, shift, ndir);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t lds = ndocs <= kDocLdsDocs ? static_cast<size_t>(ndocs) * 8 : 0;
+    unsigned long long *dl = reinterpret_cast<unsigned long long *>(doc_locs);
+    if (locs32) hipLaunchKernelGGL(k_doc_locs<uint32_t>, dim3(doc_grid(M)), dim3(kDocBlock), lds, st, t, static_cast<const uint32_t *>(locs), M, dl);
+    else hipLaunchKernelGGL(k_doc_locs<uint64_t>, dim3(doc_grid(M)), dim3(kDocBlock), lds, st, t, static_cast<const uint64_t *>(locs), M, dl);
+    return static_cast<int>(hipGetLastError());
 }
 
 int launch_doc_hits(const uint64_t *sorted, const uint32_t *dir, uint64_t size, uint32_t ndocs, uint32_t shift, uint32_t ndir, const void *locs, bool locs32,

@@ -2,6 +2,7 @@
 #include <cstdlib>
 
 #include "rbg_device.hpp"
+#include "rbg_locate_docs.hpp"
 
 namespace rbg {
 namespace {
@@ -219,6 +220,19 @@ __global__ __launch_bounds__(256, (chain_stage_waves<ChainStage<P, CH, SUB, RING
     }
 }
 
+// ---- document hits from the walk itself (rbg_locate_docs.hpp): k_locate_fill's chains, the positions resolved and reduced instead of stored ----
+// LAUNCH BOUNDS: 256 threads; tools/kernel_resources.py lists registers and scratch (none).  The dynamic LDS is what the table needs.
+extern __shared__ unsigned long long locate_docs_lds[];
+template <typename P, bool LOCS>
+__global__ __launch_bounds__(kLocDocBlock) void k_locate_docs(const DevIndex ix, const DocTable t, const uint64_t *__restrict__ lo, const uint64_t *__restrict__ hi,
+                                                             const uint64_t *__restrict__ k, const uint64_t N, const uint64_t max_hits,
+                                                             const uint32_t *__restrict__ order, const uint64_t *__restrict__ skeys, uint64_t *__restrict__ sets,
+                                                             uint32_t *__restrict__ ndocs_out, uint32_t *__restrict__ nodoc_out,
+                                                             unsigned long long *__restrict__ doc_reads, unsigned long long *__restrict__ doc_locs) {
+    locate_docs_walk<P, LOCS>(ix, t, locate_docs_lds, lo, hi, k, N, max_hits, order, skeys, sets, ndocs_out, nodoc_out, doc_reads, doc_locs,
+                              [&](const uint64_t k1) { return phi_step<P>(ix, k1); });
+}
+
 }  // namespace
 
 // ---- chain ordering for locate: permutation of the reads by toehold value (radix sort) ----------
@@ -368,6 +382,33 @@ int launch_locate_fill(const DevIndex &ix, const LaunchCfg &cfg, const uint64_t 
         if (ix.pos_bytes == 4) RBG_LAUNCH_K3(uint32_t, false, uint64_t, false, locs); else RBG_LAUNCH_K3(uint64_t, false, uint64_t, false, locs);
     }
 #undef RBG_LAUNCH_K3
+    return static_cast<int>(hipGetLastError());
+}
+
+int launch_locate_doc_hits(const DevIndex &ix, const LaunchCfg &cfg, const DocTable &t, const uint64_t *lo, const uint64_t *hi, const uint64_t *k, uint64_t N,
+                           uint64_t max_hits, const void *order, uint64_t *sets, uint32_t *ndocs_out, uint32_t *nodoc_out, uint64_t *doc_reads,
+                           uint64_t *doc_locs, void *stream) {
+    (void)cfg;
+    if (t.ndocs == 0 || t.ndocs > kLocDocLdsDocs) return static_cast<int>(hipErrorInvalidValue);
+    if (N == 0) return 0;
+    if (order && N >= 0xFFFFFFFFull) return static_cast<int>(hipErrorInvalidValue);   // (launch_locate_order refuses it too)
+    const uint64_t *skeys = order ? reinterpret_cast<const uint64_t *>(static_cast<const char *>(order) + order_layout(N).keys) : nullptr;
+    if (ix.layout == 2 && !ix.phi_slots)   // run-indexed layout with the phi list (k_runs.hip); with phi slots the kernels here answer its phi
+        return launch_locate_doc_hits_runs(ix, t, lo, hi, k, N, max_hits, order, skeys, sets, ndocs_out, nodoc_out, doc_reads, doc_locs, stream);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(locate_docs_grid(N)), block(kLocDocBlock);
+    const uint32_t *perm = static_cast<const uint32_t *>(order);
+    unsigned long long *dr = reinterpret_cast<unsigned long long *>(doc_reads), *dl = reinterpret_cast<unsigned long long *>(doc_locs);
+    const size_t lds = locate_docs_lds_bytes(t.ndocs, t.ndir, doc_locs != nullptr);
+#define RBG_LAUNCH_LD(PT, LC) \
+    do { \
+        auto kern = k_locate_docs<PT, LC>; \
+        raise_lds(kern, lds); \
+        hipLaunchKernelGGL(kern, grid, block, lds, st, ix, t, lo, hi, k, N, max_hits, perm, skeys, sets, ndocs_out, nodoc_out, dr, dl); \
+    } while (0)
+    if (ix.pos_bytes == 4) { if (doc_locs) RBG_LAUNCH_LD(uint32_t, true); else RBG_LAUNCH_LD(uint32_t, false); }
+    else { if (doc_locs) RBG_LAUNCH_LD(uint64_t, true); else RBG_LAUNCH_LD(uint64_t, false); }
+#undef RBG_LAUNCH_LD
     return static_cast<int>(hipGetLastError());
 }
 

@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "rbg_runs2_device.hpp"
+#include "rbg_locate_docs.hpp"
 #include "rbg_jump.h"
 
 namespace rbg {
@@ -447,6 +448,30 @@ __global__ __launch_bounds__(256, 4) void k_locate_fill_runs2(const DevIndex ix,
     }
 }
 
+// ---- document hits from the walk itself (rbg_locate_docs.hpp) over the run-indexed layout's phi list: k_locate_fill_runs2's chains and its phi
+// step (the branch for a toehold below zero and lane_phi, as that kernel applies them), the positions resolved and reduced instead of stored ----
+extern __shared__ unsigned long long locate_docs_lds[];
+template <typename P, bool LOCS>
+__global__ __launch_bounds__(kLocDocBlock) void k_locate_docs_runs2(const DevIndex ix, const DocTable t, const uint64_t *__restrict__ lo,
+                                                                   const uint64_t *__restrict__ hi, const uint64_t *__restrict__ k, const uint64_t N,
+                                                                   const uint64_t max_hits, const uint32_t *__restrict__ order,
+                                                                   const uint64_t *__restrict__ skeys, uint64_t *__restrict__ sets,
+                                                                   uint32_t *__restrict__ ndocs_out, uint32_t *__restrict__ nodoc_out,
+                                                                   unsigned long long *__restrict__ doc_reads, unsigned long long *__restrict__ doc_locs) {
+    const uint64_t n = ix.n;
+    locate_docs_walk<P, LOCS>(ix, t, locate_docs_lds, lo, hi, k, N, max_hits, order, skeys, sets, ndocs_out, nodoc_out, doc_reads, doc_locs,
+                              [&](const uint64_t k1) -> uint64_t {
+        if (k1 >= n) return (ix.phi_last_base + (k1 - ix.phi_last_pos)) % n;   // a toehold below zero (k_locate.hip phi_step)
+        bool found;
+        uint64_t val;
+        uint32_t ents, rounds;
+        lane_phi<P>(ix, k1, found, val, ents, rounds);
+        uint64_t s = found ? val : ix.phi_last_base + k1 + 1;   // no sampled position before k1: the last one, delta = k1 + 1 (toehold_sa.hpp:59,65)
+        if (s >= n) s -= n;
+        return s;
+    });
+}
+
 }  // namespace
 
 // `packed`: src_a = chunks, src_b = meta (see the kernel); stats != nullptr: the instrumented instantiation
@@ -537,6 +562,28 @@ int launch_locate_fill_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint
         RBG_LAUNCH_LFR2(uint64_t, uint64_t, false, false, locs);
     }
 #undef RBG_LAUNCH_LFR2
+    return static_cast<int>(hipGetLastError());
+}
+
+int launch_locate_doc_hits_runs(const DevIndex &ix, const DocTable &t, const uint64_t *lo, const uint64_t *hi, const uint64_t *k, uint64_t N, uint64_t max_hits,
+                                const void *order, const uint64_t *skeys, uint64_t *sets, uint32_t *ndocs_out, uint32_t *nodoc_out, uint64_t *doc_reads,
+                                uint64_t *doc_locs, void *stream) {
+    if (t.ndocs == 0 || t.ndocs > kLocDocLdsDocs) return static_cast<int>(hipErrorInvalidValue);
+    if (N == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(locate_docs_grid(N)), block(kLocDocBlock);
+    const uint32_t *perm = static_cast<const uint32_t *>(order);
+    unsigned long long *dr = reinterpret_cast<unsigned long long *>(doc_reads), *dl = reinterpret_cast<unsigned long long *>(doc_locs);
+    const size_t lds = locate_docs_lds_bytes(t.ndocs, t.ndir, doc_locs != nullptr);
+#define RBG_LAUNCH_LDR(PT, LC) \
+    do { \
+        auto kern = k_locate_docs_runs2<PT, LC>; \
+        raise_lds(kern, lds); \
+        hipLaunchKernelGGL(kern, grid, block, lds, st, ix, t, lo, hi, k, N, max_hits, perm, skeys, sets, ndocs_out, nodoc_out, dr, dl); \
+    } while (0)
+    if (ix.pos_bytes == 4) { if (doc_locs) RBG_LAUNCH_LDR(uint32_t, true); else RBG_LAUNCH_LDR(uint32_t, false); }
+    else { if (doc_locs) RBG_LAUNCH_LDR(uint64_t, true); else RBG_LAUNCH_LDR(uint64_t, false); }
+#undef RBG_LAUNCH_LDR
     return static_cast<int>(hipGetLastError());
 }
 

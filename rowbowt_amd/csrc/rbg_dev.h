@@ -603,6 +603,25 @@ int launch_resolve_offsets(const uint64_t *sorted, const uint32_t *dir, uint64_t
 int launch_doc_hits(const uint64_t *sorted, const uint32_t *dir, uint64_t size, uint32_t ndocs, uint32_t shift, uint32_t ndir, const void *locs, bool locs32,
                     const uint64_t *loc_off, uint64_t N, uint64_t *sets, uint32_t *ndocs_out, uint32_t *nodoc_out, uint64_t *doc_reads, int group,
                     void *stream);
+// document hits from the phi walk itself (rbg_locate_docs.hpp; the kernels beside the fill kernels they mirror, k_locate.hip and k_runs.hip): K3's chains over
+// (lo, hi, k) with every position resolved as it is produced, nothing stored per location.  order: launch_locate_order's workspace or nullptr; every output
+// nullable; doc_reads and doc_locs (locations per document) accumulate.  hipErrorInvalidValue above kLocDocLdsDocs documents: the table must fit LDS
+constexpr uint32_t kLocDocLdsDocs = 1024;      // = k_docs.hip kDocLdsDocs: the largest table these kernels stage
+struct DocTable {
+    const uint64_t *sorted;
+    const uint32_t *dir;   // ndir = buckets + 1 entries
+    uint64_t size;
+    uint32_t ndocs, shift, ndir;
+};
+int launch_locate_doc_hits(const DevIndex &ix, const LaunchCfg &cfg, const DocTable &t, const uint64_t *lo, const uint64_t *hi, const uint64_t *k, uint64_t N,
+                           uint64_t max_hits, const void *order, uint64_t *sets, uint32_t *ndocs_out, uint32_t *nodoc_out, uint64_t *doc_reads,
+                           uint64_t *doc_locs, void *stream);
+int launch_locate_doc_hits_runs(const DevIndex &ix, const DocTable &t, const uint64_t *lo, const uint64_t *hi, const uint64_t *k, uint64_t N, uint64_t max_hits,
+                                const void *order, const uint64_t *skeys, uint64_t *sets, uint32_t *ndocs_out, uint32_t *nodoc_out, uint64_t *doc_reads,
+                                uint64_t *doc_locs, void *stream);
+// locations per document from stored locations (k_docs.hip; the two-step path of rbg_doc_hits_locs): doc_locs[d] += the locations among locs[0, M) in document d
+int launch_doc_locs(const uint64_t *sorted, const uint32_t *dir, uint64_t size, uint32_t ndocs, uint32_t shift, uint32_t ndir, const void *locs, bool locs32,
+                    uint64_t M, uint64_t *doc_locs, void *stream);
 // rb_markers' report on the device (k_report.hip; rbg_markers_report[_text]): both strands of raw reads, the canonical form of the seeding kernels' records
 // (min_range gate, marker_cmp sort, unique, the two per-seed filters; group: lanes per short segment, 4 / 16 / 64, or 0 = chosen on the device --
 // report_canon_group(): what RBG_REPORT_GROUP forces), the per-read choice of printed records, and the lines by elements as in k_text.hip

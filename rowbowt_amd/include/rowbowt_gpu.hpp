@@ -238,7 +238,18 @@ class RowBowt {
         std::vector<uint64_t> doc_reads;    // [documents]
         bool hit(uint64_t read, uint64_t d) const { return (sets[read * words + d / 64] >> (d % 64)) & 1u; }
     };
+    // the same with the LOCATIONS per document (rbg_doc_hits_locs): doc_locs[d] = the locations of this batch that fall in document d; their sum plus the sum
+    // of nodoc is the number of locations locs_at(max_hits) would have returned
+    DocHits doc_hits(const std::vector<std::string> &queries, uint64_t max_hits, std::vector<uint64_t> &doc_locs) const {
+        return doc_hits_impl(queries, max_hits, &doc_locs);
+    }
+    DocHits doc_hits(const std::vector<std::string> &queries, std::vector<uint64_t> &doc_locs) const {
+        return doc_hits_impl(queries, static_cast<uint64_t>(-1), &doc_locs);
+    }
     DocHits doc_hits(const std::vector<std::string> &queries, uint64_t max_hits = static_cast<uint64_t>(-1)) const {
+        return doc_hits_impl(queries, max_hits, nullptr);
+    }
+    DocHits doc_hits_impl(const std::vector<std::string> &queries, uint64_t max_hits, std::vector<uint64_t> *doc_locs) const {
         detail::Batch b;
         for (const auto &q : queries) b.add(q);
         const uint64_t N = b.size();
@@ -254,8 +265,14 @@ class RowBowt {
         r.ndocs.assign(N, 0);
         r.nodoc.assign(N, 0);
         r.doc_reads.assign(nd, 0);
-        detail::check(rbg_doc_hits(ix_.get(), b.data(), b.off.data(), N, max_hits, lo.data(), hi.data(), r.sets.data(), r.ndocs.data(), r.nodoc.data(),
-                                   r.doc_reads.data()), "rbg_doc_hits");
+        if (doc_locs) {
+            doc_locs->assign(nd, 0);
+            detail::check(rbg_doc_hits_locs(ix_.get(), b.data(), b.off.data(), N, max_hits, lo.data(), hi.data(), r.sets.data(), r.ndocs.data(), r.nodoc.data(),
+                                            r.doc_reads.data(), doc_locs->data()), "rbg_doc_hits_locs");
+        } else {
+            detail::check(rbg_doc_hits(ix_.get(), b.data(), b.off.data(), N, max_hits, lo.data(), hi.data(), r.sets.data(), r.ndocs.data(), r.nodoc.data(),
+                                       r.doc_reads.data()), "rbg_doc_hits");
+        }
         r.ranges.resize(N);
         for (uint64_t i = 0; i < N; ++i) r.ranges[i] = {lo[i], hi[i]};
         return r;

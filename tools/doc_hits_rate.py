@@ -8,6 +8,9 @@ attaches them, 10 M x 100 bp reads with sub_rate 0.1.  HIP events on the launch 
     writes about 1/40 of it, so a kernel slower than the copy has a step to name;
   - end to end on the same reads in pageable host memory (the method of tools/host_api_rate.py): rbg_doc_hits against rbg_find_range_w_toehold +
     rbg_locs_at; and, for the first --check-reads reads, rbg_doc_hits' outputs against the oracle's locations under the lookup rule.
+  - rbg_locate_doc_hits_dev (the walk that reduces as it goes, nothing stored per location) with every output, the sets alone, with doc_locs, and with
+    d_order NULL, ALTERNATING in the same loop with the two-step sum it replaces -- rbg_locate_plan_dev + rbg_locate_fill_dev + rbg_doc_hits_dev, and the
+    32-bit pair rbg_doc_hits takes at 4-byte positions -- median of --steps after --warmup; end to end, rbg_doc_hits with RBG_DOC_HITS_FUSED 0 and 1.
 One JSON line per measurement.  GPU box only."""
 import argparse
 import json
@@ -142,11 +145,82 @@ for what, (med, lo_, hi_) in rows.items():
 copy_ms, hit_ms = rows["device-to-device hipMemcpyAsync of the locations"][0], rows["rbg_doc_hits_dev, group chosen on the device"][0]
 print(json.dumps({"rbg_doc_hits_dev / copy of the locations": round(hit_ms / copy_ms, 3), "rbg_doc_hits_dev / K3": round(hit_ms / rows["K3: rbg_locate_fill_dev, chains ordered"][0], 3)}),
       flush=True)
-del d_copy, d_locs, d_sets, d_seqs
+
+# ---- the fused walk against the two-step sum, alternating in one loop: the same (lo, hi, k), the same order workspace, the same outputs ----
+d_dl = torch.zeros(H, dtype=torch.int64, device=dev)
+d_sets2, d_nd2, d_no2, d_dr2 = new(N * W), new(N, torch.int32), new(N, torch.int32), torch.zeros(H, dtype=torch.int64, device=dev)
+pos32 = rb.info().pos_bytes == 4
+d_locs32 = new(total, torch.int32) if pos32 else None
+
+
+def two_step():
+    ok(L.rbg_locate_plan_dev(rb.h, d_lo.data_ptr(), d_hi.data_ptr(), N, MAXU, d_loc_off.data_ptr(), d_tmp.data_ptr(), tmp_bytes, st))
+    k3()
+    hits()
+
+
+def two_step32():
+    ok(L.rbg_locate_plan_dev(rb.h, d_lo.data_ptr(), d_hi.data_ptr(), N, MAXU, d_loc_off.data_ptr(), d_tmp.data_ptr(), tmp_bytes, st))
+    ok(L.rbg_locate_fill_dev32(rb.h, d_lo.data_ptr(), d_hi.data_ptr(), d_k.data_ptr(), N, MAXU, d_loc_off.data_ptr(), d_locs32.data_ptr(), d_ws.data_ptr(), st))
+    ok(L.rbg_doc_hits_dev32(rb.h, d_locs32.data_ptr(), d_loc_off.data_ptr(), N, d_sets.data_ptr(), d_nd.data_ptr(), d_no.data_ptr(), d_dr.data_ptr(), st))
+
+
+def fused(order=True, counts=True, locs=False):
+    def run():
+        ok(L.rbg_locate_doc_hits_dev(rb.h, d_lo.data_ptr(), d_hi.data_ptr(), d_k.data_ptr(), N, MAXU, d_ws.data_ptr() if order else None, d_sets2.data_ptr(),
+                                     d_nd2.data_ptr() if counts else None, d_no2.data_ptr() if counts else None, d_dr2.data_ptr() if counts else None,
+                                     d_dl.data_ptr() if locs else None, st))
+    return run
+
+
+ab = {"two-step: rbg_locate_plan_dev + rbg_locate_fill_dev + rbg_doc_hits_dev": two_step}
+if pos32:
+    ab["two-step, 32-bit locations: plan + rbg_locate_fill_dev32 + rbg_doc_hits_dev32"] = two_step32
+ab["rbg_locate_doc_hits_dev, every output but doc_locs, ordered"] = fused()
+ab["rbg_locate_doc_hits_dev, sets only, ordered"] = fused(counts=False)
+ab["rbg_locate_doc_hits_dev, every output with doc_locs, ordered"] = fused(locs=True)
+ab["rbg_locate_doc_hits_dev, every output but doc_locs, d_order NULL"] = fused(order=False)
+ab_ms = {what: [] for what in ab}
+for i in range(args.warmup + args.steps):
+    for what, step in ab.items():   # (alternating: every row sees the same clocks and the same neighbours)
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        step()
+        b.record()
+        b.synchronize()
+        if i >= args.warmup:
+            ab_ms[what].append(a.elapsed_time(b))
+for what, t in ab_ms.items():
+    print(json.dumps({"step": what, "ms_median": round(float(np.median(t)), 4), "ms_min": round(min(t), 4), "ms_max": round(max(t), 4), "reads": N, "locations": total}),
+          flush=True)
+torch.cuda.synchronize()
+same = bool((d_sets2 == d_sets).all().item() and (d_nd2 == d_nd).all().item() and (d_no2 == d_no).all().item())
+base = min(float(np.median(t)) for what, t in ab_ms.items() if what.startswith("two-step"))
+fused_ms = float(np.median(ab_ms["rbg_locate_doc_hits_dev, every output but doc_locs, ordered"]))
+spread = max(max(t) - min(t) for what, t in ab_ms.items() if what.startswith("two-step"))
+print(json.dumps({"fused / two-step (the faster two-step row)": round(fused_ms / base, 3), "two-step spread ms": round(spread, 4),
+                  "fused outputs equal the two-step outputs": same}), flush=True)
+assert same
+del d_copy, d_locs, d_sets, d_seqs, d_sets2, d_locs32
 torch.cuda.empty_cache()
 
 if args.host_calls > 0:
     best_hits = best_locs = 1e9
+    # the A/B switch of the host call, the two-step path against the fused one, ALTERNATING call by call after one call of each that is not counted: calls
+    # later in a process run slower than the first ones whatever they are (the rows below come out 10 % above a fresh process's)
+    ab_s = {"0": [], "1": []}
+    for rep in range(args.host_calls + 1):
+        for fused_env in ("0", "1"):
+            os.environ["RBG_DOC_HITS_FUSED"] = fused_env
+            t0 = time.perf_counter()
+            lo, hi, sets, ndocs, nodoc, doc_reads = rb.doc_hits(seqs, off)
+            if rep:
+                ab_s[fused_env].append(time.perf_counter() - t0)
+    os.environ.pop("RBG_DOC_HITS_FUSED", None)
+    for fused_env, t in ab_s.items():
+        print(json.dumps({"end to end, pageable host memory": f"rbg_doc_hits, RBG_DOC_HITS_FUSED={fused_env}", "s": round(min(t), 4), "s_all": [round(x, 4) for x in t],
+                          "reads_per_s": N / min(t)}), flush=True)
     for _ in range(args.host_calls):
         t0 = time.perf_counter()
         lo, hi, sets, ndocs, nodoc, doc_reads = rb.doc_hits(seqs, off)
