@@ -395,6 +395,34 @@ int rbg_wait_text(rbg_index *, const char *text);
 int rbg_release_text(rbg_index *, const char *text);
 /* make `count` pinned text buffers of `bytes` now (pinning a few hundred MB takes tenths of a second: a tool does it before its clock starts) */
 int rbg_reserve_text(rbg_index *, uint64_t bytes, int count);
+/* ---- SAM lines of raw reads, both strands, written on the device ------------------------------------------------------------------------
+ * Per read: the greedy seeds (rbg_greedy_longest_seed's choice, min_length >= 1) of the read as given and of its reverse complement -- ACGTacgt ->
+ * TGCAtgca, every other byte itself, so an N stays N and ends a seed (not rb_markers' seq_ntoa_table) --; the strand with the longer seed is kept, a tie
+ * goes to forward; its locations in locate order (locs_at with the seed's toehold) are resolved as rbg_resolve_offset resolves them.  With the read's
+ * length m and the seed [a, b) in the searched orientation, tab-separated and "\n"-terminated:
+ *   mapped, primary (location 1, SA[hi])   QNAME FLAG RNAME POS 255 CIGAR * 0 0 SEQ QUAL NH:i:<hi - lo + 1> HI:i:1
+ *       FLAG 16 on the reverse strand, else 0; POS = the offset of the seed's own text position in its document + 1 (nothing is subtracted for the
+ *       a clipped bases); CIGAR = [a "S"] (b - a) "M" [(m - b) "S"]; SEQ the searched orientation, QUAL reversed with it ("*" without qual_base)
+ *   secondary (RBG_SAM_SECONDARY only), locations j = 2 .. min(occ, max_hits):  the same with FLAG | 256, SEQ "*", QUAL "*", HI:i:<j>
+ *   unmapped (no seed of min_length on either strand)   QNAME 4 * 0 0 * * 0 0 SEQ QUAL   the read as given, no tags; an empty read: SEQ "*", QUAL "*"
+ * Without RBG_SAM_SECONDARY max_hits is taken as 1 for the walk (and max_hits == 0 as 1 with it: the primary line is always there).  MAPQ is always 255.
+ * The document of a line is that of its first aligned base: a seed that runs over a document boundary is NOT detected.
+ * Reads, qualities (qual_base nullable: every QUAL is "*"; read i's quality is the seq_len[i] bytes at qual_begin[i]) and names are N spans of their
+ * bases.  *text is one of the handle's pinned text buffers with rbg_align_text's protocol (rbg_wait_text, rbg_release_text, rbg_reserve_text); N == 0
+ * gives *text = NULL, *text_len = 0.  RBG_ENOTLOADED without the toehold SA or the document list; RBG_EARG: min_length == 0 (a zero-length seed has
+ * the full range), unknown flags, N >= 2^32, 2^32 or more bytes of reads or of names, a location before every document (as rbg_align_text).  Works
+ * on replicas.  rbg_counters: reads += 2N (both strands searched), locations += every location walked, once.  RBG_SAM_TRACE=1 prints the steps' times at
+ * exit; RBG_SAM_GRID_CAP=<workgroups> caps the grids of the call's own kernels (tests, A/Bs). */
+#define RBG_SAM_SECONDARY 1u   /* also one line per further location, up to max_hits */
+int rbg_align_sam(rbg_index *, const char *seq_base, const uint64_t *seq_begin, const uint32_t *seq_len,
+                  const char *qual_base /* nullable: every QUAL is "*" */, const uint64_t *qual_begin /* lengths = seq_len */,
+                  const char *name_base, const uint64_t *name_begin, const uint32_t *name_len, uint64_t N,
+                  uint64_t min_length, uint64_t max_hits, uint32_t flags, const char **text, uint64_t *text_len);
+/* The header that goes with those lines (host): "@HD\tVN:1.6\tSO:unsorted\n", then per document in sorted-start order "@SQ\tSN:<name>\tLN:<len>\n", then
+ * pg_line as given (nullable).  len = the next sorted start - this one, for the last document rbg_info().n - its start: an UPPER BOUND of the
+ * sequence's length, which includes the separators between documents and the terminator.  *text: NUL-terminated, through rbg_free_buffer.
+ * RBG_ENOTLOADED without a document list. */
+int rbg_sam_header(rbg_index *, const char *pg_line /* nullable, appended as given */, char **text, uint64_t *text_len);
 /* ---- rb_markers' report (what the tool prints), made on the device --------------------------------------------------------------
  * Everything rb_markers does between get_markers_greedy_seeding / get_markers_lmems and its output (rb_markers.cpp:228-315, :365-382,
  * :396-413, :429-519), for a batch of RAW reads: both strands (sequence 2i = read i through seq_ntoa_table -- ACGT of either case, N/n -> 'A',

@@ -89,6 +89,7 @@ TALLY_INFO = ("entries", "capacity", "grows", "records", "elements", "dropped")
 TALLY_PER_READ, TALLY_DROP_SITE_CONFLICTS = 1, 2
 TALLY_READ_INFO = ("reads", "elements_seen", "lost", "site_dropped")
 DOCS_MAX = 1 << 16        # RBG_DOCS_MAX: documents a device table holds (rbg_docs_prepare)
+SAM_SECONDARY = 1         # RBG_SAM_SECONDARY: rbg_align_sam also writes one line per further location, up to max_hits
 LOCATE_DOCS_MAX = 1024    # RBG_LOCATE_DOCS_MAX: documents up to which rbg_locate_doc_hits_dev runs (the table in LDS)
 DOC_NONE = 0xFFFFFFFF     # RBG_DOC_NONE: the document of a position that has none
 
@@ -232,6 +233,8 @@ _PROTOS = [
     ("rbg_doc_hits", C.c_int, [VP, VP, VP, U64, U64, VP, VP, VP, VP, VP, VP]),
     ("rbg_locate_doc_hits_dev", C.c_int, [VP, VP, VP, VP, U64, U64, VP, VP, VP, VP, VP, VP, VP]),
     ("rbg_doc_hits_locs", C.c_int, [VP, VP, VP, U64, U64, VP, VP, VP, VP, VP, VP, VP]),
+    ("rbg_align_sam", C.c_int, [VP, VP, VP, VP, VP, VP, VP, VP, VP, U64, U64, U64, C.c_uint32, C.POINTER(VP), C.POINTER(U64)]),
+    ("rbg_sam_header", C.c_int, [VP, C.c_char_p, C.POINTER(VP), C.POINTER(U64)]),
     ("rbg_set_default_option", C.c_int, [C.c_int, C.c_int64]),
     ("rbg_get_default_option", C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
 ]
@@ -775,6 +778,41 @@ class RowBowt:
             return C.string_at(text, n.value)
         finally:
             self.L.rbg_release_text(self.h, text)
+
+    def align_sam(self, seqs, quals, names, min_length=20, max_hits=16, secondary=False):
+        """rbg_align_sam: the SAM lines of a batch of raw reads (bytes), both strands searched, written on the device.  seqs / names: lists of bytes;
+        quals: a list of bytes of the reads' lengths, or None (every QUAL is "*")"""
+        def spans(items):
+            ln = np.array([len(x) for x in items], dtype=np.uint32)
+            beg = np.zeros(len(items), dtype=np.uint64)
+            if len(items) > 1:
+                beg[1:] = np.cumsum(ln[:-1], dtype=np.uint64)
+            blob = b"".join(items)
+            return C.create_string_buffer(blob, len(blob) + 1), beg, ln
+        if quals is not None and [len(q) for q in quals] != [len(s) for s in seqs]:
+            raise ValueError("align_sam: a quality string per read, of the read's length")
+        if len(names) != len(seqs):
+            raise ValueError("align_sam: a name per read")
+        sbuf, sbeg, slen = spans(seqs)
+        qbuf, qbeg, _ = spans(quals) if quals is not None else (None, None, None)
+        nbuf, nbeg, nlen = spans(names)
+        text, n = VP(), U64()
+        _check(self.L.rbg_align_sam(self.h, sbuf, _p(sbeg), _p(slen), qbuf, _p(qbeg), nbuf, _p(nbeg), _p(nlen), len(seqs), min_length, max_hits,
+                                    SAM_SECONDARY if secondary else 0, C.byref(text), C.byref(n)), "rbg_align_sam")
+        try:
+            _check(self.L.rbg_wait_text(self.h, text), "rbg_wait_text")
+            return C.string_at(text, n.value) if n.value else b""
+        finally:
+            self.L.rbg_release_text(self.h, text)
+
+    def sam_header(self, pg=None):
+        """rbg_sam_header: @HD, one @SQ per document in sorted-start order, then `pg` (bytes, appended as given)"""
+        text, n = VP(), U64()
+        _check(self.L.rbg_sam_header(self.h, pg, C.byref(text), C.byref(n)), "rbg_sam_header")
+        try:
+            return C.string_at(text, n.value)
+        finally:
+            self.L.rbg_free_buffer(text)
 
     def markers_report(self, seqs, off, params, first_fwd=None):
         """rbg_markers_report: what rb_markers prints for a batch of RAW reads, as records -> (seed_off[N+1], records (REPORT_SEED), mk);

@@ -32,6 +32,13 @@ struct BatchView {
     size_t name_len(size_t i) const { return w->recs.name_len[w0 + i]; }
     const char *seq(size_t i) const { return w->base + w->recs.seq_begin[w0 + i]; }
     uint64_t seq_len(size_t i) const { return w->recs.seq_len[w0 + i]; }
+    // the quality string of record i (seq_len(i) bytes), or nullptr for a FASTA record
+    const char *qual(size_t i) const { const uint64_t q = w->recs.qual_begin[w0 + i]; return q == RecordSpans::kNoQual ? nullptr : w->base + q; }
+    bool all_have_qual() const {
+        for (size_t i = 0; i < n; ++i)
+            if (w->recs.qual_begin[w0 + i] == RecordSpans::kNoQual) return false;
+        return true;
+    }
 };
 
 // the raw reads of a batch back to back: read i is seqs[off[i] .. off[i + 1])

@@ -27,14 +27,23 @@ struct RecordSpans {              // records of one buffer, in input order
     std::vector<uint64_t> name_begin, seq_begin;   // offsets from the buffer's first byte (seq: modulo 2^64 when in the arena)
     std::vector<uint32_t> name_len, seq_len;
     std::vector<std::string> arena;                // rebuilt sequences (kept alive with the spans)
+    // the quality string of every record (its length is seq_len): an offset like seq_begin, or kNoQual for a FASTA record.  A quality string of
+    // several lines (or with a trailing '\r') is rebuilt in qual_arena -- an arena of its OWN: finish_arena pairs the entries of each arena with
+    // their pending records by order, so rebuilt sequences and rebuilt qualities must not share one
+    std::vector<uint64_t> qual_begin;
+    std::vector<std::string> qual_arena;
+    static constexpr uint64_t kPending = ~uint64_t(0);       // in an arena, not placed yet (finish_arena)
+    static constexpr uint64_t kNoQual = ~uint64_t(0) - 1;    // (no arena string lies two bytes below the buffer: heap and mapping do not wrap)
     size_t size() const { return seq_begin.size(); }
-    void clear() { name_begin.clear(); seq_begin.clear(); name_len.clear(); seq_len.clear(); arena.clear(); }
+    void clear() { name_begin.clear(); seq_begin.clear(); name_len.clear(); seq_len.clear(); arena.clear(); qual_begin.clear(); qual_arena.clear(); }
     void append(RecordSpans &&o) {
         name_begin.insert(name_begin.end(), o.name_begin.begin(), o.name_begin.end());
         seq_begin.insert(seq_begin.end(), o.seq_begin.begin(), o.seq_begin.end());
         name_len.insert(name_len.end(), o.name_len.begin(), o.name_len.end());
         seq_len.insert(seq_len.end(), o.seq_len.begin(), o.seq_len.end());
         for (auto &s : o.arena) arena.push_back(std::move(s));   // (std::string moves keep heap buffers in place; short ones are re-pointed below)
+        qual_begin.insert(qual_begin.end(), o.qual_begin.begin(), o.qual_begin.end());
+        for (auto &s : o.qual_arena) qual_arena.push_back(std::move(s));
     }
 };
 
@@ -112,7 +121,8 @@ inline int scan_records(const char *buf, uint64_t pos, uint64_t end, bool final,
         // -- sequence lines until a line that starts with '>', '+' or '@' (kseq.h:195-199)
         uint64_t seq_b = pos, seq_l = 0;
         bool contiguous = true;    // the sequence is exactly buf[seq_b, seq_b + seq_l)
-        std::string rebuilt;
+        std::string rebuilt, qual_rebuilt;
+        uint64_t qual_b = 0, qual_l = 0, qlines = 0;   // the quality string: buf[qual_b, qual_b + qual_l) when it is one line
         int c = -1;
         uint64_t nlines = 0;
         while (true) {
@@ -152,6 +162,8 @@ inline int scan_records(const char *buf, uint64_t pos, uint64_t end, bool final,
             }
             pos = static_cast<uint64_t>(e - buf) + 1;
             uint64_t qlen = 0;
+            qlines = 0;
+            qual_rebuilt.clear();
             bool first = true;
             while (first || qlen < final_len) {   // at least one line (the call sits in kseq's loop condition)
                 first = false;
@@ -163,7 +175,15 @@ inline int scan_records(const char *buf, uint64_t pos, uint64_t end, bool final,
                 if (!qe && !final) return need_more(rec_at, rec_state);
                 const uint64_t le = qe ? static_cast<uint64_t>(qe - buf) : end;
                 qlen += le - pos;
-                if (qlen > 1 && le > pos && buf[le - 1] == '\r') --qlen;   // the '\r' rule, on the accumulated quality string
+                bool cr = false;
+                if (qlen > 1 && le > pos && buf[le - 1] == '\r') { --qlen; cr = true; }   // the '\r' rule, on the accumulated quality string
+                // where the quality bytes lie: one line is a span of the buffer, more lines are rebuilt
+                if (qlines == 0) { qual_b = pos; qual_l = le - pos - (cr ? 1 : 0); }
+                else {
+                    if (qlines == 1) qual_rebuilt.assign(buf + qual_b, qual_l);
+                    qual_rebuilt.append(buf + pos, le - pos - (cr ? 1 : 0));
+                }
+                ++qlines;
                 pos = qe ? le + 1 : end;
             }
             if (qlen != final_len) {
@@ -183,6 +203,12 @@ inline int scan_records(const char *buf, uint64_t pos, uint64_t end, bool final,
             out.seq_begin.push_back(~uint64_t(0));                 // fixed up by finish_arena()
             out.seq_len.push_back(static_cast<uint32_t>(out.arena.back().size()));
         }
+        if (c != '+') out.qual_begin.push_back(RecordSpans::kNoQual);
+        else if (qlines <= 1) out.qual_begin.push_back(qual_b);       // (an empty quality string of an empty read: any offset, length 0)
+        else {
+            out.qual_arena.push_back(std::move(qual_rebuilt));
+            out.qual_begin.push_back(RecordSpans::kPending);
+        }
         st = after;
         if (c < 0) {   // the stream ended inside / right after this record
             *resume = end;
@@ -198,6 +224,10 @@ inline void finish_arena(const char *buf, RecordSpans &r) {
     for (size_t i = 0; i < r.size(); ++i)
         if (r.seq_begin[i] == ~uint64_t(0))
             r.seq_begin[i] = static_cast<uint64_t>(reinterpret_cast<uintptr_t>(r.arena[a++].data()) - reinterpret_cast<uintptr_t>(buf));
+    size_t q = 0;
+    for (size_t i = 0; i < r.qual_begin.size(); ++i)
+        if (r.qual_begin[i] == RecordSpans::kPending)
+            r.qual_begin[i] = static_cast<uint64_t>(reinterpret_cast<uintptr_t>(r.qual_arena[q++].data()) - reinterpret_cast<uintptr_t>(buf));
 }
 
 // a guessed record boundary at or after `from`: a line start that looks like a FASTQ or FASTA header

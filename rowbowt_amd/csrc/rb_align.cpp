@@ -7,6 +7,9 @@
 //   -s: "\tlocs: " { "<l>/<doc>:<off> " } "\n"
 //   -m: "\tmarkers: " ( "no markers (consider building the marker array with a larger window size)"
 //                      | { "<pos>/<allele> " } ) "\n"
+// --format sam (not the reference's: its -s/--sam keeps its meaning and output) writes SAM instead: the header once (rbg_sam_header), then per batch the
+// lines rbg_align_sam makes on the device -- both strands, the longer greedy seed of --min-seed-length located, soft-clipped, --max-hits secondary lines
+// with --secondary.  QUAL is "*" for a batch in which any record has no quality string (FASTA).
 // stderr keeps the reference's shape ("will load SA and DA", "<load_s> <query_s>").
 // Input parsing follows kseq.h semantics (name = header up to the first whitespace; FASTA or FASTQ,
 // plain or gzip; kseq_read's -2 "truncated quality string" error is reported the same way).
@@ -43,6 +46,9 @@ using rbg_cli::InputSource;
 struct RbAlignArgs {  // rb_align.cpp:17-24
     std::string inpre, fastq_fname, outpre;
     int sam = 0, markers = 0;
+    bool format_sam = false;                       // --format sam
+    uint64_t min_seed_length = 20, max_hits = 16;  // --min-seed-length, --max-hits
+    bool secondary = false;                        // --secondary
     int device = 0;
     int gpus = 1;     // replicas: devices device .. device + gpus - 1; every batch is sharded over them
     std::vector<int> devices;  // --devices a,b,...: the replicas' devices, in shard order (overrides --gpu/--gpus)
@@ -59,6 +65,10 @@ void print_help() {  // rb_align.cpp:26-35
     fprintf(stderr, "    --output_prefix/-o <basename>    output prefix\n");
     fprintf(stderr, "    --markers/-m                     print markers\n");
     fprintf(stderr, "    --sam/-s                         print locations\n");
+    fprintf(stderr, "    --format sam                     write SAM records (both strands, the longest greedy seed, soft-clipped) instead of the report\n");
+    fprintf(stderr, "    --min-seed-length <n>            --format sam: shortest seed that maps a read (default 20)\n");
+    fprintf(stderr, "    --max-hits <n>                   --format sam --secondary: lines per read, at most (default 16)\n");
+    fprintf(stderr, "    --secondary                      --format sam: also one line per further location\n");
     fprintf(stderr, "    --gpu <n>                        HIP device ordinal (default 0)\n");
     fprintf(stderr, "    --gpus <G>                       replicate the index on G devices (from --gpu on) and shard every batch over them\n");
     fprintf(stderr, "    --devices <a,b,...>              the same with an explicit device list\n");
@@ -80,6 +90,10 @@ RbAlignArgs parse_args(int argc, char **argv) {  // rb_align.cpp:37-84
                                            {"batch", required_argument, 0, 'b'},
                                            {"threads", required_argument, 0, 't'},
                                            {"window-mb", required_argument, 0, 'W'},
+                                           {"format", required_argument, 0, 'F'},
+                                           {"min-seed-length", required_argument, 0, 'L'},
+                                           {"max-hits", required_argument, 0, 'H'},
+                                           {"secondary", no_argument, 0, 'S'},
                                            {0, 0, 0, 0}};
     int c, long_index = 0;
     while ((c = getopt_long(argc, argv, "o:smh", long_options, &long_index)) != -1) {
@@ -100,6 +114,13 @@ RbAlignArgs parse_args(int argc, char **argv) {  // rb_align.cpp:37-84
             case 'b': args.batch = strtoull(optarg, nullptr, 10); args.batch_given = true; break;
             case 't': args.threads = atoi(optarg); break;
             case 'W': args.window_mb = strtoull(optarg, nullptr, 10); break;
+            case 'F':
+                if (std::strcmp(optarg, "sam") != 0) { fprintf(stderr, "--format: only \"sam\" is known\n"); exit(1); }
+                args.format_sam = true;
+                break;
+            case 'L': args.min_seed_length = strtoull(optarg, nullptr, 10); break;
+            case 'H': args.max_hits = strtoull(optarg, nullptr, 10); break;
+            case 'S': args.secondary = true; break;
             default: print_help(); exit(1);
         }
     }
@@ -112,6 +133,8 @@ RbAlignArgs parse_args(int argc, char **argv) {  // rb_align.cpp:37-84
     if (args.outpre.empty()) args.outpre = args.inpre;
     if (args.batch == 0) args.batch = 1;
     if (!args.batch_given && args.sam) args.batch = 1u << 19;
+    if (args.format_sam && (args.sam || args.markers)) { fprintf(stderr, "--format sam goes without -s and -m\n"); exit(1); }
+    if (args.format_sam && args.min_seed_length == 0) { fprintf(stderr, "--min-seed-length must be at least 1\n"); exit(1); }
     if (args.gpus < 1) args.gpus = 1;
     if (args.threads < 1) args.threads = 1;
     if (args.window_mb < 1) args.window_mb = 1;
@@ -150,7 +173,7 @@ struct ShardError {
 // than a library call per batch does (measured: 7.4e7 reads/s against 2.8e7 through rbg_align_text with k = NULL).
 bool device_text(const RbAlignArgs &args) {
     static const bool off = [] { const char *e = std::getenv("RB_ALIGN_HOST_TEXT"); return e && e[0] == '1'; }();
-    return args.sam && !off;
+    return args.format_sam || (args.sam && !off);
 }
 
 ShardError query_shard(rbg_index *ix, const RbAlignArgs &args, const BatchView &b, uint64_t begin, uint64_t end, BatchResult &r) {
@@ -164,6 +187,15 @@ ShardError query_shard(rbg_index *ix, const RbAlignArgs &args, const BatchView &
         const uint64_t *sb = b.w->recs.seq_begin.data() + b.w0 + begin;
         const uint32_t *sl = b.w->recs.seq_len.data() + b.w0 + begin;
         int rc;
+        if (args.format_sam) {   // the whole of it in one call: the finished lines come back like -s's text
+            const bool quals = b.all_have_qual();   // (of the whole batch, so that the text does not depend on how it is sharded)
+            r.text_owner = ix;
+            if ((rc = rbg_align_sam(ix, b.w->base, sb, sl, quals ? b.w->base : nullptr, quals ? b.w->recs.qual_begin.data() + b.w0 + begin : nullptr, b.w->base,
+                                    b.w->recs.name_begin.data() + b.w0 + begin, b.w->recs.name_len.data() + b.w0 + begin, N, args.min_seed_length, args.max_hits,
+                                    args.secondary ? RBG_SAM_SECONDARY : 0u, &r.text, &r.text_len)))
+                return {rc, "rbg_align_sam"};
+            return {};
+        }
         r.lo.resize(N); r.hi.resize(N);
         if (args.sam) {  // rb_get_range(sa=true), rb_align.cpp:99-103
             r.k.resize(N);
@@ -359,7 +391,7 @@ int main(int argc, char **argv) {
     const RbAlignArgs args = parse_args(argc, argv);
     auto start = std::chrono::high_resolution_clock::now();
     rbwt::LoadRbwtFlag flag = rbwt::LoadRbwtFlag::NONE;  // load_rbwt, rb_align.cpp:147-160
-    if (args.sam) {
+    if (args.sam || args.format_sam) {
         std::cerr << "will load SA and DA" << std::endl;
         flag = flag | rbwt::LoadRbwtFlag::SA | rbwt::LoadRbwtFlag::DL;
     }
@@ -417,6 +449,10 @@ int main(int argc, char **argv) {
         // back and the next batch's text being ready: the process-to-process bimodality of `rb_align -s -m` in round 3 (2.0e7 against
         // 3.4e7 reads/s) -- profiles/r04_numa_probe.txt lists the pinned allocations of 32 processes beside their rates.
         for (rbg_index *r : once) (void)rbg_reserve_text(r, (args.batch / reps.size() + 1) * 1100 + (size_t(1) << 20), 4 * S);
+    }
+    if (args.format_sam) {   // the header goes out once, ahead of every batch's lines
+        const std::string header = rb.sam_header("@PG\tID:rb_align\tPN:rb_align\n");
+        fwrite(header.data(), 1, header.size(), stdout);
     }
     start = std::chrono::high_resolution_clock::now();
     // the shared loop (cli_pipeline.hpp) in GPU batches of --batch reads: batch j + 1 is queried (library calls: packing, GPU,

@@ -527,6 +527,34 @@ void text_total_ptrs(void *ws, uint64_t E, const uint64_t **last_at, const uint3
 int launch_text_fill(const uint64_t *lo, const uint64_t *hi, const uint64_t *loc_off, const uint64_t *locs, uint64_t N, uint64_t E, const char *names,
                      const uint32_t *name_off, const uint64_t *doc_start, const char *doc_names, const uint32_t *doc_name_off, uint64_t ndocs,
                      uint64_t text_size, bool with_locs, const uint64_t *mk_off, const uint64_t *mk, void *ws, uint64_t total, char *text, void *stream);
+// SAM lines on the device (k_sam.hip; rbg_align_sam; the rules: rbg_sam.hpp).  launch_sam_strands: N reads (off[0] == 0, total = off[N]) -> the 2N-sequence batch
+// `out` (16-byte aligned, ((2 total + 15) & ~15) + 16 bytes) and off2[2N + 1], sequence 2i + 1 the reverse complement of read i with N kept.  launch_sam_pick: the
+// 2N answers of launch_greedy_seed -> per read the longer seed's range, toehold, [a, b) and strand (a tie: forward; none: {1, 0}), its number of lines
+// (occurrences up to max_hits >= 1; 1 when unmapped) in nlines[N + 1] and their exclusive sum line_off[N + 1]; counters[0] += 2N.  Then plan / fill as in
+// k_text.hip, one element per line (E = line_off[N] >= 1).  cap: the most workgroups of a launch, 0 = the kernels' default.
+struct SamBatch {
+    uint64_t N, E;
+    const uint64_t *lo, *hi, *a, *b;               // [N], launch_sam_pick's
+    const uint8_t *rev;                            // [N]
+    const uint64_t *line_off, *loc_off, *locs;     // [N + 1]; [N + 1] and the locations of launch_locate_plan / _fill over (lo, hi) with the same max_hits
+    const char *seqs, *quals;                      // the reads as given; quals nullable
+    const uint64_t *roff;                          // [N + 1]
+    const char *names;
+    const uint32_t *name_off;                      // [N + 1]
+    const uint64_t *doc_start;                     // the document table as launch_text_plan takes it
+    const char *doc_names;
+    const uint32_t *doc_name_off;
+    uint64_t ndocs, text_size;
+};
+int launch_sam_strands(const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t total, uint8_t *out, uint64_t *off2, uint32_t cap, void *stream);
+size_t sam_pick_tmp_bytes(uint64_t N);
+int launch_sam_pick(const uint64_t *lo2, const uint64_t *hi2, const uint64_t *qs2, const uint64_t *qe2, const uint64_t *ss2, uint64_t N, uint64_t max_hits,
+                    uint64_t *lo, uint64_t *hi, uint64_t *k, uint64_t *a, uint64_t *b, uint8_t *rev, uint64_t *nlines, uint64_t *line_off,
+                    unsigned long long *counters, void *tmp, size_t tmp_bytes, uint32_t cap, void *stream);
+size_t sam_ws_bytes(uint64_t E);
+int launch_sam_plan(const SamBatch &B, void *ws, size_t ws_bytes, unsigned int *d_bad, uint32_t cap, void *stream);
+void sam_total_ptrs(void *ws, uint64_t E, const uint64_t **last_at, const uint64_t **last_len);
+int launch_sam_fill(const SamBatch &B, void *ws, uint64_t total, char *text, uint32_t cap, void *stream);
 // run-indexed layout from run lists already on the device (k_build.hip): the tables' directories, 8-byte samples packed to 6
 int launch_run_dirs(uint32_t pos_bytes, const void *ent, const uint64_t *first, const uint64_t *nruns, const uint64_t *doff, const uint32_t *dshift,
                     uint32_t T, uint64_t total, uint32_t *dir, void *stream);

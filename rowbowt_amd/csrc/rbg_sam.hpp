@@ -1,0 +1,161 @@
+// rbg_sam.hpp -- the rules of rbg_align_sam's SAM lines and of rbg_sam_header's text, stated once for host and device (k_sam.hip formats lines with
+// sam_put_line, capi/sam.ipp builds the header with sam_header_text; a host compiler takes this file alone: tests/cpp/sam_host_check.cpp).
+//
+// COMPLEMENT.  ACGTacgt -> TGCAtgca, every other byte is itself.  This is not seq_ntoa_table (k_report.hip): an N stays N and ends a seed.
+//
+// CIGAR.  A read of m bytes whose seed is [a, b) in the searched orientation: [a "S"] (b - a) "M" [(m - b) "S"], zero-length operations left out.
+//
+// LINES (fields separated by tabs, "\n" at the end):
+//   mapped     QNAME FLAG RNAME POS 255 CIGAR * 0 0 SEQ QUAL NH:i:<occ> HI:i:<j>     FLAG = (reverse ? 16 : 0) | (j > 1 ? 256 : 0); j > 1: SEQ and QUAL are "*"
+//   unmapped   QNAME 4 * 0 0 * * 0 0 SEQ QUAL                                         the read as given; an empty read has SEQ "*" and QUAL "*"
+// SEQ of a reverse-strand primary line is the complement of the read's bytes taken backwards, its QUAL the quality bytes taken backwards; QUAL is "*"
+// when the call has no qualities.  POS is 1 + the offset of the seed's own text position in its document (nothing is subtracted for the clipped
+// bases), and the document is that of this first aligned base: a seed that runs over a document boundary is NOT detected.
+//
+// HEADER.  "@HD\tVN:1.6\tSO:unsorted\n", then per document in sorted-start order "@SQ\tSN:<name>\tLN:<len>\n" with len = the next sorted start - this one,
+// and n - start for the last (n: the index's text length; 0 if the start lies beyond it).  That is an UPPER BOUND of the sequence's length: it includes
+// the separators between documents and the terminator.  Names pair with sorted starts by position, as rbg_doc_table lists them.
+#ifndef RBG_SAM_HPP
+#define RBG_SAM_HPP
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define RBG_SAM_HD __host__ __device__ __forceinline__
+#else
+#define RBG_SAM_HD inline
+#endif
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+namespace rbg {
+
+constexpr uint32_t kSamFlagReverse = 16, kSamFlagSecondary = 256, kSamFlagUnmapped = 4;
+
+RBG_SAM_HD uint8_t sam_comp(const uint8_t c) {
+    switch (c) {
+        case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A';
+        case 'a': return 't'; case 'c': return 'g'; case 'g': return 'c'; case 't': return 'a';
+        default: return c;
+    }
+}
+
+// (the same digits as rbg_text_dev.hpp's dec_len / put_dec; restated so that a host compiler needs this header only)
+RBG_SAM_HD uint32_t sam_dec_len(uint64_t v) {
+    uint32_t n = 1;
+    while (v >= 10) { v /= 10; ++n; }
+    return n;
+}
+template <typename Ptr>
+RBG_SAM_HD uint32_t sam_put_dec(Ptr p, uint64_t v) {
+    const uint32_t n = sam_dec_len(v);
+    for (uint32_t j = n; j-- > 0;) {
+        const uint64_t q = v / 10;
+        p[j] = static_cast<char>('0' + static_cast<uint32_t>(v - q * 10));
+        v = q;
+    }
+    return n;
+}
+
+RBG_SAM_HD uint32_t sam_cigar_len(const uint64_t m, const uint64_t a, const uint64_t b) {
+    return (a ? sam_dec_len(a) + 1 : 0) + sam_dec_len(b - a) + 1 + (m > b ? sam_dec_len(m - b) + 1 : 0);
+}
+template <typename Ptr>
+RBG_SAM_HD uint32_t sam_put_cigar(Ptr p, const uint64_t m, const uint64_t a, const uint64_t b) {
+    uint32_t n = 0;
+    if (a) { n += sam_put_dec(p + n, a); p[n++] = 'S'; }
+    n += sam_put_dec(p + n, b - a);
+    p[n++] = 'M';
+    if (m > b) { n += sam_put_dec(p + n, m - b); p[n++] = 'S'; }
+    return n;
+}
+
+// one line, by its parts
+struct SamLine {
+    uint64_t name_len;
+    bool mapped;
+    bool reverse;      // mapped: the seed was found in the reverse complement
+    uint64_t hit;      // mapped: 1 = the primary line, j > 1 = the secondary line of location j
+    uint64_t occ;      // mapped: hi - lo + 1
+    uint64_t rname_len, pos;   // mapped: the document's name, 1 + offset
+    uint64_t m, a, b;  // read length; mapped: the seed [a, b) in the searched orientation
+    bool has_qual;     // the call has quality bytes
+};
+RBG_SAM_HD uint32_t sam_flag(const SamLine &L) {
+    return L.mapped ? (L.reverse ? kSamFlagReverse : 0u) | (L.hit > 1 ? kSamFlagSecondary : 0u) : kSamFlagUnmapped;
+}
+RBG_SAM_HD uint64_t sam_seq_len(const SamLine &L) { return (L.mapped && L.hit > 1) || L.m == 0 ? 1 : L.m; }
+RBG_SAM_HD uint64_t sam_qual_len(const SamLine &L) { return (L.mapped && L.hit > 1) || L.m == 0 || !L.has_qual ? 1 : L.m; }
+constexpr uint32_t kSamUnmappedMid = 17;   // "\t4\t*\t0\t0\t*\t*\t0\t0\t"
+RBG_SAM_HD uint64_t sam_line_len(const SamLine &L) {
+    if (!L.mapped) return L.name_len + kSamUnmappedMid + sam_seq_len(L) + 1 + sam_qual_len(L) + 1;
+    return L.name_len + 1 + sam_dec_len(sam_flag(L)) + 1 + L.rname_len + 1 + sam_dec_len(L.pos) + 5 /* \t255\t */ + sam_cigar_len(L.m, L.a, L.b) +
+           7 /* \t*\t0\t0\t */ + sam_seq_len(L) + 1 + sam_qual_len(L) + 6 /* \tNH:i: */ + sam_dec_len(L.occ) + 6 /* \tHI:i: */ + sam_dec_len(L.hit) + 1;
+}
+
+template <typename Ptr>
+RBG_SAM_HD Ptr sam_put_lit(Ptr p, const char *s, const uint32_t n) {
+    for (uint32_t j = 0; j < n; ++j) p[j] = s[j];
+    return p + n;
+}
+// SEQ or QUAL: n = 1 and "*", or the m bytes of src, forwards or backwards, complemented or not
+template <typename Ptr>
+RBG_SAM_HD Ptr sam_put_bases(Ptr p, const char *src, const uint64_t m, const bool star, const bool backwards, const bool complement) {
+    if (star) { p[0] = '*'; return p + 1; }
+    for (uint64_t j = 0; j < m; ++j) {
+        const uint8_t c = static_cast<uint8_t>(src[backwards ? m - 1 - j : j]);
+        p[j] = static_cast<char>(complement ? sam_comp(c) : c);
+    }
+    return p + m;
+}
+// the sam_line_len(L) bytes of the line at p; seq / qual: the read's ORIGINAL bytes (qual unused without has_qual)
+template <typename Ptr>
+RBG_SAM_HD void sam_put_line(Ptr p, const SamLine &L, const char *name, const char *rname, const char *seq, const char *qual) {
+    for (uint64_t j = 0; j < L.name_len; ++j) p[j] = name[j];
+    p += L.name_len;
+    const bool star = (L.mapped && L.hit > 1) || L.m == 0;
+    if (!L.mapped) {
+        p = sam_put_lit(p, "\t4\t*\t0\t0\t*\t*\t0\t0\t", kSamUnmappedMid);
+        p = sam_put_bases(p, seq, L.m, star, false, false);
+        *p = '\t'; p += 1;
+        p = sam_put_bases(p, qual, L.m, star || !L.has_qual, false, false);
+        *p = '\n';
+        return;
+    }
+    *p = '\t'; p += 1;
+    p += sam_put_dec(p, sam_flag(L));
+    *p = '\t'; p += 1;
+    for (uint64_t j = 0; j < L.rname_len; ++j) p[j] = rname[j];
+    p += L.rname_len;
+    *p = '\t'; p += 1;
+    p += sam_put_dec(p, L.pos);
+    p = sam_put_lit(p, "\t255\t", 5);
+    p += sam_put_cigar(p, L.m, L.a, L.b);
+    p = sam_put_lit(p, "\t*\t0\t0\t", 7);
+    p = sam_put_bases(p, seq, L.m, star, L.reverse, L.reverse);
+    *p = '\t'; p += 1;
+    p = sam_put_bases(p, qual, L.m, star || !L.has_qual, L.reverse, false);
+    p = sam_put_lit(p, "\tNH:i:", 6);
+    p += sam_put_dec(p, L.occ);
+    p = sam_put_lit(p, "\tHI:i:", 6);
+    p += sam_put_dec(p, L.hit);
+    *p = '\n';
+}
+
+// the header's text (host).  sorted[ndocs]: the documents' starts ascending, names[j] the name listed with sorted[j]; n: the text length of the index
+inline std::string sam_header_text(const std::vector<std::string> &names, const std::vector<uint64_t> &sorted, const uint64_t n, const char *pg_line) {
+    std::string s = "@HD\tVN:1.6\tSO:unsorted\n";
+    for (size_t j = 0; j < sorted.size(); ++j) {
+        const uint64_t end = j + 1 < sorted.size() ? sorted[j + 1] : n;
+        s += "@SQ\tSN:";
+        s += names[j];
+        s += "\tLN:";
+        s += std::to_string(end > sorted[j] ? end - sorted[j] : 0);
+        s += '\n';
+    }
+    if (pg_line) s += pg_line;
+    return s;
+}
+
+}  // namespace rbg
+#endif

@@ -207,6 +207,42 @@ class RowBowt {
         return std::make_pair(std::string(name), off);
     }
 
+    // SAM lines of a batch of raw reads (rbg_align_sam: both strands searched, the longer greedy seed located, soft-clipped records written on the device)
+    // as one string; quals: a quality string per read of the read's length, or empty for QUAL "*"; names: one per read
+    std::string align_sam(const std::vector<std::string> &seqs, const std::vector<std::string> &quals, const std::vector<std::string> &names,
+                          uint64_t min_length = 20, uint64_t max_hits = 16, bool secondary = false) const {
+        const uint64_t N = seqs.size();
+        if (names.size() != N || (!quals.empty() && quals.size() != N)) detail::die("align_sam: a name (and a quality string, if any) per read", RBG_EARG);
+        std::string sblob, qblob, nblob;
+        std::vector<uint64_t> sbeg(N), nbeg(N);
+        std::vector<uint32_t> slen(N), nlen(N);
+        for (uint64_t i = 0; i < N; ++i) {
+            if (!quals.empty() && quals[i].size() != seqs[i].size()) detail::die("align_sam: a quality string of the read's length", RBG_EARG);
+            sbeg[i] = sblob.size(); slen[i] = static_cast<uint32_t>(seqs[i].size()); sblob += seqs[i];
+            if (!quals.empty()) qblob += quals[i];
+            nbeg[i] = nblob.size(); nlen[i] = static_cast<uint32_t>(names[i].size()); nblob += names[i];
+        }
+        const char *text = nullptr;
+        uint64_t n = 0;
+        detail::check(rbg_align_sam(ix_.get(), sblob.data(), sbeg.data(), slen.data(), quals.empty() ? nullptr : qblob.data(), sbeg.data(), nblob.data(),
+                                    nbeg.data(), nlen.data(), N, min_length, max_hits, secondary ? RBG_SAM_SECONDARY : 0u, &text, &n), "rbg_align_sam");
+        const int rc = rbg_wait_text(ix_.get(), text);
+        std::string out = rc == RBG_OK && n ? std::string(text, n) : std::string();
+        (void)rbg_release_text(ix_.get(), text);
+        detail::check(rc, "rbg_wait_text");
+        return out;
+    }
+    std::string align_sam(const std::vector<std::string> &seqs, const std::vector<std::string> &names) const { return align_sam(seqs, {}, names); }
+    // the header that goes with those lines (rbg_sam_header): @HD, one @SQ per document, then pg_line as given
+    std::string sam_header(const std::string &pg_line = std::string()) const {
+        char *text = nullptr;
+        uint64_t n = 0;
+        detail::check(rbg_sam_header(ix_.get(), pg_line.empty() ? nullptr : pg_line.c_str(), &text, &n), "rbg_sam_header");
+        std::string out(text, n);
+        rbg_free_buffer(text);
+        return out;
+    }
+
     // resolve_offset for many positions that are in HOST memory: one fetch of the table (rbg_doc_table) and the rule of doclist.hpp:46-50, :77-79 (rbg_docdir.hpp) per position,
     // instead of a call through the ABI each.  doc[i] = the document's index into names() of rbg_doc_table, RBG_DOC_NONE where position i has none (the single
     // call exits there; the offset is then the position itself).  Positions that are on the device go through rbg_resolve_offsets_dev and never come here.
