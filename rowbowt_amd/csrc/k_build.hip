@@ -1,5 +1,6 @@
 // k_build.hip -- load-time kernels: first-level slot tables and dense overflow tables from the uploaded run lists, the ftab.
 #include "rbg_device.hpp"
+#include "rbg_launch.hpp"
 
 namespace rbg {
 
@@ -452,39 +453,37 @@ int launch_run_dirs2(const void *ent, const uint64_t *first, const uint64_t *nru
 }
 int launch_fold_F(uint32_t pos_bytes, void *ent, const uint64_t *first, const uint64_t *F, uint32_t T, uint64_t total, void *stream) {
     if (total == 0 || T == 0) return 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (pos_bytes == 4) hipLaunchKernelGGL((k_fold_F<uint32_t>), dim3(grid_of(total)), dim3(256), 0, st, static_cast<RunEnt<uint32_t> *>(ent), first, F, T, total);
-    else hipLaunchKernelGGL((k_fold_F<uint64_t>), dim3(grid_of(total)), dim3(256), 0, st, static_cast<RunEnt<uint64_t> *>(ent), first, F, T, total);
-    return static_cast<int>(hipGetLastError());
+    return with_pos(pos_bytes, [&](auto p) {
+        using P = pos_t<decltype(p)>;
+        return launch_grid(k_fold_F<P>, dim3(grid_of(total)), dim3(256), 0, stream, static_cast<RunEnt<P> *>(ent), first, F, T, total);
+    });
 }
 int launch_run_recs2(uint32_t pos_bytes, const void *ent, const uint64_t *first, const uint64_t *nruns, const uint64_t *roff, const uint32_t *rshift, uint32_t T, uint64_t total,
                      void *recs, unsigned long long *overflow, void *stream) {
     if (!total) return 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (pos_bytes == 4) hipLaunchKernelGGL((k_run_recs2<uint32_t>), dim3(grid_of(total)), dim3(256), 0, st, static_cast<const RunEnt<uint32_t> *>(ent), first, nruns, roff, rshift, T, total,
-                                           static_cast<RunRec2 *>(recs), overflow);
-    else hipLaunchKernelGGL((k_run_recs2<uint64_t>), dim3(grid_of(total)), dim3(256), 0, st, static_cast<const RunEnt<uint64_t> *>(ent), first, nruns, roff, rshift, T, total,
-                            static_cast<RunRec2 *>(recs), overflow);
-    return static_cast<int>(hipGetLastError());
+    return with_pos(pos_bytes, [&](auto p) {
+        using P = pos_t<decltype(p)>;
+        return launch_grid(k_run_recs2<P>, dim3(grid_of(total)), dim3(256), 0, stream, static_cast<const RunEnt<P> *>(ent), first, nruns, roff, rshift, T, total,
+                           static_cast<RunRec2 *>(recs), overflow);
+    });
 }
 int launch_phi_dir(uint32_t pos_bytes, const void *ent, uint64_t m, uint32_t shift, uint64_t nb, uint32_t *dir, uint32_t ss, uint64_t *super, void *stream) {
     if (!nb) return 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (pos_bytes == 4) hipLaunchKernelGGL(k_phi_dir<uint32_t>, dim3(grid_of(nb)), dim3(256), 0, st, ent, m, shift, nb, dir, 0u, static_cast<uint64_t *>(nullptr));
-    else hipLaunchKernelGGL(k_phi_dir<uint64_t>, dim3(grid_of(nb)), dim3(256), 0, st, ent, m, shift, nb, dir, ss, super);
-    return static_cast<int>(hipGetLastError());
+    return with_pos(pos_bytes, [&](auto p) {   // (the super-directory: 8-byte positions only)
+        constexpr bool wide = sizeof(pos_t<decltype(p)>) == 8;
+        return launch_grid(k_phi_dir<pos_t<decltype(p)>>, dim3(grid_of(nb)), dim3(256), 0, stream, ent, m, shift, nb, dir, wide ? ss : 0u,
+                           wide ? super : static_cast<uint64_t *>(nullptr));
+    });
 }
 
 int launch_run_dirs(uint32_t pos_bytes, const void *ent, const uint64_t *first, const uint64_t *nruns, const uint64_t *doff, const uint32_t *dshift,
                     uint32_t T, uint64_t total, uint32_t *dir, void *stream) {
     if (!total) return 0;
     const int grid = static_cast<int>(std::min<uint64_t>((total + 255) / 256, 256ull * 64));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (pos_bytes == 4)
-        hipLaunchKernelGGL((k_run_dirs<uint32_t>), dim3(grid), dim3(256), 0, st, static_cast<const RunEnt<uint32_t> *>(ent), first, nruns, doff, dshift, T, total, dir);
-    else
-        hipLaunchKernelGGL((k_run_dirs<uint64_t>), dim3(grid), dim3(256), 0, st, static_cast<const RunEnt<uint64_t> *>(ent), first, nruns, doff, dshift, T, total, dir);
-    return static_cast<int>(hipGetLastError());
+    return with_pos(pos_bytes, [&](auto p) {
+        using P = pos_t<decltype(p)>;
+        return launch_grid(k_run_dirs<P>, dim3(grid), dim3(256), 0, stream, static_cast<const RunEnt<P> *>(ent), first, nruns, doff, dshift, T, total, dir);
+    });
 }
 int launch_pack_samp48(const uint64_t *in, uint64_t n, void *out, void *stream) {
     if (!n) return 0;
@@ -499,14 +498,11 @@ int launch_build_rank_slots(uint32_t pos_bytes, const void *ent, uint64_t nruns,
     const uint64_t nb = (n >> shift) + 2;
     const uint64_t groups = (nb + kBuildGroup - 1) / kBuildGroup;
     const int grid = static_cast<int>(std::min<uint64_t>((groups + 255) / 256, 256ull * 64));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (pos_bytes == 4)
-        hipLaunchKernelGGL((k_build_rank_slots<uint32_t>), dim3(grid), dim3(256), 0, st, static_cast<const RunEnt<uint32_t> *>(ent), nruns, n, shift,
+    return with_pos(pos_bytes, [&](auto p) {
+        using P = pos_t<decltype(p)>;
+        return launch_grid(k_build_rank_slots<P>, dim3(grid), dim3(256), 0, stream, static_cast<const RunEnt<P> *>(ent), nruns, n, shift,
                            static_cast<RankSlot *>(slots), ord, overflow, dense_cursor);
-    else
-        hipLaunchKernelGGL((k_build_rank_slots<uint64_t>), dim3(grid), dim3(256), 0, st, static_cast<const RunEnt<uint64_t> *>(ent), nruns, n, shift,
-                           static_cast<RankSlot *>(slots), ord, overflow, dense_cursor);
-    return static_cast<int>(hipGetLastError());
+    });
 }
 
 int launch_fill_dense(uint32_t pos_bytes, const void *ent, uint64_t n, uint32_t shift, const void *slots, const uint32_t *ord,
@@ -514,14 +510,11 @@ int launch_fill_dense(uint32_t pos_bytes, const void *ent, uint64_t n, uint32_t 
     if (shift > kMaxNarrowShift) return 0;
     const uint64_t nb = (n >> shift) + 2;
     const int grid = static_cast<int>(std::min<uint64_t>((nb + 255) / 256, 256ull * 64));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (pos_bytes == 4)
-        hipLaunchKernelGGL((k_fill_dense<uint32_t>), dim3(grid), dim3(256), 0, st, static_cast<const RunEnt<uint32_t> *>(ent), n, shift,
+    return with_pos(pos_bytes, [&](auto p) {
+        using P = pos_t<decltype(p)>;
+        return launch_grid(k_fill_dense<P>, dim3(grid), dim3(256), 0, stream, static_cast<const RunEnt<P> *>(ent), n, shift,
                            static_cast<const RankSlot *>(slots), ord, dense);
-    else
-        hipLaunchKernelGGL((k_fill_dense<uint64_t>), dim3(grid), dim3(256), 0, st, static_cast<const RunEnt<uint64_t> *>(ent), n, shift,
-                           static_cast<const RankSlot *>(slots), ord, dense);
-    return static_cast<int>(hipGetLastError());
+    });
 }
 
 int launch_build_phi_slots(uint32_t pos_bytes, bool packed, const void *ent, uint64_t r, uint64_t n, uint32_t shift, void *slots, uint32_t *ord,
@@ -529,17 +522,11 @@ int launch_build_phi_slots(uint32_t pos_bytes, bool packed, const void *ent, uin
     const uint64_t nb = (n >> shift) + 2;
     const uint64_t groups = (nb + kBuildGroup - 1) / kBuildGroup;
     const int grid = static_cast<int>(std::min<uint64_t>((groups + 255) / 256, 256ull * 64));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (pos_bytes == 4)
-        hipLaunchKernelGGL((k_build_phi_slots<uint32_t, false>), dim3(grid), dim3(256), 0, st, static_cast<const PhiEnt<uint32_t> *>(ent), r, n, shift,
+    return with_pos(pos_bytes, [&](auto p) { return with_flag(packed, [&](auto pk) {   // (packed entries: 8-byte positions only)
+        using P = pos_t<decltype(p)>;
+        return launch_grid(k_build_phi_slots<P, sizeof(P) == 8 && decltype(pk)::value>, dim3(grid), dim3(256), 0, stream, static_cast<const PhiEnt<P> *>(ent), r, n, shift,
                            slots, ord, overflow);
-    else if (packed)
-        hipLaunchKernelGGL((k_build_phi_slots<uint64_t, true>), dim3(grid), dim3(256), 0, st, static_cast<const PhiEnt<uint64_t> *>(ent), r, n, shift,
-                           slots, ord, overflow);
-    else
-        hipLaunchKernelGGL((k_build_phi_slots<uint64_t, false>), dim3(grid), dim3(256), 0, st, static_cast<const PhiEnt<uint64_t> *>(ent), r, n, shift,
-                           slots, ord, overflow);
-    return static_cast<int>(hipGetLastError());
+    }); });
 }
 
 // ---- ftab construction: search every word of k major symbols with the step kernel itself ---------
@@ -618,9 +605,9 @@ int launch_build_ftab(const DevIndex &ix, const LaunchCfg &cfg, uint32_t k, void
         rc = static_cast<int>(hipGetLastError());
         if (!rc) rc = launch_find_range(plain, cfg, seqs, off, cnt, lo, hi, ss, st);
         if (!rc) {
-            if (ix.pos_bytes == 4) hipLaunchKernelGGL(k_ftab_pack<uint32_t>, dim3(grid_for(cfg, cnt)), dim3(256), 0, st, cnt, lo, hi, ss, dst);
-            else hipLaunchKernelGGL(k_ftab_pack<uint64_t>, dim3(grid_for(cfg, cnt)), dim3(256), 0, st, cnt, lo, hi, ss, dst);
-            rc = static_cast<int>(hipGetLastError());
+            rc = with_pos(ix.pos_bytes, [&](auto p) {
+                return launch_grid(k_ftab_pack<pos_t<decltype(p)>>, dim3(grid_for(cfg, cnt)), dim3(256), 0, st, cnt, lo, hi, ss, dst);
+            });
         }
     }
     if (!rc) rc = static_cast<int>(hipStreamSynchronize(st));

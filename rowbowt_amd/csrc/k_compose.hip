@@ -15,6 +15,7 @@
 // {n, total} -- the array shape both layouts consume (DevSym::ent slices / DevTree::ent) -- their run-end samples, and per
 // table (runs, total, F).
 #include "rbg_device.hpp"
+#include "rbg_dispatch.hpp"
 
 #include <chrono>
 #include <cstdlib>
@@ -676,8 +677,9 @@ int compose_levels_device(uint32_t pos_bytes, uint64_t n, uint32_t M, const Comp
     hipStream_t st = static_cast<hipStream_t>(stream);
     Pool pool;
     struct Scope { Pool *prev; explicit Scope(Pool *p) : prev(t_pool) { t_pool = p; } ~Scope() { t_pool = prev; } } scope(&pool);
-    return pos_bytes == 4 ? compose_impl<uint32_t>(n, M, major, g_start, g_id, g_samp, g_n, kmax, with_samples, out, st, keep_mask, inputs_released)
-                          : compose_impl<uint64_t>(n, M, major, g_start, g_id, g_samp, g_n, kmax, with_samples, out, st, keep_mask, inputs_released);
+    return with_pos(pos_bytes, [&](auto p) {
+        return compose_impl<pos_t<decltype(p)>>(n, M, major, g_start, g_id, g_samp, g_n, kmax, with_samples, out, st, keep_mask, inputs_released);
+    });
 }
 
 }  // namespace rbg

@@ -2,6 +2,7 @@
 #include <cstdlib>
 
 #include "rbg_device.hpp"
+#include "rbg_launch.hpp"
 #include "rbg_locate_docs.hpp"
 
 namespace rbg {
@@ -349,7 +350,6 @@ int launch_locate_fill(const DevIndex &ix, const LaunchCfg &cfg, const uint64_t 
                        const uint64_t *k, uint64_t N, uint64_t max_hits, const uint64_t *loc_off, uint64_t *locs,
                        const uint64_t *sub, const void *order, void *stream, unsigned long long *stats, uint32_t *locs32) {
     if (N == 0) return 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     // (the grid: up to 32 workgroups per CU looping over the chains; 8 / 16 / 64 per CU and one workgroup per 256 chains without a loop measured
     //  level or worse within the processes' spread: profiles/r06_experiments.txt)
     const dim3 grid(grid_for(cfg, N)), block(cfg.block_threads);
@@ -366,23 +366,21 @@ int launch_locate_fill(const DevIndex &ix, const LaunchCfg &cfg, const uint64_t 
     }
     // (rbg_device.hpp ChainStage: a value as its low word + one high byte; RBG_K3_HI8=0 -- tests -- stages whole 8-byte values at any n)
     const bool hi8 = ix.pos_bytes == 8 && ix.n < kChainHi8Limit && chain_hi8_enabled();
-#define RBG_LAUNCH_K3(PT, STS, OUT, SB, DST) \
-    do { \
-        if (sizeof(PT) == 8 && hi8) hipLaunchKernelGGL((k_locate_fill<PT, STS, OUT, SB, sizeof(PT) == 8>), grid, block, 0, st, ix, lo, hi, k, N, max_hits, loc_off, DST, sub, perm, skeys, stats); \
-        else hipLaunchKernelGGL((k_locate_fill<PT, STS, OUT, SB, false>), grid, block, 0, st, ix, lo, hi, k, N, max_hits, loc_off, DST, sub, perm, skeys, stats); \
-    } while (0)
-    if (locs32) {   // 4-byte locations (4-byte positions only; the caller checked)
-        if (ix.pos_bytes != 4) return static_cast<int>(hipErrorInvalidValue);
-        RBG_LAUNCH_K3(uint32_t, false, uint32_t, false, locs32);
-    } else if (stats) {
-        if (ix.pos_bytes == 4) RBG_LAUNCH_K3(uint32_t, true, uint64_t, false, locs); else RBG_LAUNCH_K3(uint64_t, true, uint64_t, false, locs);
-    } else if (sub) {
-        if (ix.pos_bytes == 4) RBG_LAUNCH_K3(uint32_t, false, uint64_t, true, locs); else RBG_LAUNCH_K3(uint64_t, false, uint64_t, true, locs);
-    } else {
-        if (ix.pos_bytes == 4) RBG_LAUNCH_K3(uint32_t, false, uint64_t, false, locs); else RBG_LAUNCH_K3(uint64_t, false, uint64_t, false, locs);
-    }
-#undef RBG_LAUNCH_K3
-    return static_cast<int>(hipGetLastError());
+    if (locs32 && ix.pos_bytes != 4) return static_cast<int>(hipErrorInvalidValue);   // 4-byte locations: 4-byte positions only (the caller checked)
+    return with_pos(ix.pos_bytes, [&](auto p) {
+        using P = pos_t<decltype(p)>;
+        // the variants that exist: instrumented, sub-ranges, plain, and at 4-byte positions 4-byte locations; HI8 at 8-byte positions only
+        auto fill = [&](auto sts, auto sb, auto *dst) {
+            return with_flag(hi8, [&](auto h8) {
+                return launch_grid(k_locate_fill<P, decltype(sts)::value, std::remove_pointer_t<decltype(dst)>, decltype(sb)::value, sizeof(P) == 8 && decltype(h8)::value>,
+                                   grid, block, 0, stream, ix, lo, hi, k, N, max_hits, loc_off, dst, sub, perm, skeys, stats);
+            });
+        };
+        if constexpr (sizeof(P) == 4) { if (locs32) return fill(no, no, locs32); }
+        if (stats) return fill(yes, no, locs);
+        if (sub) return fill(no, yes, locs);
+        return fill(no, no, locs);
+    });
 }
 
 int launch_locate_doc_hits(const DevIndex &ix, const LaunchCfg &cfg, const DocTable &t, const uint64_t *lo, const uint64_t *hi, const uint64_t *k, uint64_t N,
@@ -395,21 +393,14 @@ int launch_locate_doc_hits(const DevIndex &ix, const LaunchCfg &cfg, const DocTa
     const uint64_t *skeys = order ? reinterpret_cast<const uint64_t *>(static_cast<const char *>(order) + order_layout(N).keys) : nullptr;
     if (ix.layout == 2 && !ix.phi_slots)   // run-indexed layout with the phi list (k_runs.hip); with phi slots the kernels here answer its phi
         return launch_locate_doc_hits_runs(ix, t, lo, hi, k, N, max_hits, order, skeys, sets, ndocs_out, nodoc_out, doc_reads, doc_locs, stream);
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(locate_docs_grid(N)), block(kLocDocBlock);
     const uint32_t *perm = static_cast<const uint32_t *>(order);
     unsigned long long *dr = reinterpret_cast<unsigned long long *>(doc_reads), *dl = reinterpret_cast<unsigned long long *>(doc_locs);
     const size_t lds = locate_docs_lds_bytes(t.ndocs, t.ndir, doc_locs != nullptr);
-#define RBG_LAUNCH_LD(PT, LC) \
-    do { \
-        auto kern = k_locate_docs<PT, LC>; \
-        raise_lds(kern, lds); \
-        hipLaunchKernelGGL(kern, grid, block, lds, st, ix, t, lo, hi, k, N, max_hits, perm, skeys, sets, ndocs_out, nodoc_out, dr, dl); \
-    } while (0)
-    if (ix.pos_bytes == 4) { if (doc_locs) RBG_LAUNCH_LD(uint32_t, true); else RBG_LAUNCH_LD(uint32_t, false); }
-    else { if (doc_locs) RBG_LAUNCH_LD(uint64_t, true); else RBG_LAUNCH_LD(uint64_t, false); }
-#undef RBG_LAUNCH_LD
-    return static_cast<int>(hipGetLastError());
+    return with_pos(ix.pos_bytes, [&](auto p) { return with_flag(doc_locs != nullptr, [&](auto lc) {
+        return launch_lds(k_locate_docs<pos_t<decltype(p)>, decltype(lc)::value>, grid, block, lds, 0, stream,
+                          ix, t, lo, hi, k, N, max_hits, perm, skeys, sets, ndocs_out, nodoc_out, dr, dl);
+    }); });
 }
 
 }  // namespace rbg

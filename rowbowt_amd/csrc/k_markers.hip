@@ -1,5 +1,6 @@
 // k_markers.hip -- K4 and the seeding kernels: markers_at, find_range_w_markers, greedy seeds, marker seeds, single LF steps (rowbowt.hpp:74-88, :222-339, :406-482)
 #include "rbg_device.hpp"
+#include "rbg_launch.hpp"
 
 namespace rbg {
 namespace {
@@ -990,12 +991,10 @@ int launch_find_range_markers_plan(const DevIndex &ix, const LaunchCfg &cfg, con
         if (rc2) return rc2;
         return scan_in_place(mk_off + 1, N, tmp, tmp_bytes, st);
     }
-    const dim3 grid(grid_for(cfg, N)), block(cfg.block_threads);
-    if (ix.pos_bytes == 4)
-        hipLaunchKernelGGL((k_find_range_markers<uint32_t, false>), grid, block, 0, st, ix, seqs, off, N, wsize, max_range, lo, hi, mk_off, nullptr, nullptr);
-    else
-        hipLaunchKernelGGL((k_find_range_markers<uint64_t, false>), grid, block, 0, st, ix, seqs, off, N, wsize, max_range, lo, hi, mk_off, nullptr, nullptr);
-    int rc = static_cast<int>(hipGetLastError());
+    const int rc = with_pos(ix.pos_bytes, [&](auto p) {
+        return launch_grid(k_find_range_markers<pos_t<decltype(p)>, false>, dim3(grid_for(cfg, N)), dim3(cfg.block_threads), 0, stream,
+                           ix, seqs, off, N, wsize, max_range, lo, hi, mk_off, nullptr, nullptr);
+    });
     if (rc) return rc;
     return scan_in_place(mk_off + 1, N, tmp, tmp_bytes, st);
 }
@@ -1005,13 +1004,10 @@ int launch_find_range_markers_fill(const DevIndex &ix, const LaunchCfg &cfg, con
                                    void *stream) {
     if (N == 0) return 0;
     if (ix.layout == 2) return launch_find_range_markers_runs(ix, cfg, seqs, off, N, wsize, max_range, nullptr, nullptr, nullptr, mk_off, mk, true, stream);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid(grid_for(cfg, N)), block(cfg.block_threads);
-    if (ix.pos_bytes == 4)
-        hipLaunchKernelGGL((k_find_range_markers<uint32_t, true>), grid, block, 0, st, ix, seqs, off, N, wsize, max_range, nullptr, nullptr, nullptr, mk_off, mk);
-    else
-        hipLaunchKernelGGL((k_find_range_markers<uint64_t, true>), grid, block, 0, st, ix, seqs, off, N, wsize, max_range, nullptr, nullptr, nullptr, mk_off, mk);
-    return static_cast<int>(hipGetLastError());
+    return with_pos(ix.pos_bytes, [&](auto p) {
+        return launch_grid(k_find_range_markers<pos_t<decltype(p)>, true>, dim3(grid_for(cfg, N)), dim3(cfg.block_threads), 0, stream,
+                           ix, seqs, off, N, wsize, max_range, nullptr, nullptr, nullptr, mk_off, mk);
+    });
 }
 
 int launch_marker_seeds_plan(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N,
@@ -1027,17 +1023,10 @@ int launch_marker_seeds_plan(const DevIndex &ix, const LaunchCfg &cfg, const uin
     if (ix.layout == 2) {   // run-indexed layout: k_runs_seeds.hip
         rc = launch_marker_seeds_runs(ix, cfg, seqs, off, N, wsize, max_range, seed_off, mk_off, nullptr, nullptr, nullptr, nullptr, false, stream, lg, ftab_k);
     } else {
-#define RBG_MSP(PT, LG)                                                                                                                  \
-    do {                                                                                                                                  \
-        auto kern = k_marker_seeds<PT, false, LG>;                                                                                        \
-        const KmerLaunch L = kmer_launch(ix, cfg, N, kern, 0, kSeedKmerLevel);                                                            \
-        hipLaunchKernelGGL(kern, L.grid, L.block, L.lds, st, ix, seqs, off, N, wsize, max_range, ftab_k, seed_off, mk_off, nullptr, nullptr, nullptr, \
-                           nullptr, kSeedKmerLevel, lg);                                                                                  \
-    } while (0)
-        if (ix.pos_bytes == 4) { if (lg.base) RBG_MSP(uint32_t, true); else RBG_MSP(uint32_t, false); }
-        else { if (lg.base) RBG_MSP(uint64_t, true); else RBG_MSP(uint64_t, false); }
-#undef RBG_MSP
-        rc = static_cast<int>(hipGetLastError());
+        rc = with_pos(ix.pos_bytes, [&](auto p) { return with_flag(lg.base != nullptr, [&](auto logged) {
+            return launch_kmer(k_marker_seeds<pos_t<decltype(p)>, false, decltype(logged)::value>, ix, cfg, N, 0, kSeedKmerLevel, stream,
+                               ix, seqs, off, N, wsize, max_range, ftab_k, seed_off, mk_off, nullptr, nullptr, nullptr, nullptr, kSeedKmerLevel, lg);
+        }); });
     }
     if (rc) return rc;
     rc = scan_in_place(seed_off + 1, N, tmp, tmp_bytes, st);
@@ -1062,23 +1051,17 @@ int launch_marker_seeds_fill(const DevIndex &ix, const LaunchCfg &cfg, const uin
         if (rc) return rc;
         const uint64_t threads = N * 8;
         const int grid = static_cast<int>(std::min<uint64_t>((threads + 255) / 256, 256ull * 64));
-        if (ix.pos_bytes == 4) hipLaunchKernelGGL((k_marker_seeds_from_log<uint32_t>), dim3(grid), dim3(256), 0, st, ix, N, seed_off, mk_off, seeds, mk, lg);
-        else hipLaunchKernelGGL((k_marker_seeds_from_log<uint64_t>), dim3(grid), dim3(256), 0, st, ix, N, seed_off, mk_off, seeds, mk, lg);
-        rc = static_cast<int>(hipGetLastError());
+        rc = with_pos(ix.pos_bytes, [&](auto p) {
+            return launch_grid(k_marker_seeds_from_log<pos_t<decltype(p)>>, dim3(grid), dim3(256), 0, stream, ix, N, seed_off, mk_off, seeds, mk, lg);
+        });
         if (rc) return rc;
     }
     if (ix.layout == 2)
         return launch_marker_seeds_runs(ix, cfg, seqs, off, N, wsize, max_range, nullptr, nullptr, seed_off, mk_off, seeds, mk, true, stream, lg, ftab_k);
-#define RBG_MSF(PT)                                                                                                                       \
-    do {                                                                                                                                  \
-        auto kern = k_marker_seeds<PT, true, false>;                                                                                      \
-        const KmerLaunch L = kmer_launch(ix, cfg, N, kern, lg.base ? 256 : 0, kSeedKmerLevel);                                            \
-        hipLaunchKernelGGL(kern, L.grid, L.block, L.lds, st, ix, seqs, off, N, wsize, max_range, ftab_k, nullptr, nullptr, seed_off, mk_off, seeds, mk, \
-                           kSeedKmerLevel, lg);                                                                                           \
-    } while (0)
-    if (ix.pos_bytes == 4) RBG_MSF(uint32_t); else RBG_MSF(uint64_t);
-#undef RBG_MSF
-    return static_cast<int>(hipGetLastError());
+    return with_pos(ix.pos_bytes, [&](auto p) {
+        return launch_kmer(k_marker_seeds<pos_t<decltype(p)>, true, false>, ix, cfg, N, lg.base ? 256 : 0, kSeedKmerLevel, stream,
+                           ix, seqs, off, N, wsize, max_range, ftab_k, nullptr, nullptr, seed_off, mk_off, seeds, mk, kSeedKmerLevel, lg);
+    });
 }
 
 int launch_greedy_seed(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N,
@@ -1086,16 +1069,10 @@ int launch_greedy_seed(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *
     if (N == 0) return 0;
     if (ix.layout == 2) return launch_greedy_seed_runs(ix, cfg, seqs, off, N, min_length, lo, hi, qs, qe, ss, stream, stats);
     if (stats) return static_cast<int>(hipErrorNotSupported);   // (instrumented on the run-indexed layout only)
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define RBG_GS(PT)                                                                                                        \
-    do {                                                                                                                  \
-        auto kern = k_greedy_seed<PT>;                                                                                    \
-        const KmerLaunch L = kmer_launch(ix, cfg, N, kern, 0, kSeedKmerLevel);                                            \
-        hipLaunchKernelGGL(kern, L.grid, L.block, L.lds, st, ix, seqs, off, N, min_length, lo, hi, qs, qe, ss, kSeedKmerLevel); \
-    } while (0)
-    if (ix.pos_bytes == 4) RBG_GS(uint32_t); else RBG_GS(uint64_t);
-#undef RBG_GS
-    return static_cast<int>(hipGetLastError());
+    return with_pos(ix.pos_bytes, [&](auto p) {
+        return launch_kmer(k_greedy_seed<pos_t<decltype(p)>>, ix, cfg, N, 0, kSeedKmerLevel, stream,
+                           ix, seqs, off, N, min_length, lo, hi, qs, qe, ss, kSeedKmerLevel);
+    });
 }
 
 // greedy seed lists, two phases: the plan counts (no toehold) and scans, the fill walks again and writes
@@ -1107,13 +1084,10 @@ int launch_greedy_seeds_plan(const DevIndex &ix, const LaunchCfg &cfg, const uin
     if (ix.layout == 2) {
         rc = launch_greedy_seeds_list_runs(ix, cfg, seqs, off, N, min_length, w_sample, seed_off, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, stream);
     } else {
-        auto launch = [&](auto kern) {
-            const KmerLaunch L = kmer_launch(ix, cfg, N, kern, 0, kSeedKmerLevel);
-            hipLaunchKernelGGL(kern, L.grid, L.block, L.lds, st, ix, seqs, off, N, min_length, w_sample, seed_off, nullptr, nullptr, nullptr, nullptr, nullptr,
-                               nullptr, kSeedKmerLevel);
-        };
-        if (ix.pos_bytes == 4) launch(k_greedy_seeds_list<uint32_t, false, false>); else launch(k_greedy_seeds_list<uint64_t, false, false>);
-        rc = static_cast<int>(hipGetLastError());
+        rc = with_pos(ix.pos_bytes, [&](auto p) {
+            return launch_kmer(k_greedy_seeds_list<pos_t<decltype(p)>, false, false>, ix, cfg, N, 0, kSeedKmerLevel, stream,
+                               ix, seqs, off, N, min_length, w_sample, seed_off, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, kSeedKmerLevel);
+        });
     }
     if (rc) return rc;
     return scan_in_place(seed_off + 1, N, tmp, tmp_bytes, st);
@@ -1123,14 +1097,10 @@ int launch_greedy_seeds_fill(const DevIndex &ix, const LaunchCfg &cfg, const uin
                              bool w_sample, const uint64_t *seed_off, uint64_t *lo, uint64_t *hi, uint64_t *qs, uint64_t *qe, uint64_t *ss, void *stream) {
     if (N == 0) return 0;
     if (ix.layout == 2) return launch_greedy_seeds_list_runs(ix, cfg, seqs, off, N, min_length, w_sample, nullptr, seed_off, lo, hi, qs, qe, ss, true, stream);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    auto launch = [&](auto kern) {
-        const KmerLaunch L = kmer_launch(ix, cfg, N, kern, 0, kSeedKmerLevel);
-        hipLaunchKernelGGL(kern, L.grid, L.block, L.lds, st, ix, seqs, off, N, min_length, w_sample, nullptr, seed_off, lo, hi, qs, qe, ss, kSeedKmerLevel);
-    };
-    if (ix.pos_bytes == 4) { if (w_sample) launch(k_greedy_seeds_list<uint32_t, true, true>); else launch(k_greedy_seeds_list<uint32_t, true, false>); }
-    else { if (w_sample) launch(k_greedy_seeds_list<uint64_t, true, true>); else launch(k_greedy_seeds_list<uint64_t, true, false>); }
-    return static_cast<int>(hipGetLastError());
+    return with_pos(ix.pos_bytes, [&](auto p) { return with_flag(w_sample, [&](auto ws) {   // (the fill; the count is the plan's <false, false>)
+        return launch_kmer(k_greedy_seeds_list<pos_t<decltype(p)>, true, decltype(ws)::value>, ix, cfg, N, 0, kSeedKmerLevel, stream,
+                           ix, seqs, off, N, min_length, w_sample, nullptr, seed_off, lo, hi, qs, qe, ss, kSeedKmerLevel);
+    }); });
 }
 
 // toehold checkpoints: the slots of every read (from the offsets alone), then one walk
@@ -1147,11 +1117,10 @@ int launch_toehold_chkpnts(const DevIndex &ix, const LaunchCfg &cfg, const uint8
                            const uint64_t *slot_off, uint64_t *cnt, uint64_t *lo, uint64_t *hi, uint64_t *qs, uint64_t *qe, uint64_t *ss, void *stream) {
     if (N == 0) return 0;
     if (ix.layout == 2) return launch_toehold_chkpnts_runs(ix, cfg, seqs, off, N, wsize, slot_off, cnt, lo, hi, qs, qe, ss, stream);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid(grid_for(cfg, N)), block(cfg.block_threads);
-    if (ix.pos_bytes == 4) hipLaunchKernelGGL((k_toehold_chkpnts<uint32_t>), grid, block, 0, st, ix, seqs, off, N, wsize, slot_off, cnt, lo, hi, qs, qe, ss);
-    else hipLaunchKernelGGL((k_toehold_chkpnts<uint64_t>), grid, block, 0, st, ix, seqs, off, N, wsize, slot_off, cnt, lo, hi, qs, qe, ss);
-    return static_cast<int>(hipGetLastError());
+    return with_pos(ix.pos_bytes, [&](auto p) {
+        return launch_grid(k_toehold_chkpnts<pos_t<decltype(p)>>, dim3(grid_for(cfg, N)), dim3(cfg.block_threads), 0, stream,
+                           ix, seqs, off, N, wsize, slot_off, cnt, lo, hi, qs, qe, ss);
+    });
 }
 
 size_t marker_lmems_tmp_bytes(uint64_t total) { return (((total + 1) * 8 + 255) & ~size_t(255)) + scan_tmp_bytes(total); }
@@ -1159,16 +1128,10 @@ size_t marker_lmems_tmp_bytes(uint64_t total) { return (((total + 1) * 8 + 255) 
 static int marker_lmems_walk(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t total, uint64_t wsize,
                              uint64_t max_range, uint64_t K, uint64_t *rec_off, uint64_t *seeds, uint64_t *mk, bool fill, hipStream_t st) {
     if (ix.layout == 2) return launch_marker_lmems_runs(ix, cfg, seqs, off, N, total, wsize, max_range, K, rec_off, seeds, mk, fill, st);
-#define RBG_LMS(PT, F)                                                                                                                    \
-    do {                                                                                                                                  \
-        auto kern = k_marker_lmems<PT, F>;                                                                                                \
-        const KmerLaunch L = kmer_launch(ix, cfg, total, kern, 0, kSeedKmerLevel);                                                        \
-        hipLaunchKernelGGL(kern, L.grid, L.block, L.lds, st, ix, seqs, off, N, total, wsize, max_range, K, rec_off, seeds, mk, kSeedKmerLevel); \
-    } while (0)
-    if (ix.pos_bytes == 4) { if (fill) RBG_LMS(uint32_t, true); else RBG_LMS(uint32_t, false); }
-    else { if (fill) RBG_LMS(uint64_t, true); else RBG_LMS(uint64_t, false); }
-#undef RBG_LMS
-    return static_cast<int>(hipGetLastError());
+    return with_pos(ix.pos_bytes, [&](auto p) { return with_flag(fill, [&](auto f) {
+        return launch_kmer(k_marker_lmems<pos_t<decltype(p)>, decltype(f)::value>, ix, cfg, total, 0, kSeedKmerLevel, st,
+                           ix, seqs, off, N, total, wsize, max_range, K, rec_off, seeds, mk, kSeedKmerLevel);
+    }); });
 }
 
 int launch_marker_lmems_plan(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t total,
@@ -1201,11 +1164,9 @@ int launch_lf(const DevIndex &ix, const LaunchCfg &cfg, const uint64_t *lo, cons
               uint64_t N, uint64_t *lo_out, uint64_t *hi_out, void *stream) {
     if (N == 0) return 0;
     if (ix.layout == 2) return launch_lf_runs(ix, cfg, lo, hi, sym, N, lo_out, hi_out, stream);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid(grid_for(cfg, N)), block(cfg.block_threads);
-    if (ix.pos_bytes == 4) hipLaunchKernelGGL((k_lf<uint32_t>), grid, block, 0, st, ix, lo, hi, sym, N, lo_out, hi_out);
-    else hipLaunchKernelGGL((k_lf<uint64_t>), grid, block, 0, st, ix, lo, hi, sym, N, lo_out, hi_out);
-    return static_cast<int>(hipGetLastError());
+    return with_pos(ix.pos_bytes, [&](auto p) {
+        return launch_grid(k_lf<pos_t<decltype(p)>>, dim3(grid_for(cfg, N)), dim3(cfg.block_threads), 0, stream, ix, lo, hi, sym, N, lo_out, hi_out);
+    });
 }
 
 int launch_count_from_ranges(const uint64_t *lo, const uint64_t *hi, uint64_t N, uint64_t *count, void *stream) {

@@ -8,6 +8,7 @@
 #include "rbg_runs2_device.hpp"
 #include "rbg_locate_docs.hpp"
 #include "rbg_jump.h"
+#include "rbg_launch.hpp"
 
 namespace rbg {
 namespace {
@@ -479,45 +480,30 @@ int launch_find_range_runs_impl(const DevIndex &ix, const LaunchCfg &cfg, const 
                                 uint64_t *lo, uint64_t *hi, uint64_t *ssamp, void *stream, bool packed, unsigned long long *stats,
                                 const uint32_t *sel = nullptr, const uint32_t *nsel = nullptr) {
     if (N == 0) return 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t lds = run_search2_lds(ix);
     // how a quad's bucket records travel (rbg_runs2_device.hpp): LDS-direct loads (the default), or RBG_REC_FETCH=quad: registers + quad permutes
     static const bool glds = [] { const char *e = std::getenv("RBG_REC_FETCH"); return !(e && std::strcmp(e, "quad") == 0); }();
     // the byte form stages its reads as 2-bit codes in LDS (STAGE above; needs an alphabet the register tables express: DevIndex::stage_ok);
     // RBG_STAGE_READS=0: every lane walks its read through a cursor of 16-byte chunks as before round 6 (A/B, profiles/r06_k2_sectors.md)
     static const bool stage = [] { const char *e = std::getenv("RBG_STAGE_READS"); return !(e && e[0] == '0'); }();
-    LaunchCfg c = cfg;   // 512-thread workgroups: the staged tables and top level are shared by eight waves
-    c.block_threads = 512;
-    c.max_blocks = cfg.max_blocks > 0 ? std::max(1, cfg.max_blocks / 2) : 256 * 16;
+    if (stats && packed) return static_cast<int>(hipErrorNotSupported);
+    const LaunchCfg c = runs512_cfg(cfg);
     // sel mode: the number of reads is only known on the device; a fixed modest grid loops over it
     const dim3 grid(sel ? std::min(grid_for(c, N), 256) : grid_for(c, N)), block(512);
-#define RBG_LAUNCH_FRR1(PT, TOE, PK, STS, GL, SG)                                                      \
-    do {                                                                                               \
-        auto kern = k_find_range_runs<PT, TOE, PK, STS, GL, SG>;                                       \
-        raise_lds(kern, lds, (GL ? 8 * kTileBytes : 0) + (SG ? 8 * kStageWaveBytes : 0));             \
-        hipLaunchKernelGGL(kern, grid, block, lds, st, ix, src_a, src_b, N, lo, hi, ssamp, stats, sel, nsel);     \
-    } while (0)
-#define RBG_LAUNCH_FRR(PT, TOE, PK, STS)                                                               \
-    do {                                                                                               \
-        if (glds && stage && !PK && !sel) RBG_LAUNCH_FRR1(PT, TOE, false, STS, true, true);            \
-        else if (glds) RBG_LAUNCH_FRR1(PT, TOE, PK, STS, true, false);                                 \
-        else RBG_LAUNCH_FRR1(PT, TOE, PK, STS, false, false);                                          \
-    } while (0)
-#define RBG_LAUNCH_FRR2(PT, TOE)                                                                       \
-    do {                                                                                               \
-        if (stats) { if (packed) return static_cast<int>(hipErrorNotSupported); RBG_LAUNCH_FRR(PT, TOE, false, true); } \
-        else if (packed) RBG_LAUNCH_FRR(PT, TOE, true, false);                                         \
-        else RBG_LAUNCH_FRR(PT, TOE, false, false);                                                    \
-    } while (0)
-    if (ix.pos_bytes == 4) {
-        if (ssamp) RBG_LAUNCH_FRR2(uint32_t, true); else RBG_LAUNCH_FRR2(uint32_t, false);
-    } else {
-        if (ssamp) RBG_LAUNCH_FRR2(uint64_t, true); else RBG_LAUNCH_FRR2(uint64_t, false);
-    }
-#undef RBG_LAUNCH_FRR2
-#undef RBG_LAUNCH_FRR
-#undef RBG_LAUNCH_FRR1
-    return static_cast<int>(hipGetLastError());
+    return with_pos(ix.pos_bytes, [&](auto p) { return with_flag(ssamp != nullptr, [&](auto toe) {
+        auto search = [&](auto pk, auto sts, auto gl, auto sg) {
+            constexpr bool GL = decltype(gl)::value, SG = decltype(sg)::value;
+            return launch_lds(k_find_range_runs<pos_t<decltype(p)>, decltype(toe)::value, decltype(pk)::value, decltype(sts)::value, GL, SG>, grid, block, lds,
+                              (GL ? 8 * kTileBytes : 0) + (SG ? 8 * kStageWaveBytes : 0), stream, ix, src_a, src_b, N, lo, hi, ssamp, stats, sel, nsel);
+        };
+        // the variants that exist: the byte form staged, LDS-direct or by quads (instrumented or not); the packed form LDS-direct or by quads
+        auto fetch = [&](auto pk, auto sts) {
+            if constexpr (!decltype(pk)::value) { if (glds && stage && !sel) return search(no, sts, yes, yes); }
+            return glds ? search(pk, sts, yes, no) : search(pk, sts, no, no);
+        };
+        if (stats) return fetch(no, yes);
+        return packed ? fetch(yes, no) : fetch(no, no);
+    }); });
 }
 
 int launch_find_range_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N,
@@ -540,29 +526,24 @@ int launch_locate_fill_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint
                             const void *order, const uint64_t *skeys, void *stream, unsigned long long *stats, uint32_t *locs32) {
     if (N == 0) return 0;
     if ((stats || locs32) && sub) return static_cast<int>(hipErrorInvalidValue);
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(grid_for(cfg, N)), block(256);
     const uint32_t *perm = static_cast<const uint32_t *>(order);
     const bool hi8 = ix.pos_bytes == 8 && ix.n < kChainHi8Limit && chain_hi8_enabled();
-#define RBG_LAUNCH_LFR2(PT, OUT, STS, SB, DST) \
-    do { \
-        if (sizeof(PT) == 8 && hi8) hipLaunchKernelGGL((k_locate_fill_runs2<PT, OUT, STS, SB, sizeof(PT) == 8>), grid, block, 0, st, ix, lo, hi, k, N, max_hits, loc_off, DST, sub, perm, skeys, stats); \
-        else hipLaunchKernelGGL((k_locate_fill_runs2<PT, OUT, STS, SB, false>), grid, block, 0, st, ix, lo, hi, k, N, max_hits, loc_off, DST, sub, perm, skeys, stats); \
-    } while (0)
-    if (locs32) {
-        if (ix.pos_bytes != 4) return static_cast<int>(hipErrorInvalidValue);
-        RBG_LAUNCH_LFR2(uint32_t, uint32_t, false, false, locs32);
-    } else if (stats) {
-        if (ix.pos_bytes == 4) RBG_LAUNCH_LFR2(uint32_t, uint64_t, true, false, locs); else RBG_LAUNCH_LFR2(uint64_t, uint64_t, true, false, locs);
-    } else if (sub) {
-        if (ix.pos_bytes == 4) RBG_LAUNCH_LFR2(uint32_t, uint64_t, false, true, locs); else RBG_LAUNCH_LFR2(uint64_t, uint64_t, false, true, locs);
-    } else if (ix.pos_bytes == 4) {
-        RBG_LAUNCH_LFR2(uint32_t, uint64_t, false, false, locs);
-    } else {
-        RBG_LAUNCH_LFR2(uint64_t, uint64_t, false, false, locs);
-    }
-#undef RBG_LAUNCH_LFR2
-    return static_cast<int>(hipGetLastError());
+    if (locs32 && ix.pos_bytes != 4) return static_cast<int>(hipErrorInvalidValue);
+    return with_pos(ix.pos_bytes, [&](auto p) {
+        using P = pos_t<decltype(p)>;
+        // the variants that exist: as launch_locate_fill's (k_locate.hip)
+        auto fill = [&](auto sts, auto sb, auto *dst) {
+            return with_flag(hi8, [&](auto h8) {
+                return launch_grid(k_locate_fill_runs2<P, std::remove_pointer_t<decltype(dst)>, decltype(sts)::value, decltype(sb)::value, sizeof(P) == 8 && decltype(h8)::value>,
+                                   grid, block, 0, stream, ix, lo, hi, k, N, max_hits, loc_off, dst, sub, perm, skeys, stats);
+            });
+        };
+        if constexpr (sizeof(P) == 4) { if (locs32) return fill(no, no, locs32); }
+        if (stats) return fill(yes, no, locs);
+        if (sub) return fill(no, yes, locs);
+        return fill(no, no, locs);
+    });
 }
 
 int launch_locate_doc_hits_runs(const DevIndex &ix, const DocTable &t, const uint64_t *lo, const uint64_t *hi, const uint64_t *k, uint64_t N, uint64_t max_hits,
@@ -570,21 +551,14 @@ int launch_locate_doc_hits_runs(const DevIndex &ix, const DocTable &t, const uin
                                 uint64_t *doc_locs, void *stream) {
     if (t.ndocs == 0 || t.ndocs > kLocDocLdsDocs) return static_cast<int>(hipErrorInvalidValue);
     if (N == 0) return 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(locate_docs_grid(N)), block(kLocDocBlock);
     const uint32_t *perm = static_cast<const uint32_t *>(order);
     unsigned long long *dr = reinterpret_cast<unsigned long long *>(doc_reads), *dl = reinterpret_cast<unsigned long long *>(doc_locs);
     const size_t lds = locate_docs_lds_bytes(t.ndocs, t.ndir, doc_locs != nullptr);
-#define RBG_LAUNCH_LDR(PT, LC) \
-    do { \
-        auto kern = k_locate_docs_runs2<PT, LC>; \
-        raise_lds(kern, lds); \
-        hipLaunchKernelGGL(kern, grid, block, lds, st, ix, t, lo, hi, k, N, max_hits, perm, skeys, sets, ndocs_out, nodoc_out, dr, dl); \
-    } while (0)
-    if (ix.pos_bytes == 4) { if (doc_locs) RBG_LAUNCH_LDR(uint32_t, true); else RBG_LAUNCH_LDR(uint32_t, false); }
-    else { if (doc_locs) RBG_LAUNCH_LDR(uint64_t, true); else RBG_LAUNCH_LDR(uint64_t, false); }
-#undef RBG_LAUNCH_LDR
-    return static_cast<int>(hipGetLastError());
+    return with_pos(ix.pos_bytes, [&](auto p) { return with_flag(doc_locs != nullptr, [&](auto lc) {
+        return launch_lds(k_locate_docs_runs2<pos_t<decltype(p)>, decltype(lc)::value>, grid, block, lds, 0, stream,
+                          ix, t, lo, hi, k, N, max_hits, perm, skeys, sets, ndocs_out, nodoc_out, dr, dl);
+    }); });
 }
 
 }  // namespace rbg

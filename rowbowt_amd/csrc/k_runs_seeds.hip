@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "rbg_runs2_device.hpp"
+#include "rbg_launch.hpp"
 
 namespace rbg {
 namespace {
@@ -1028,149 +1029,118 @@ struct SeedLaunch {
     size_t lds;
 };
 SeedLaunch seed_launch(const DevIndex &ix, const LaunchCfg &cfg, uint64_t N) {
-    LaunchCfg c = cfg;   // 512-thread workgroups: the staged tables are shared by eight waves
-    c.block_threads = 512;
-    c.max_blocks = cfg.max_blocks > 0 ? std::max(1, cfg.max_blocks / 2) : 256 * 16;
-    return SeedLaunch{dim3(grid_for(c, N)), dim3(512), run_search2_lds(ix)};
+    return SeedLaunch{dim3(grid_for(runs512_cfg(cfg), N)), dim3(512), run_search2_lds(ix)};
+}
+
+// every lane fetches its own record: the quad fetch of k_find_range_runs (rbg_runs2_device.hpp lane_lf2_quad) measured the same here (6.80 ms
+// against 6.77 per 10 M reads on the bench index, profiles/r05_experiments.txt) and costs the 8-byte instantiation its fourth wave per SIMD
+// (131 VGPRs).  RBG_GREEDY_FETCH=quad keeps the A/B runnable.
+bool greedy_fetch_quad() {
+    static const bool quad = [] { const char *e = std::getenv("RBG_GREEDY_FETCH"); return e && e[0] == 'q'; }();
+    return quad;
+}
+
+// (the two seed walks hold the staged reads: static LDS)
+template <typename Kernel, typename... Args>
+int launch_seed(Kernel kern, const SeedLaunch &L, void *stream, const Args &...args) {
+    return launch_lds(kern, L.grid, L.block, L.lds, 8 * kStageWaveBytes, stream, args...);
 }
 
 }  // namespace
 
-#define RBG_LAUNCH_SEEDK(KERN, ...)                                                     \
-    do {                                                                                \
-        auto kern = KERN;                                                               \
-        raise_lds(kern, L.lds, 8 * kStageWaveBytes);   /* (the two seed walks hold the staged reads: static LDS) */ \
-        hipLaunchKernelGGL(kern, L.grid, L.block, L.lds, st, ix, __VA_ARGS__);          \
-    } while (0)
-
 int launch_lf_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint64_t *lo, const uint64_t *hi, const uint8_t *sym, uint64_t N,
                    uint64_t *lo_out, uint64_t *hi_out, void *stream) {
     if (N == 0) return 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const SeedLaunch L = seed_launch(ix, cfg, N);
-    if (ix.pos_bytes == 4) RBG_LAUNCH_SEEDK((k_lf_runs<uint32_t>), lo, hi, sym, N, lo_out, hi_out);
-    else RBG_LAUNCH_SEEDK((k_lf_runs<uint64_t>), lo, hi, sym, N, lo_out, hi_out);
-    return static_cast<int>(hipGetLastError());
+    return with_pos(ix.pos_bytes, [&](auto p) { return launch_seed(k_lf_runs<pos_t<decltype(p)>>, L, stream, ix, lo, hi, sym, N, lo_out, hi_out); });
 }
 
 int launch_find_range_markers_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N,
                                    uint64_t wsize, uint64_t max_range, uint64_t *lo, uint64_t *hi, uint64_t *cnt, const uint64_t *mk_off,
                                    uint64_t *mk, bool fill, void *stream) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const SeedLaunch L = seed_launch(ix, cfg, N);
-#define RBG_FRM(PT)                                                                                                                           \
-    do {                                                                                                                                     \
-        if (fill) RBG_LAUNCH_SEEDK((k_find_range_markers_runs<PT, true>), seqs, off, N, wsize, max_range, lo, hi, cnt, mk_off, mk);           \
-        else RBG_LAUNCH_SEEDK((k_find_range_markers_runs<PT, false>), seqs, off, N, wsize, max_range, lo, hi, cnt, mk_off, mk);               \
-    } while (0)
-    if (ix.pos_bytes == 4) RBG_FRM(uint32_t); else RBG_FRM(uint64_t);
-#undef RBG_FRM
-    return static_cast<int>(hipGetLastError());
+    return with_pos(ix.pos_bytes, [&](auto p) { return with_flag(fill, [&](auto f) {
+        return launch_seed(k_find_range_markers_runs<pos_t<decltype(p)>, decltype(f)::value>, L, stream,
+                           ix, seqs, off, N, wsize, max_range, lo, hi, cnt, mk_off, mk);
+    }); });
 }
 
 int launch_greedy_seed_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N,
                             uint64_t min_length, uint64_t *lo, uint64_t *hi, uint64_t *qs, uint64_t *qe, uint64_t *ss, void *stream, unsigned long long *stats) {
     if (N == 0) return 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const SeedLaunch L = seed_launch(ix, cfg, N);
-    if (stats) {   // the instrumented instantiation (rbg_greedy_longest_seed_stats_dev): same walk, same outputs
-        if (ix.pos_bytes == 4) RBG_LAUNCH_SEEDK((k_greedy_seed_runs<uint32_t, false, true>), seqs, off, N, min_length, lo, hi, qs, qe, ss, stats);
-        else RBG_LAUNCH_SEEDK((k_greedy_seed_runs<uint64_t, false, true>), seqs, off, N, min_length, lo, hi, qs, qe, ss, stats);
-        return static_cast<int>(hipGetLastError());
-    }
-    // every lane fetches its own record: the quad fetch of k_find_range_runs (rbg_runs2_device.hpp lane_lf2_quad) measured the same here (6.80 ms
-    // against 6.77 per 10 M reads on the bench index, profiles/r05_experiments.txt) and costs the 8-byte instantiation its fourth wave per SIMD
-    // (131 VGPRs).  RBG_GREEDY_FETCH=quad keeps the A/B runnable.
-    static const bool quad = [] { const char *e = std::getenv("RBG_GREEDY_FETCH"); return e && e[0] == 'q'; }();
-    if (quad) {
-        if (ix.pos_bytes == 4) RBG_LAUNCH_SEEDK((k_greedy_seed_runs<uint32_t, true>), seqs, off, N, min_length, lo, hi, qs, qe, ss, nullptr);
-        else RBG_LAUNCH_SEEDK((k_greedy_seed_runs<uint64_t, true>), seqs, off, N, min_length, lo, hi, qs, qe, ss, nullptr);
-    } else {
-        if (ix.pos_bytes == 4) RBG_LAUNCH_SEEDK((k_greedy_seed_runs<uint32_t, false>), seqs, off, N, min_length, lo, hi, qs, qe, ss, nullptr);
-        else RBG_LAUNCH_SEEDK((k_greedy_seed_runs<uint64_t, false>), seqs, off, N, min_length, lo, hi, qs, qe, ss, nullptr);
-    }
-    return static_cast<int>(hipGetLastError());
+    return with_pos(ix.pos_bytes, [&](auto p) {
+        auto walk = [&](auto qd, auto sts) {
+            return launch_seed(k_greedy_seed_runs<pos_t<decltype(p)>, decltype(qd)::value, decltype(sts)::value>, L, stream,
+                               ix, seqs, off, N, min_length, lo, hi, qs, qe, ss, stats);
+        };
+        // the variants that exist: instrumented (rbg_greedy_longest_seed_stats_dev: same walk, same outputs, own fetch only), quad fetch, own fetch
+        if (stats) return walk(no, yes);
+        return greedy_fetch_quad() ? walk(yes, no) : walk(no, no);
+    });
 }
 
 int launch_marker_seeds_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t wsize,
                              uint64_t max_range, uint64_t *seed_cnt, uint64_t *mk_cnt, const uint64_t *seed_off, const uint64_t *mk_off,
                              uint64_t *seeds, uint64_t *mk, bool fill, void *stream, const SeedLog &lg, uint64_t ftab_k) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
     SeedLaunch L = seed_launch(ix, cfg, N);
     if (fill && lg.base) L.grid = dim3(std::min<unsigned>(L.grid.x, 128u));   // the listed sequences only: their number is on the device
-    if (ftab_k) {   // rb_markers --ftab
-#define RBG_MSF(PT)                                                                                                                          \
-    do {                                                                                                                                     \
-        if (fill) RBG_LAUNCH_SEEDK((k_marker_seeds_ftab_runs2<PT, true, false>), seqs, off, N, wsize, max_range, ftab_k, seed_cnt, mk_cnt, seed_off, mk_off, seeds, mk, lg); \
-        else if (lg.base) RBG_LAUNCH_SEEDK((k_marker_seeds_ftab_runs2<PT, false, true>), seqs, off, N, wsize, max_range, ftab_k, seed_cnt, mk_cnt, seed_off, mk_off, seeds, mk, lg); \
-        else RBG_LAUNCH_SEEDK((k_marker_seeds_ftab_runs2<PT, false, false>), seqs, off, N, wsize, max_range, ftab_k, seed_cnt, mk_cnt, seed_off, mk_off, seeds, mk, lg); \
-    } while (0)
-        if (ix.pos_bytes == 4) RBG_MSF(uint32_t); else RBG_MSF(uint64_t);
-#undef RBG_MSF
-        return static_cast<int>(hipGetLastError());
-    }
-    if (lg.stats && !lg.base) {   // the instrumented instantiations (rbg_marker_seeds_stats_dev): same walks, same outputs
-#define RBG_MSS(PT)                                                                                                                          \
-    do {                                                                                                                                     \
-        if (fill) RBG_LAUNCH_SEEDK((k_marker_seeds_runs<PT, true, false, true>), seqs, off, N, wsize, max_range, seed_cnt, mk_cnt, seed_off, mk_off, seeds, mk, lg); \
-        else RBG_LAUNCH_SEEDK((k_marker_seeds_runs<PT, false, false, true>), seqs, off, N, wsize, max_range, seed_cnt, mk_cnt, seed_off, mk_off, seeds, mk, lg); \
-    } while (0)
-        if (ix.pos_bytes == 4) RBG_MSS(uint32_t); else RBG_MSS(uint64_t);
-#undef RBG_MSS
-        return static_cast<int>(hipGetLastError());
-    }
-#define RBG_MSR(PT)                                                                                                                          \
-    do {                                                                                                                                     \
-        if (fill) RBG_LAUNCH_SEEDK((k_marker_seeds_runs<PT, true, false>), seqs, off, N, wsize, max_range, seed_cnt, mk_cnt, seed_off, mk_off, seeds, mk, lg); \
-        else if (lg.base) RBG_LAUNCH_SEEDK((k_marker_seeds_runs<PT, false, true>), seqs, off, N, wsize, max_range, seed_cnt, mk_cnt, seed_off, mk_off, seeds, mk, lg); \
-        else RBG_LAUNCH_SEEDK((k_marker_seeds_runs<PT, false, false>), seqs, off, N, wsize, max_range, seed_cnt, mk_cnt, seed_off, mk_off, seeds, mk, lg); \
-    } while (0)
-    if (ix.pos_bytes == 4) RBG_MSR(uint32_t); else RBG_MSR(uint64_t);
-#undef RBG_MSR
-    return static_cast<int>(hipGetLastError());
+    return with_pos(ix.pos_bytes, [&](auto p) {
+        using P = pos_t<decltype(p)>;
+        if (ftab_k) {   // rb_markers --ftab
+            auto walk = [&](auto f, auto lg_) {
+                return launch_seed(k_marker_seeds_ftab_runs2<P, decltype(f)::value, decltype(lg_)::value>, L, stream,
+                                   ix, seqs, off, N, wsize, max_range, ftab_k, seed_cnt, mk_cnt, seed_off, mk_off, seeds, mk, lg);
+            };
+            // the variants that exist: fill, logged count, count
+            if (fill) return walk(yes, no);
+            return lg.base ? walk(no, yes) : walk(no, no);
+        }
+        auto walk = [&](auto f, auto lg_, auto sts) {
+            return launch_seed(k_marker_seeds_runs<P, decltype(f)::value, decltype(lg_)::value, decltype(sts)::value>, L, stream,
+                               ix, seqs, off, N, wsize, max_range, seed_cnt, mk_cnt, seed_off, mk_off, seeds, mk, lg);
+        };
+        // the variants that exist: fill and count, each instrumented or not (rbg_marker_seeds_stats_dev: same walks, same outputs), and the logged count
+        if (lg.stats && !lg.base) return fill ? walk(yes, no, yes) : walk(no, no, yes);
+        if (fill) return walk(yes, no, no);
+        return lg.base ? walk(no, yes, no) : walk(no, no, no);
+    });
 }
 
 int launch_marker_lmems_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t total,
                              uint64_t wsize, uint64_t max_range, uint64_t ftab_k, uint64_t *rec_off, uint64_t *seeds, uint64_t *mk, bool fill,
                              void *stream) {
     if (N == 0 || total == 0) return 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const SeedLaunch L = seed_launch(ix, cfg, total);
-#define RBG_LMR(PT)                                                                                                                          \
-    do {                                                                                                                                     \
-        if (fill) RBG_LAUNCH_SEEDK((k_marker_lmems_runs<PT, true>), seqs, off, N, total, wsize, max_range, ftab_k, rec_off, seeds, mk);     \
-        else RBG_LAUNCH_SEEDK((k_marker_lmems_runs<PT, false>), seqs, off, N, total, wsize, max_range, ftab_k, rec_off, seeds, mk);         \
-    } while (0)
-    if (ix.pos_bytes == 4) RBG_LMR(uint32_t); else RBG_LMR(uint64_t);
-#undef RBG_LMR
-    return static_cast<int>(hipGetLastError());
+    return with_pos(ix.pos_bytes, [&](auto p) { return with_flag(fill, [&](auto f) {
+        return launch_seed(k_marker_lmems_runs<pos_t<decltype(p)>, decltype(f)::value>, L, stream,
+                           ix, seqs, off, N, total, wsize, max_range, ftab_k, rec_off, seeds, mk);
+    }); });
 }
+
 int launch_greedy_seeds_list_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t min_length,
                                   bool w_sample, uint64_t *seed_cnt, const uint64_t *seed_off, uint64_t *lo, uint64_t *hi, uint64_t *qs, uint64_t *qe,
                                   uint64_t *ss, bool fill, void *stream) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const SeedLaunch L = seed_launch(ix, cfg, N);
-#define RBG_GSL(PT)                                                                                                                          \
-    do {                                                                                                                                     \
-        if (!fill) RBG_LAUNCH_SEEDK((k_greedy_seeds_list_runs<PT, false, false>), seqs, off, N, min_length, w_sample, seed_cnt, seed_off, lo, hi, qs, qe, ss); \
-        else if (w_sample) RBG_LAUNCH_SEEDK((k_greedy_seeds_list_runs<PT, true, true>), seqs, off, N, min_length, w_sample, seed_cnt, seed_off, lo, hi, qs, qe, ss); \
-        else RBG_LAUNCH_SEEDK((k_greedy_seeds_list_runs<PT, true, false>), seqs, off, N, min_length, w_sample, seed_cnt, seed_off, lo, hi, qs, qe, ss); \
-    } while (0)
-    if (ix.pos_bytes == 4) RBG_GSL(uint32_t); else RBG_GSL(uint64_t);
-#undef RBG_GSL
-    return static_cast<int>(hipGetLastError());
+    return with_pos(ix.pos_bytes, [&](auto p) {
+        auto walk = [&](auto f, auto ws) {
+            return launch_seed(k_greedy_seeds_list_runs<pos_t<decltype(p)>, decltype(f)::value, decltype(ws)::value>, L, stream,
+                               ix, seqs, off, N, min_length, w_sample, seed_cnt, seed_off, lo, hi, qs, qe, ss);
+        };
+        // the variants that exist: count (no toehold), fill with and without toeholds
+        if (!fill) return walk(no, no);
+        return w_sample ? walk(yes, yes) : walk(yes, no);
+    });
 }
 
 int launch_toehold_chkpnts_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N, uint64_t wsize,
                                 const uint64_t *slot_off, uint64_t *cnt, uint64_t *lo, uint64_t *hi, uint64_t *qs, uint64_t *qe, uint64_t *ss,
                                 void *stream) {
     if (N == 0) return 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const SeedLaunch L = seed_launch(ix, cfg, N);
-    if (ix.pos_bytes == 4) RBG_LAUNCH_SEEDK((k_toehold_chkpnts_runs<uint32_t>), seqs, off, N, wsize, slot_off, cnt, lo, hi, qs, qe, ss);
-    else RBG_LAUNCH_SEEDK((k_toehold_chkpnts_runs<uint64_t>), seqs, off, N, wsize, slot_off, cnt, lo, hi, qs, qe, ss);
-    return static_cast<int>(hipGetLastError());
+    return with_pos(ix.pos_bytes, [&](auto p) {
+        return launch_seed(k_toehold_chkpnts_runs<pos_t<decltype(p)>>, L, stream, ix, seqs, off, N, wsize, slot_off, cnt, lo, hi, qs, qe, ss);
+    });
 }
-#undef RBG_LAUNCH_SEEDK
 
 }  // namespace rbg

@@ -14,6 +14,7 @@
 // (direct-addressed by position >> shift) that already answers the rank, and both ranks of a step
 // share that slot whenever lo and hi+1 fall in the same bucket.
 #include "rbg_device.hpp"
+#include "rbg_launch.hpp"
 
 namespace rbg {
 namespace {
@@ -420,23 +421,12 @@ int launch_find_range_impl(const DevIndex &ix, const LaunchCfg &cfg, const uint8
                            uint64_t *lo, uint64_t *hi, uint64_t *ssamp, const uint32_t *sel, const uint32_t *nsel, void *stream,
                            unsigned long long *stats = nullptr) {
     if (N == 0) return 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool toe = ssamp != nullptr;
     // sel mode: the number of reads is only known on the device; a fixed modest grid loops over it
     const int cap = sel ? 512 : 0;
-#define RBG_LAUNCH_FR(PT, TOE)                                                                                      \
-    do {                                                                                                            \
-        auto kern = k_find_range<PT, TOE, USE_FTAB, STATS>;                                                         \
-        const KmerLaunch L = kmer_launch(ix, cfg, N, kern, cap);                                                    \
-        hipLaunchKernelGGL(kern, L.grid, L.block, L.lds, st, ix, seqs, off, N, lo, hi, ssamp, sel, nsel, stats);    \
-    } while (0)
-    if (ix.pos_bytes == 4) {
-        if (toe) RBG_LAUNCH_FR(uint32_t, true); else RBG_LAUNCH_FR(uint32_t, false);
-    } else {
-        if (toe) RBG_LAUNCH_FR(uint64_t, true); else RBG_LAUNCH_FR(uint64_t, false);
-    }
-#undef RBG_LAUNCH_FR
-    return static_cast<int>(hipGetLastError());
+    return with_pos(ix.pos_bytes, [&](auto p) { return with_flag(ssamp != nullptr, [&](auto toe) {
+        return launch_kmer(k_find_range<pos_t<decltype(p)>, decltype(toe)::value, USE_FTAB, STATS>, ix, cfg, N, cap, kSearchKmerLevel, stream,
+                           ix, seqs, off, N, lo, hi, ssamp, sel, nsel, stats);
+    }); });
 }
 
 int launch_find_range_stats(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *seqs, const uint64_t *off, uint64_t N,
@@ -503,37 +493,31 @@ int launch_pack_reads(const DevIndex &ix, const LaunchCfg &cfg, const uint8_t *s
     return static_cast<int>(hipGetLastError());
 }
 
+namespace {
+int launch_packed_search(const DevIndex &ix, const LaunchCfg &cfg, const uint2 *meta, const uint4 *chunks, uint64_t N, uint64_t *lo, uint64_t *hi,
+                         uint64_t *ssamp, void *stream) {
+    return with_pos(ix.pos_bytes, [&](auto p) { return with_flag(ssamp != nullptr, [&](auto toe) {
+        return launch_kmer(k_find_range_packed<pos_t<decltype(p)>, decltype(toe)::value>, ix, cfg, N, 0, kSearchKmerLevel, stream, ix, meta, chunks, N, lo, hi, ssamp);
+    }); });
+}
+}  // namespace
+
 // the packed search alone, on a batch packed elsewhere (the host path of rbg_capi.hip packs on the CPU): flagged
 // reads (meta.y bit 31) are skipped, the caller searches them from their bytes
 int launch_find_range_packed_only(const DevIndex &ix, const LaunchCfg &cfg, const uint2 *meta, const uint4 *chunks, uint64_t N,
                                   uint64_t *lo, uint64_t *hi, uint64_t *ssamp, void *stream) {
     if (N == 0) return 0;
     if (ix.layout == 2) return launch_find_range_runs_packed(ix, cfg, meta, chunks, N, lo, hi, ssamp, stream);   // run-indexed layout (k_runs.hip)
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define RBG_LAUNCH_FRP(PT, TOE)                                                                       \
-    do {                                                                                              \
-        auto kern = k_find_range_packed<PT, TOE>;                                                     \
-        const KmerLaunch L = kmer_launch(ix, cfg, N, kern);                                           \
-        hipLaunchKernelGGL(kern, L.grid, L.block, L.lds, st, ix, meta, chunks, N, lo, hi, ssamp);     \
-    } while (0)
-    if (ix.pos_bytes == 4) {
-        if (ssamp) RBG_LAUNCH_FRP(uint32_t, true); else RBG_LAUNCH_FRP(uint32_t, false);
-    } else {
-        if (ssamp) RBG_LAUNCH_FRP(uint64_t, true); else RBG_LAUNCH_FRP(uint64_t, false);
-    }
-#undef RBG_LAUNCH_FRP
-    return static_cast<int>(hipGetLastError());
+    return launch_packed_search(ix, cfg, meta, chunks, N, lo, hi, ssamp, stream);
 }
 
 int launch_find_range_packed(const DevIndex &ix, const LaunchCfg &cfg, const void *ws, const uint8_t *seqs, const uint64_t *off,
                              uint64_t N, uint64_t total_bytes, uint64_t *lo, uint64_t *hi, uint64_t *ssamp, void *stream) {
     if (N == 0) return 0;
     const PackLayout L = pack_layout(N, total_bytes);
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const char *b = static_cast<const char *>(ws);
     const uint2 *meta = reinterpret_cast<const uint2 *>(b + L.meta);
     const uint4 *chunks = reinterpret_cast<const uint4 *>(b + L.chunks);
-    const bool toe = ssamp != nullptr;
     int rc;
     if (ix.layout == 2) {   // run-indexed layout (k_runs.hip); the flagged reads go to its byte kernel below
         rc = launch_find_range_runs_packed(ix, cfg, meta, chunks, N, lo, hi, ssamp, stream);
@@ -541,19 +525,7 @@ int launch_find_range_packed(const DevIndex &ix, const LaunchCfg &cfg, const voi
         const uint32_t *sel2 = reinterpret_cast<const uint32_t *>(b + L.sel), *nsel2 = reinterpret_cast<const uint32_t *>(b + L.nsel);
         return launch_find_range_runs_sel(ix, cfg, seqs, off, N, lo, hi, ssamp, sel2, nsel2, stream);
     }
-#define RBG_LAUNCH_FRP(PT, TOE)                                                                       \
-    do {                                                                                              \
-        auto kern = k_find_range_packed<PT, TOE>;                                                     \
-        const KmerLaunch L = kmer_launch(ix, cfg, N, kern);                                           \
-        hipLaunchKernelGGL(kern, L.grid, L.block, L.lds, st, ix, meta, chunks, N, lo, hi, ssamp);     \
-    } while (0)
-    if (ix.pos_bytes == 4) {
-        if (toe) RBG_LAUNCH_FRP(uint32_t, true); else RBG_LAUNCH_FRP(uint32_t, false);
-    } else {
-        if (toe) RBG_LAUNCH_FRP(uint64_t, true); else RBG_LAUNCH_FRP(uint64_t, false);
-    }
-#undef RBG_LAUNCH_FRP
-    rc = static_cast<int>(hipGetLastError());
+    rc = launch_packed_search(ix, cfg, meta, chunks, N, lo, hi, ssamp, stream);
     if (rc) return rc;
     // the reads the packed form cannot express (a symbol outside the major alphabet)
     const uint32_t *sel = reinterpret_cast<const uint32_t *>(b + L.sel), *nsel = reinterpret_cast<const uint32_t *>(b + L.nsel);

@@ -8,7 +8,9 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
+#include <map>
 #include <mutex>
 #include <set>
 #include <utility>
@@ -489,13 +491,14 @@ inline int grid_for(const LaunchCfg &cfg, uint64_t N) {
 // 1024-thread workgroups they drop to 4 waves per SIMD and lose more than the fifth symbol gains
 // (k_marker_seeds 47-50 -> 52 ms per 10M reads): they stage the levels up to 4.
 constexpr uint32_t kSeedKmerLevel = 4;
+constexpr uint32_t kSearchKmerLevel = 5;   // the search kernels stage every level there is
 
 struct KmerLaunch {
     dim3 grid, block;
     size_t lds;
 };
 template <typename Kernel>
-KmerLaunch kmer_launch(const DevIndex &ix, const LaunchCfg &cfg, uint64_t N, Kernel kernel, int grid_cap = 0, uint32_t max_k = 5) {
+KmerLaunch kmer_launch(const DevIndex &ix, const LaunchCfg &cfg, uint64_t N, Kernel kernel, int grid_cap = 0, uint32_t max_k = kSearchKmerLevel) {
     const bool five = ix.kmer_steps >= 5 && max_k >= 5;
     LaunchCfg c = cfg;
     if (five) { c.block_threads = 1024; c.max_blocks = cfg.max_blocks > 0 ? std::max(1, cfg.max_blocks / 4) : 256 * 8; }
@@ -516,6 +519,26 @@ KmerLaunch kmer_launch(const DevIndex &ix, const LaunchCfg &cfg, uint64_t N, Ker
             (void)hipFuncSetAttribute(key.second, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(L.lds));
     }
     return L;
+}
+
+// `bytes` = the launch's DYNAMIC LDS (what the attribute limits); `static_bytes` = the kernel's static __shared__ arrays, which count
+// towards the 48 KB a kernel gets without asking but are not part of the attribute's value
+template <typename Kernel>
+void raise_lds(Kernel kernel, size_t bytes, size_t static_bytes = 0) {
+    if (bytes + static_bytes <= 48 * 1024) return;
+    static std::mutex mu;
+    static std::map<std::pair<int, const void *>, size_t> raised;   // the largest size raised so far per (device, kernel)
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const auto key = std::make_pair(dev, reinterpret_cast<const void *>(kernel));
+    std::lock_guard<std::mutex> g(mu);
+    size_t &have = raised[key];
+    if (bytes <= have) return;
+    // (a later index on the same device may need more than the first one did: raise again, and say so when the runtime refuses --
+    //  the launch that follows would fail with an unrelated-looking error)
+    const hipError_t e = hipFuncSetAttribute(key.second, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+    if (e == hipSuccess) have = bytes;
+    else std::fprintf(stderr, "rbg: raising a kernel's dynamic LDS limit to %zu bytes failed: %s\n", bytes, hipGetErrorString(e));
 }
 
 inline int scan_in_place(uint64_t *vals, uint64_t N, void *tmp, size_t tmp_bytes, hipStream_t st) {

@@ -1,11 +1,9 @@
 // rbg_runs_device.hpp -- what the kernels of the run-indexed layout share beside the search itself (rbg_runs2_device.hpp):
-// the wave-local LDS fence, the one-off raise of a kernel's dynamic LDS limit, the step's record lookup and result.
+// the wave-local LDS fence, the step's record lookup and result.
 // (Until round 4 this file held the wave-cooperative probes of the layout's first format -- 16-lane rows, quads, 128-byte
 // bucket records; they lost every A/B to one lane per query and were retired: profiles/r04_fmt_ab.txt, DESIGN_HISTORY.md.)
 // Everything lives in an anonymous namespace: each unit gets its own inlined copy.
 #pragma once
-
-#include <map>
 
 #include "rbg_device.hpp"
 
@@ -14,25 +12,7 @@ namespace {
 
 // (wave_lds_sync -- the wave-local LDS fence -- is rbg_device.hpp's)
 
-// `bytes` = the launch's DYNAMIC LDS (what the attribute limits); `static_bytes` = the kernel's static __shared__ arrays, which count
-// towards the 48 KB a kernel gets without asking but are not part of the attribute's value
-template <typename Kernel>
-void raise_lds(Kernel kernel, size_t bytes, size_t static_bytes = 0) {
-    if (bytes + static_bytes <= 48 * 1024) return;
-    static std::mutex mu;
-    static std::map<std::pair<int, const void *>, size_t> raised;   // the largest size raised so far per (device, kernel)
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const auto key = std::make_pair(dev, reinterpret_cast<const void *>(kernel));
-    std::lock_guard<std::mutex> g(mu);
-    size_t &have = raised[key];
-    if (bytes <= have) return;
-    // (a later index on the same device may need more than the first one did: raise again, and say so when the runtime refuses --
-    //  the launch that follows would fail with an unrelated-looking error)
-    const hipError_t e = hipFuncSetAttribute(key.second, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-    if (e == hipSuccess) have = bytes;
-    else std::fprintf(stderr, "rbg: raising a kernel's dynamic LDS limit to %zu bytes failed: %s\n", bytes, hipGetErrorString(e));
-}
+// (raise_lds -- the one-off raise of a kernel's dynamic LDS limit -- is rbg_device.hpp's, beside kmer_launch)
 
 // ---- STAGE: the wave's reads as 2-bit codes in LDS, made by the wave itself -----------------------------------------------------------
 // A lane that walks its read through a cursor of 16-byte chunks fetches a chunk every second step: by then the memory system has turned its

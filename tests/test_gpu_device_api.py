@@ -301,6 +301,112 @@ def test_instrumented_kernels_and_32_bit_locations(synth, layout):
     rb8.close()
 
 
+SD_SEED_RECS, SD_SEQUENCES = 13, 14   # include/rbg.h RBG_SD_SEED_RECS, RBG_SD_SEQUENCES
+
+
+@pytest.mark.parametrize("layout,pos_bytes", [(capi.LAYOUT_SLOTS, 8), (capi.LAYOUT_RUNS, 4), (capi.LAYOUT_RUNS, 8)])
+def test_instrumented_and_packed_variants_at_both_widths(synth, layout, pos_bytes):
+    """The launchers' variants that the test above reaches at 4-byte positions only, at 8-byte ones -- the instrumented search with and
+    without a toehold, the instrumented locate, the packed search -- and the instrumented seeding walks of the run-indexed layout
+    (rbg_greedy_longest_seed_stats_dev, rbg_marker_seeds_stats_dev: what bench.py prices the seeding kernels with) at both widths: the same
+    outputs as the plain calls, which their own tests pin to the oracle, and sums that add up."""
+    import torch
+    S = synth
+    with capi.default_option(capi.OPT_POS_BYTES, pos_bytes):
+        rb = _with_layout(layout, lambda: ra.RowBowt.from_runs(S.heads, S.lens, S.ssa, S.esa, device=0))
+    assert rb.info().rank_layout == layout and rb.info().pos_bytes == pos_bytes
+    rb.set_markers(*S.markers(wsize=10))
+    reads = S.sample_reads(290, 130, seed=47, sub_rate=0.3, ragged=True) + [b"", b"ACGTN", b"A", S.text[200:330].tobytes()]
+    assert len(reads) <= 300 and max(len(q) for q in reads) <= 130
+    seqs, off = ra.pack_reads(reads)
+    N, total_syms = len(reads), int(off[-1])
+    dev = torch.device("cuda:0")
+    d_seqs = torch.from_numpy(np.concatenate([seqs, np.zeros(16 + (-len(seqs)) % 16, np.uint8)])).to(dev)
+    d_off = torch.from_numpy(off.view(np.int64)).to(dev)
+    st = torch.cuda.current_stream().cuda_stream
+    L = ra.lib()
+    same = lambda d, a: bool((d.cpu().numpy().view(np.uint64) == a).all())
+    lo, hi, k = rb.find_range_w_toehold(seqs, off)
+    assert 0 < int((hi >= lo).sum()) < N
+    d_lo, d_hi, d_k = (torch.full((N,), -3, dtype=torch.int64, device=dev) for _ in range(3))
+    d_stats = torch.zeros(16, dtype=torch.int64, device=dev)
+    for toe in (True, False):
+        d_stats.zero_(); d_lo.fill_(-3); d_hi.fill_(-3); d_k.fill_(-3)
+        assert L.rbg_find_range_stats_dev(rb.h, d_seqs.data_ptr(), d_off.data_ptr(), N, d_lo.data_ptr(), d_hi.data_ptr(),
+                                          d_k.data_ptr() if toe else None, d_stats.data_ptr(), st) == 0
+        torch.cuda.synchronize()
+        assert same(d_lo, lo) and same(d_hi, hi) and (same(d_k, k) if toe else bool((d_k == -3).all().item()))
+        steps, symbols = d_stats[0].item(), d_stats[7].item()
+        assert 0 < steps <= symbols <= total_syms
+    # the packed search, with and without a toehold
+    wsb = L.rbg_pack_ws_bytes(N, total_syms)
+    d_pws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    assert L.rbg_pack_reads_dev(rb.h, d_seqs.data_ptr(), d_off.data_ptr(), N, total_syms, d_pws.data_ptr(), wsb, st) == 0
+    d_lo.fill_(-3); d_hi.fill_(-3); d_k.fill_(-3)
+    assert L.rbg_find_range_w_toehold_packed_dev(rb.h, d_pws.data_ptr(), d_seqs.data_ptr(), d_off.data_ptr(), N, total_syms,
+                                                 d_lo.data_ptr(), d_hi.data_ptr(), d_k.data_ptr(), st) == 0
+    torch.cuda.synchronize()
+    assert same(d_lo, lo) and same(d_hi, hi) and same(d_k, k)
+    d_lo.fill_(-3); d_hi.fill_(-3)
+    assert L.rbg_find_range_packed_dev(rb.h, d_pws.data_ptr(), d_seqs.data_ptr(), d_off.data_ptr(), N, total_syms, d_lo.data_ptr(), d_hi.data_ptr(), st) == 0
+    torch.cuda.synchronize()
+    assert same(d_lo, lo) and same(d_hi, hi)
+    # the instrumented locate against the plain one and the host call
+    max_hits = 9
+    woff, wlocs = rb.locs_at(lo, hi, k, max_hits)
+    d_loc_off = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    tmp_bytes = L.rbg_locate_plan_tmp_bytes(N)
+    d_tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)
+    assert L.rbg_locate_plan_dev(rb.h, d_lo.data_ptr(), d_hi.data_ptr(), N, max_hits, d_loc_off.data_ptr(), d_tmp.data_ptr(), tmp_bytes, st) == 0
+    total = int(d_loc_off[-1].item())
+    assert total == len(wlocs) > 0
+    ws_bytes = L.rbg_locate_order_ws_bytes(N)
+    d_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    assert L.rbg_locate_order_dev(rb.h, d_k.data_ptr(), N, d_ws.data_ptr(), ws_bytes, st) == 0
+    for order in (d_ws.data_ptr(), None):
+        d_locs = torch.full((total + 1,), -1, dtype=torch.int64, device=dev)
+        d_stats.zero_()
+        assert L.rbg_locate_fill_stats_dev(rb.h, d_lo.data_ptr(), d_hi.data_ptr(), d_k.data_ptr(), N, max_hits, d_loc_off.data_ptr(), d_locs.data_ptr(),
+                                           order, d_stats.data_ptr(), st) == 0
+        torch.cuda.synchronize()
+        assert same(d_locs[:total], wlocs) and d_locs[total].item() == -1
+        phi_steps, _search, chains, nlocs = d_stats.cpu().numpy().tolist()[:4]
+        assert nlocs == total and chains == int((hi >= lo).sum()) and phi_steps == total - chains
+    # the instrumented seeding walks: the run-indexed layout's, refused on the other
+    min_length, wsize, max_range = 12, 10, 1000
+    want = rb.greedy_longest_seed(seqs, off, min_length)
+    d_g = [torch.full((N,), -3, dtype=torch.int64, device=dev) for _ in range(5)]
+    d_stats.zero_()
+    rc = L.rbg_greedy_longest_seed_stats_dev(rb.h, d_seqs.data_ptr(), d_off.data_ptr(), N, min_length, *(t.data_ptr() for t in d_g), d_stats.data_ptr(), st)
+    d_soff, d_moff, d_soff_s, d_moff_s = (torch.full((N + 1,), -1, dtype=torch.int64, device=dev) for _ in range(4))
+    assert L.rbg_marker_seeds_plan_dev(rb.h, d_seqs.data_ptr(), d_off.data_ptr(), N, wsize, max_range, 0, d_soff.data_ptr(), d_moff.data_ptr(),
+                                       d_tmp.data_ptr(), tmp_bytes, st) == 0
+    ns, nm = int(d_soff[-1].item()), int(d_moff[-1].item())
+    assert ns > 0 and nm > 0
+    d_rec, d_rec_s = (torch.full((ns * 6 + 6,), -1, dtype=torch.int64, device=dev) for _ in range(2))
+    d_mk, d_mk_s = (torch.full((nm + 1,), -1, dtype=torch.int64, device=dev) for _ in range(2))
+    assert L.rbg_marker_seeds_fill_dev(rb.h, d_seqs.data_ptr(), d_off.data_ptr(), N, wsize, max_range, 0, d_soff.data_ptr(), d_moff.data_ptr(),
+                                       d_rec.data_ptr(), d_mk.data_ptr(), st) == 0
+    d_mstats = torch.zeros(16, dtype=torch.int64, device=dev)
+    rc_m = L.rbg_marker_seeds_stats_dev(rb.h, d_seqs.data_ptr(), d_off.data_ptr(), N, wsize, max_range, d_soff_s.data_ptr(), d_moff_s.data_ptr(),
+                                        d_tmp.data_ptr(), tmp_bytes, d_rec_s.data_ptr(), d_mk_s.data_ptr(), d_mstats.data_ptr(), st)
+    torch.cuda.synchronize()
+    if layout != capi.LAYOUT_RUNS:
+        assert rc == -4 and rc_m == -4
+    else:
+        assert rc == 0 and rc_m == 0
+        for d, a in zip(d_g, want):
+            assert same(d, a)
+        sv = d_stats.cpu().numpy().tolist()
+        assert sv[SD_SEQUENCES] == N and 0 < sv[0] <= sv[7]
+        assert bool((d_soff_s == d_soff).all().item()) and bool((d_moff_s == d_moff).all().item())
+        assert bool((d_rec_s == d_rec).all().item()) and bool((d_mk_s == d_mk).all().item())
+        assert d_rec[ns * 6:].tolist() == [-1] * 6 and d_mk[nm].item() == -1 and bool((d_rec[:ns * 6] != -1).any().item())
+        mv = d_mstats.cpu().numpy().tolist()
+        assert mv[SD_SEQUENCES] == 2 * N and mv[SD_SEED_RECS] == ns   # (two walks, the count and the fill; the fill writes the records)
+    rb.close()
+
+
 def test_device_pipeline_is_graph_capturable(synth):
     """The *_dev entry points neither allocate nor synchronise: the whole count+locate step is captured
     into one HIP graph and replayed on new reads in the same buffers."""

@@ -577,3 +577,68 @@ def test_staged_read_walk_at_its_boundaries(synth, pos_bytes):
     assert int((whi >= wlo).sum()) > 800
     rb.close()
     o.close()
+
+
+@pytest.mark.parametrize("switch", [pytest.param(("RBG_REC_FETCH", "quad"), id="rec_fetch_quad"), pytest.param(("RBG_STAGE_READS", "0"), id="stage_reads_0")])
+def test_search_variants_behind_the_environment_switches(synth, switch):
+    """The two A/B switches of the run-indexed search's launcher (k_runs.hip launch_find_range_runs_impl) choose other instantiations of
+    k_find_range_runs than a default process ever launches: RBG_REC_FETCH=quad the ones that move a quad's bucket records through registers
+    (no LDS-direct loads, no staging) for the byte form, the instrumented form and the packed form; RBG_STAGE_READS=0 the LDS-direct ones
+    that walk bytes through a cursor instead of reads staged in LDS.  A switch is read once per process, so each case runs in a child.  At
+    both position widths, with and without a toehold: the host calls, the instrumented device call and the packed device calls (whose
+    reads outside the alphabet go through the `sel` launch) against the oracle (find_range / find_range_w_toehold, rowbowt.hpp:121-131, :169-184)."""
+    import subprocess
+    name, value = switch
+    if os.environ.get(name) != value:
+        r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu",
+                            f"{__file__}::test_search_variants_behind_the_environment_switches[{'rec_fetch_quad' if name == 'RBG_REC_FETCH' else 'stage_reads_0'}]"],
+                           env=dict(os.environ, **{name: value}), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0 and "1 passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+        return
+    import torch
+    S = synth
+    reads = S.sample_reads(280, 130, seed=53, sub_rate=0.3, ragged=True)
+    reads += [b"", b"A", b"N", b"ACGTN", S.text[500:630].tobytes(), S.text[40:100].tobytes()[:30] + b"N" + S.text[100:160].tobytes()[:30], S.text[:20].tobytes().lower()]
+    assert len(reads) <= 300 and max(len(q) for q in reads) <= 130
+    seqs, off = ra.pack_reads(reads)
+    N, total_syms = len(reads), int(off[-1])
+    o = orc.Oracle.from_runs(S.heads, S.lens, S.ssa, S.esa)
+    wlo, whi, wk = o.find_range_w_toehold_batch(seqs, off, nthreads=4)
+    assert 100 < int((whi >= wlo).sum()) < N
+    dev = torch.device("cuda:0")
+    d_seqs = torch.from_numpy(np.concatenate([seqs, np.zeros((-len(seqs)) % 16 + 16, np.uint8)])).to(dev)
+    d_off = torch.from_numpy(off.view(np.int64)).to(dev)
+    st = torch.cuda.current_stream().cuda_stream
+    L = ra.lib()
+    same = lambda d, a: bool((d.cpu().numpy().view(np.uint64) == a).all())
+    for pos_bytes in (4, 8):
+        with capi.default_option(capi.OPT_RANK_LAYOUT, capi.LAYOUT_RUNS), capi.default_option(capi.OPT_POS_BYTES, pos_bytes):
+            rb = ra.RowBowt.from_runs(S.heads, S.lens, S.ssa, S.esa, device=0)
+        assert rb.info().rank_layout == capi.LAYOUT_RUNS and rb.info().pos_bytes == pos_bytes
+        lo, hi, k = rb.find_range_w_toehold(seqs, off)
+        assert (lo == wlo).all() and (hi == whi).all() and (k == wk).all(), pos_bytes
+        clo, chi = rb.find_range(seqs, off)
+        assert (clo == wlo).all() and (chi == whi).all(), pos_bytes
+        d_lo, d_hi, d_k = (torch.full((N,), -3, dtype=torch.int64, device=dev) for _ in range(3))
+        d_stats = torch.zeros(16, dtype=torch.int64, device=dev)
+        for toe in (True, False):                                  # the instrumented instantiation
+            d_stats.zero_(); d_lo.fill_(-3); d_hi.fill_(-3); d_k.fill_(-3)
+            assert L.rbg_find_range_stats_dev(rb.h, d_seqs.data_ptr(), d_off.data_ptr(), N, d_lo.data_ptr(), d_hi.data_ptr(),
+                                              d_k.data_ptr() if toe else None, d_stats.data_ptr(), st) == 0
+            torch.cuda.synchronize()
+            assert same(d_lo, wlo) and same(d_hi, whi) and (same(d_k, wk) if toe else bool((d_k == -3).all().item())), (pos_bytes, toe)
+            assert 0 < d_stats[0].item() <= d_stats[7].item() <= total_syms
+        wsb = L.rbg_pack_ws_bytes(N, total_syms)                   # the packed form; the reads it cannot express go through the `sel` launch
+        d_pws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        assert L.rbg_pack_reads_dev(rb.h, d_seqs.data_ptr(), d_off.data_ptr(), N, total_syms, d_pws.data_ptr(), wsb, st) == 0
+        d_lo.fill_(-3); d_hi.fill_(-3); d_k.fill_(-3)
+        assert L.rbg_find_range_w_toehold_packed_dev(rb.h, d_pws.data_ptr(), d_seqs.data_ptr(), d_off.data_ptr(), N, total_syms,
+                                                     d_lo.data_ptr(), d_hi.data_ptr(), d_k.data_ptr(), st) == 0
+        torch.cuda.synchronize()
+        assert same(d_lo, wlo) and same(d_hi, whi) and same(d_k, wk), pos_bytes
+        d_lo.fill_(-3); d_hi.fill_(-3)
+        assert L.rbg_find_range_packed_dev(rb.h, d_pws.data_ptr(), d_seqs.data_ptr(), d_off.data_ptr(), N, total_syms, d_lo.data_ptr(), d_hi.data_ptr(), st) == 0
+        torch.cuda.synchronize()
+        assert same(d_lo, wlo) and same(d_hi, whi), pos_bytes
+        rb.close()
+    o.close()

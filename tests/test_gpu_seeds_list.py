@@ -351,3 +351,33 @@ def test_cpp_shim_seed_lists(data_dir, tmp_path, small, error_reads):
     want.append("chk " + " ".join(",".join(map(str, r)) for r in toehold_chkpnts(o, chk_read, wsize)))
     want.append("empty 0 0")
     assert p.stdout.decode().splitlines() == [w.rstrip() for w in want]
+
+
+def test_longest_seed_with_the_quad_fetch_switch(synth):
+    """RBG_GREEDY_FETCH=quad makes launch_greedy_seed_runs launch the instantiation of k_greedy_seed_runs whose first record of a step is fetched by
+    the lane's quad -- one no default process launches.  The switch is read once per process, so the case runs in a child.  rbg_greedy_longest_seed
+    at both position widths against the model: the first seed of strictly greatest length of get_seeds_greedy_w_sample's list (rowbowt.hpp:222-256,
+    :669-677)."""
+    import sys
+    if os.environ.get("RBG_GREEDY_FETCH") != "quad":
+        r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", f"{__file__}::test_longest_seed_with_the_quad_fetch_switch"],
+                           env=dict(os.environ, RBG_GREEDY_FETCH="quad"), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0 and "1 passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+        return
+    S = synth
+    o = orc.Oracle.from_runs(S.heads, S.lens, S.ssa, S.esa)
+    reads = [q for q in _synth_reads(S) if len(q) <= 130][:293] + [b"", b"AC", b"ACGTN", b"NNN", S.text[:40].tobytes().lower(), b"A", S.text[300:430].tobytes()]
+    assert len(reads) <= 300
+    seqs, off = ra.pack_reads(reads)
+    want = {ml: [longest_seed(seeds_greedy(o, q, ml)) or (1, 0, 0, 0, 0) for q in reads] for ml in (0, 5, 10, 40)}
+    assert sum(w != (1, 0, 0, 0, 0) for w in want[10]) > 100 and any(w == (1, 0, 0, 0, 0) for w in want[40])
+    for pos_bytes in (4, 8):
+        with capi.default_option(capi.OPT_POS_BYTES, pos_bytes):
+            rb = _with_layout(capi.LAYOUT_RUNS, lambda: ra.RowBowt.from_runs(S.heads, S.lens, S.ssa, S.esa, device=0))
+        assert rb.info().rank_layout == capi.LAYOUT_RUNS and rb.info().pos_bytes == pos_bytes
+        for ml, w in want.items():
+            b = rb.greedy_longest_seed(seqs, off, ml)
+            for i in range(len(reads)):
+                assert tuple(int(a[i]) for a in b) == w[i], (pos_bytes, ml, i)
+        rb.close()
+    o.close()

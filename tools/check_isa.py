@@ -8,8 +8,12 @@ amount in v71: results shifted by the contents of v0; seen as a memory fault who
 
 usage: tools/check_isa.py [files...]   (default: every k_*.hip)     exit 1 when a kernel has such a shift (scratch is listed: the slot
 layout's search kernels and rocPRIM's sorts use some by design; no kernel of the run-indexed layout may -- tests/test_capi_host.py)
+       tools/check_isa.py --names > tests/golden/kernel_set.json      the set of kernels every file instantiates (tests/test_capi_host.py
+compares it: a launcher that names a variant nobody asked for, or drops one, changes it).  After adding a kernel on purpose, regenerate.
 """
 import glob
+import hashlib
+import json
 import os
 import re
 import subprocess
@@ -67,7 +71,41 @@ def scan(files=None, workers=4):
         return dict(zip(files, ex.map(kernels_of, files)))
 
 
+def _tag(name):
+    return hashlib.sha256(name.encode()).hexdigest()[:12]
+
+
+def kernel_set(per_file):
+    """{file: {"kernels": the sorted mangled names of the project's own kernels, "library": the sorted 12-digit sha256 tags of the others' names}}
+    (the kernels rocPRIM's sorts and scans instantiate are twenty times as many, with names of a few hundred bytes each -- more than a megabyte
+    in all -- so each is on record as a tag of its name; kernel_set_diff turns a mismatch back into names)"""
+    out = {}
+    for f, ks in sorted(per_file.items()):
+        names = sorted(k[0] for k in ks)
+        out[f] = {"kernels": [n for n in names if n.startswith("_ZN3rbg")], "library": sorted(_tag(n) for n in names if not n.startswith("_ZN3rbg"))}
+    return out
+
+
+def kernel_set_diff(per_file, want):
+    """what differs between the scan and a recorded kernel_set, by name wherever the scan has the name: [] when they agree"""
+    got, out = kernel_set(per_file), []
+    for f in sorted(set(got) | set(want)):
+        g, w = got.get(f, {"kernels": [], "library": []}), want.get(f, {"kernels": [], "library": []})
+        out += [f"{f}: not on record: {n}" for n in sorted(set(g["kernels"]) - set(w["kernels"]))]
+        out += [f"{f}: on record, not instantiated: {n}" for n in sorted(set(w["kernels"]) - set(g["kernels"]))]
+        extra = set(g["library"]) - set(w["library"])
+        out += [f"{f}: library kernel not on record: {k[0]}" for k in per_file.get(f, []) if not k[0].startswith("_ZN3rbg") and _tag(k[0]) in extra]
+        out += [f"{f}: library kernel on record, not instantiated: tag {t}" for t in sorted(set(w["library"]) - set(g["library"]))]
+        if not out and (g["kernels"] != w["kernels"] or g["library"] != w["library"]):
+            out.append(f"{f}: same names, another multiplicity or order")
+    return out
+
+
 def main():
+    if sys.argv[1:2] == ["--names"]:
+        json.dump(kernel_set(scan(sys.argv[2:] or None)), sys.stdout, indent=1)
+        print()
+        return 0
     per_file = scan(sys.argv[1:] or None)
     rc = 0
     for f, ks in per_file.items():
