@@ -12,7 +12,7 @@ import orc
 import rowbowt_amd as ra
 from rowbowt_amd import capi
 
-__all__ = ["ROOT", "DEFAULT_KMER_STEPS", "split", "_check_marker_seeds", "_run_cli", "_run_rb_markers", "_random_run_index", "_lf_walk_reads", "_with_layout",
+__all__ = ["ROOT", "DEFAULT_KMER_STEPS", "split", "_check_marker_seeds", "_run_cli", "_run_rb_markers", "_random_run_index", "_random_run_index_exact", "_pin_run_end_samples", "_lf_walk_reads", "_with_layout",
            "_run_indexed_checks"]
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -76,6 +76,42 @@ def _random_run_index(rng, r, max_len, term_at=None):
     vals = (np.arange(2 * r, dtype=np.uint64) * np.uint64(stride) + rng.integers(0, stride, size=2 * r).astype(np.uint64))
     rng.shuffle(vals)
     return heads, lens, vals[:r].copy(), vals[r:].copy(), n
+
+
+def _random_run_index_exact(rng, r, n):
+    """_random_run_index with the text length set: max_len is chosen so that the lengths add up to a little below n (15/16 of it on average, five
+    standard deviations of the sum away) and the difference goes to the longest run, never the terminator's.  The samples stay distinct and below n."""
+    heads, lens, ssa, esa, n0 = _random_run_index(rng, r, 2 * n * 15 // (16 * r))
+    assert n0 < n, (n0, n)
+    t = int(np.argmax(lens))
+    assert heads[t] != 1
+    lens[t] += np.uint64(n - n0)
+    assert int(lens.sum()) == n and len(np.unique(np.concatenate([ssa, esa]))) == 2 * r and int(max(ssa.max(), esa.max())) < n
+    return heads, lens, ssa, esa, n
+
+
+def _pin_run_end_samples(rng, heads, ssa, esa, n, top=0, toeholds=None):
+    """run-end samples of a random run list moved where a test needs toeholds and locations (in place; the samples stay distinct and below n).
+    toeholds = {symbol: t}: the sample of the symbol's last run is set so that the one-symbol read of that symbol has the toehold t (LF_w_loc takes
+    samples_last of that run, rowbowt.hpp:555-573, and samples_last = the sample given - 1); top: that many further samples go to distinct random
+    values in [n - 2^15, n), the top of the position range."""
+    taken = set(ssa.tolist()) | set(esa.tolist())
+    pinned = set()
+    for c, want in (toeholds or {}).items():
+        run = int(np.flatnonzero(heads == c)[-1])
+        assert 0 <= want < n - 1 and want + 1 not in taken
+        taken.discard(int(esa[run]))
+        esa[run] = want + 1
+        taken.add(want + 1)
+        pinned.add(run)
+    for i in [i for i in rng.permutation(len(heads)).tolist() if i not in pinned and heads[i] != 1][:top]:
+        v = n - 1 - int(rng.integers(0, 1 << 15))
+        while v in taken:
+            v -= 1
+        taken.discard(int(esa[i]))
+        esa[i] = v
+        taken.add(v)
+    assert len(np.unique(np.concatenate([ssa, esa]))) == 2 * len(heads) and int(max(ssa.max(), esa.max())) < n
 
 
 def _lf_walk_reads(o, heads, lens, n, rng, count, max_len):
