@@ -418,6 +418,50 @@ int rbg_align_sam(rbg_index *, const char *seq_base, const uint64_t *seq_begin, 
                   const char *qual_base /* nullable: every QUAL is "*" */, const uint64_t *qual_begin /* lengths = seq_len */,
                   const char *name_base, const uint64_t *name_begin, const uint32_t *name_len, uint64_t N,
                   uint64_t min_length, uint64_t max_hits, uint32_t flags, const char **text, uint64_t *text_len);
+/* ---- the same lines with every seed extended LEFTWARDS through mismatches, by an LF walk ------------------------------------------------------
+ * rbg_align_sam's steps through the locate fill, then per LINE (each location of a read by itself: two haplotypes that share the seed may differ in the
+ * flank and get different NM and MD): the row of the line's occurrence is known -- line j of the range [lo, hi] is row hi - (j - 1) --, BWT[row] is the
+ * reference base left of it and LF(row) the row of the occurrence one base further left, so the left flank is read base by base from the index and compared
+ * with the read's clipped prefix.  With s the searched orientation, [a, b) the seed, offs the location's offset in its document and K = max_mismatch:
+ *     L = min(a, offs)                       never leaves the read, never crosses the document's start
+ *     score = best = 0; e = 0; nm = 0; mm = 0; r = row
+ *     for t in 0 .. L-1:
+ *         c = BWT[r]                         one of the bytes A C G T, else stop (terminator, separator, N, anything else)
+ *         x = s[a-1-t]                       bytes compared as they are: a lower-case or N read base is a mismatch
+ *         if c == x: score += 1
+ *         else: mm += 1; if mm > K: stop     the (K+1)-th mismatch is not taken
+ *               score -= 4; remember (t, c)
+ *         if score >= best: best = score; e = t + 1; nm = mm
+ *         r = LF(r, c)
+ * e is the extension (it ends on a match; trailing mismatches fall away), nm the mismatches inside it, AS = (b - a) + best.  A mapped line differs from
+ * rbg_align_sam's in POS = offs + 1 - e, CIGAR = [(a-e)S] (b-a+e)M [(m-b)S] and three tags after HI: NM:i:<nm>, MD:Z:<match counts separated by the
+ * reference base of each mismatch, over the read positions [a-e, b); it starts and ends with a number>, AS:i:<AS> -- on every mapped line, also at e = 0.
+ * Unmapped lines, FLAG, RNAME, SEQ, QUAL, NH, HI and the strand pick (the longer seed) are rbg_align_sam's.  THERE IS NO RIGHT EXTENSION: LF only goes
+ * left and the index holds no FL structure; the right flank stays soft-clipped.  Arguments, text-buffer protocol, errors and counters as rbg_align_sam;
+ * RBG_EARG also for max_mismatch > RBG_SAM_MAX_MISMATCH and for a NULL handle.  Works on replicas.  RBG_SAM_TRACE=1 prints this call's steps on a line of its own, with an
+ * `extend` column (items + walks); RBG_SAM_GRID_CAP caps its grids too. */
+#define RBG_SAM_MAX_MISMATCH 8
+int rbg_align_sam_extend(rbg_index *, const char *seq_base, const uint64_t *seq_begin, const uint32_t *seq_len,
+                         const char *qual_base /* nullable: every QUAL is "*" */, const uint64_t *qual_begin /* lengths = seq_len */,
+                         const char *name_base, const uint64_t *name_begin, const uint32_t *name_len, uint64_t N,
+                         uint64_t min_length, uint64_t max_hits, uint32_t flags, uint32_t max_mismatch, const char **text, uint64_t *text_len);
+/* The walk alone, one lane per item: item j extends leftwards from position d_item_a[j] of sequence d_item_seq[j] of the batch (d_seqs 16-byte aligned,
+ * d_off[N + 1], as the *_dev searches take it), whose base at a lies at row d_item_row[j] of the suffix array's order; it goes at most d_item_limit[j]
+ * bases (offs).  d_out[j]: ext = e, nm, score = best, steps = the bases taken (LF steps), and EVERY taken mismatch in the order met -- mis_t[k] = its t,
+ * mis_ref[k] = the reference base; the first nm of them lie inside the extension, unused entries are zero.  RBG_EARG for max_mismatch >
+ * RBG_SAM_MAX_MISMATCH (before anything runs).  The items are checked on the device -- a sequence index >= N, an a beyond its sequence, a row >= n: the
+ * item's record is zero, the others are walked -- and reported when the kernel has run: this call WAITS for `stream` and then returns RBG_EARG.  Works on
+ * replicas. */
+typedef struct rbg_extend_t {
+    uint32_t ext, nm;
+    int32_t score;
+    uint32_t steps;
+    uint32_t mis_t[8];
+    uint8_t mis_ref[8];
+} rbg_extend_t;
+int rbg_extend_left_dev(rbg_index *, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, const uint32_t *d_item_seq /* [M] */,
+                        const uint32_t *d_item_a /* [M] */, const uint64_t *d_item_row /* [M] */, const uint64_t *d_item_limit /* [M]: offs */, uint64_t M,
+                        uint32_t max_mismatch, rbg_extend_t *d_out /* [M] */, void *stream);
 /* The header that goes with those lines (host): "@HD\tVN:1.6\tSO:unsorted\n", then per document in sorted-start order "@SQ\tSN:<name>\tLN:<len>\n", then
  * pg_line as given (nullable).  len = the next sorted start - this one, for the last document rbg_info().n - its start: an UPPER BOUND of the
  * sequence's length, which includes the separators between documents and the terminator.  *text: NUL-terminated, through rbg_free_buffer.

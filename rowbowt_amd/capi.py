@@ -89,6 +89,9 @@ TALLY_INFO = ("entries", "capacity", "grows", "records", "elements", "dropped")
 TALLY_PER_READ, TALLY_DROP_SITE_CONFLICTS = 1, 2
 TALLY_READ_INFO = ("reads", "elements_seen", "lost", "site_dropped")
 DOCS_MAX = 1 << 16        # RBG_DOCS_MAX: documents a device table holds (rbg_docs_prepare)
+SAM_MAX_MISMATCH = 8      # RBG_SAM_MAX_MISMATCH: the largest budget of rbg_align_sam_extend / rbg_extend_left_dev
+# rbg_extend_t: what the left extension of one item leaves behind
+EXTEND = np.dtype([("ext", np.uint32), ("nm", np.uint32), ("score", np.int32), ("steps", np.uint32), ("mis_t", np.uint32, 8), ("mis_ref", np.uint8, 8)])
 SAM_SECONDARY = 1         # RBG_SAM_SECONDARY: rbg_align_sam also writes one line per further location, up to max_hits
 LOCATE_DOCS_MAX = 1024    # RBG_LOCATE_DOCS_MAX: documents up to which rbg_locate_doc_hits_dev runs (the table in LDS)
 DOC_NONE = 0xFFFFFFFF     # RBG_DOC_NONE: the document of a position that has none
@@ -235,6 +238,8 @@ _PROTOS = [
     ("rbg_doc_hits_locs", C.c_int, [VP, VP, VP, U64, U64, VP, VP, VP, VP, VP, VP, VP]),
     ("rbg_align_sam", C.c_int, [VP, VP, VP, VP, VP, VP, VP, VP, VP, U64, U64, U64, C.c_uint32, C.POINTER(VP), C.POINTER(U64)]),
     ("rbg_sam_header", C.c_int, [VP, C.c_char_p, C.POINTER(VP), C.POINTER(U64)]),
+    ("rbg_align_sam_extend", C.c_int, [VP, VP, VP, VP, VP, VP, VP, VP, VP, U64, U64, U64, C.c_uint32, C.c_uint32, C.POINTER(VP), C.POINTER(U64)]),
+    ("rbg_extend_left_dev", C.c_int, [VP, VP, VP, U64, VP, VP, VP, VP, U64, C.c_uint32, VP, VP]),
     ("rbg_set_default_option", C.c_int, [C.c_int, C.c_int64]),
     ("rbg_get_default_option", C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
 ]
@@ -779,9 +784,42 @@ class RowBowt:
         finally:
             self.L.rbg_release_text(self.h, text)
 
+    def align_sam_extend(self, seqs, quals, names, min_length=20, max_hits=16, secondary=False, max_mismatch=4):
+        """rbg_align_sam_extend: align_sam's lines with every seed extended leftwards through up to max_mismatch mismatches by an LF walk (POS and the left
+        clip move, NM / MD / AS follow HI on every mapped line); there is no right extension"""
+        return self._sam_lines(seqs, quals, names, min_length, max_hits, secondary, max_mismatch)
+
+    def extend_left(self, seqs, off, item_seq, item_a, item_row, item_limit, max_mismatch=4):
+        """rbg_extend_left_dev: the LF walk alone -- item j goes left from position item_a[j] of sequence item_seq[j] of the packed batch (seqs, off), whose
+        occurrence lies at row item_row[j], at most item_limit[j] bases -> a numpy array of EXTEND records.  The arrays cross to the device and back through
+        torch"""
+        import torch
+        seqs, off = np.ascontiguousarray(seqs, dtype=np.uint8), _u64(off)
+        N, M = len(off) - 1, len(item_seq)
+        pad = (-len(seqs)) % 16 + 16
+        info = self.info()
+        with torch.cuda.device(info.device):
+            dev = lambda a, t: torch.from_numpy(np.ascontiguousarray(a).view(t)).cuda()
+            d_seqs = dev(np.concatenate([seqs, np.zeros(pad, np.uint8)]), np.uint8)
+            d_off = dev(off, np.int64)
+            d_seq, d_a = dev(np.asarray(item_seq, np.uint32), np.int32), dev(np.asarray(item_a, np.uint32), np.int32)
+            d_row, d_lim = dev(_u64(item_row), np.int64), dev(_u64(item_limit), np.int64)
+            d_out = torch.full((max(M, 1) * EXTEND.itemsize,), 0xA5, dtype=torch.uint8, device="cuda")
+            st = torch.cuda.current_stream().cuda_stream
+            rc = self.L.rbg_extend_left_dev(self.h, d_seqs.data_ptr(), d_off.data_ptr(), N, d_seq.data_ptr() if M else None, d_a.data_ptr() if M else None,
+                                            d_row.data_ptr() if M else None, d_lim.data_ptr() if M else None, M, max_mismatch, d_out.data_ptr(), st)
+            torch.cuda.synchronize()
+            out = d_out.cpu().numpy()[:M * EXTEND.itemsize].view(EXTEND).copy()
+        _check(rc, "rbg_extend_left_dev")
+        return out
+
     def align_sam(self, seqs, quals, names, min_length=20, max_hits=16, secondary=False):
         """rbg_align_sam: the SAM lines of a batch of raw reads (bytes), both strands searched, written on the device.  seqs / names: lists of bytes;
         quals: a list of bytes of the reads' lengths, or None (every QUAL is "*")"""
+        return self._sam_lines(seqs, quals, names, min_length, max_hits, secondary, None)
+
+    def _sam_lines(self, seqs, quals, names, min_length, max_hits, secondary, _max_mismatch):
+        """the spans of a batch, then rbg_align_sam (_max_mismatch None) or rbg_align_sam_extend, then the text"""
         def spans(items):
             ln = np.array([len(x) for x in items], dtype=np.uint32)
             beg = np.zeros(len(items), dtype=np.uint64)
@@ -797,8 +835,13 @@ class RowBowt:
         qbuf, qbeg, _ = spans(quals) if quals is not None else (None, None, None)
         nbuf, nbeg, nlen = spans(names)
         text, n = VP(), U64()
-        _check(self.L.rbg_align_sam(self.h, sbuf, _p(sbeg), _p(slen), qbuf, _p(qbeg), nbuf, _p(nbeg), _p(nlen), len(seqs), min_length, max_hits,
-                                    SAM_SECONDARY if secondary else 0, C.byref(text), C.byref(n)), "rbg_align_sam")
+        flags = SAM_SECONDARY if secondary else 0
+        if _max_mismatch is None:
+            _check(self.L.rbg_align_sam(self.h, sbuf, _p(sbeg), _p(slen), qbuf, _p(qbeg), nbuf, _p(nbeg), _p(nlen), len(seqs), min_length, max_hits,
+                                        flags, C.byref(text), C.byref(n)), "rbg_align_sam")
+        else:
+            _check(self.L.rbg_align_sam_extend(self.h, sbuf, _p(sbeg), _p(slen), qbuf, _p(qbeg), nbuf, _p(nbeg), _p(nlen), len(seqs), min_length, max_hits,
+                                               flags, _max_mismatch, C.byref(text), C.byref(n)), "rbg_align_sam_extend")
         try:
             _check(self.L.rbg_wait_text(self.h, text), "rbg_wait_text")
             return C.string_at(text, n.value) if n.value else b""

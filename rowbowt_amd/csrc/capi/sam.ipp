@@ -1,29 +1,45 @@
-// capi/sam.ipp -- rbg_align_sam (SAM lines of a batch of raw reads, both strands, made on the device: k_sam.hip) and rbg_sam_header (host).  Part of
+// capi/sam.ipp -- rbg_align_sam (SAM lines of a batch of raw reads, both strands, made on the device: k_sam.hip), rbg_align_sam_extend (the same call with
+// every line's seed extended leftwards through mismatches by an LF walk: sam_extend.hip), rbg_extend_left_dev (that walk alone) and rbg_sam_header (host).  Part of
 // rbg_capi.hip.  The steps: the call's inputs through one pinned block (launch_copy16), k_sam_strands, launch_greedy_seed over the 2N sequences, k_sam_pick,
 // the locate plan / order / fill of seeds.ipp over the picked ranges, then k_sam.hip's plan and fill; the text leaves through the handle's pinned text
-// buffers as rbg_align_text's does (text.ipp).
+// buffers as rbg_align_text's does (text.ipp).  The extended call runs the same steps through the locate fill, then sam_extend.hip's: every line's read,
+// document and walk item, k_extend_left over the lines, the extended lengths, k_sam.hip's offsets, the extended text.
 namespace {
 // RBG_SAM_TRACE=1: where rbg_align_sam spends its time (each step synchronised), summed over the process's calls and printed at exit
 struct SamTrace {
+    const char *what;
+    bool extend;       // the extended call: one more column, the lines' LF walks
     bool on = std::getenv("RBG_SAM_TRACE") != nullptr;
     std::mutex mu;
-    double t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double t[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t calls = 0, bytes = 0;
+    // the extended call, from the lines' records: lines, lines with a clipped prefix (a > 0: the walks), bases taken, mismatches taken, lines extended at
+    // all, extended bases, lines whose left clip went to zero
+    uint64_t walks[7] = {0, 0, 0, 0, 0, 0, 0};
+    SamTrace(const char *w, bool x) : what(w), extend(x) {}
     ~SamTrace() {
-        if (on && calls)
-            std::fprintf(stderr, "rbg_align_sam: %llu calls, %.1f MB of text: copy in %.3f s, strands %.3f, search %.3f, pick %.3f, locate %.3f, text plan %.3f, "
-                                 "text fill %.3f, copy out %.3f\n", static_cast<unsigned long long>(calls), static_cast<double>(bytes) / 1e6,
-                         t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7]);
+        if (!(on && calls)) return;
+        std::fprintf(stderr, "%s: %llu calls, %.1f MB of text: copy in %.3f s, strands %.3f, search %.3f, pick %.3f, locate %.3f, ", what,
+                     static_cast<unsigned long long>(calls), static_cast<double>(bytes) / 1e6, t[0], t[1], t[2], t[3], t[4]);
+        if (extend) std::fprintf(stderr, "extend %.3f, ", t[8]);
+        std::fprintf(stderr, "text plan %.3f, text fill %.3f, copy out %.3f\n", t[5], t[6], t[7]);
+        if (extend)
+            std::fprintf(stderr, "%s walks: %llu lines, %llu with a clipped prefix, %llu LF steps, %llu of them mismatches taken (the others hit at the first "
+                                 "request), %llu lines extended by %llu bases, %llu left clips gone\n", what, static_cast<unsigned long long>(walks[0]),
+                         static_cast<unsigned long long>(walks[1]), static_cast<unsigned long long>(walks[2]), static_cast<unsigned long long>(walks[3]),
+                         static_cast<unsigned long long>(walks[4]), static_cast<unsigned long long>(walks[5]), static_cast<unsigned long long>(walks[6]));
     }
 };
-SamTrace g_sam_trace;
-}  // namespace
-extern "C" {
+SamTrace g_sam_trace("rbg_align_sam", false), g_sam_ext_trace("rbg_align_sam_extend", true);
+static_assert(sizeof(rbg_extend_t) == sizeof(SamExtend) && offsetof(rbg_extend_t, mis_t) == offsetof(SamExtend, mis_t) &&
+              offsetof(rbg_extend_t, mis_ref) == offsetof(SamExtend, mis_ref) && RBG_SAM_MAX_MISMATCH == 8, "rbg.h mirrors rbg_sam.hpp");
 
-int rbg_align_sam(rbg_index *ix, const char *seq_base, const uint64_t *seq_begin, const uint32_t *seq_len, const char *qual_base, const uint64_t *qual_begin,
-                  const char *name_base, const uint64_t *name_begin, const uint32_t *name_len, uint64_t N, uint64_t min_length, uint64_t max_hits,
-                  uint32_t flags, const char **text, uint64_t *text_len) {
-    return guarded([&]() -> int {
+// max_mismatch < 0: rbg_align_sam's lines; else the extended lines with that budget
+int align_sam_lines(rbg_index *ix, const char *seq_base, const uint64_t *seq_begin, const uint32_t *seq_len, const char *qual_base, const uint64_t *qual_begin,
+                    const char *name_base, const uint64_t *name_begin, const uint32_t *name_len, uint64_t N, uint64_t min_length, uint64_t max_hits,
+                    uint32_t flags, int max_mismatch, const char **text, uint64_t *text_len) {
+    const bool extend = max_mismatch >= 0;
+    SamTrace &g_trace = extend ? g_sam_ext_trace : g_sam_trace;
     if (!queryable(ix)) return RBG_ENODEV;
     if (flags & ~static_cast<uint32_t>(RBG_SAM_SECONDARY)) return RBG_EARG;
     if (!ix->H().has_tsa || !ix->H().has_dl) return RBG_ENOTLOADED;
@@ -45,10 +61,10 @@ int rbg_align_sam(rbg_index *ix, const char *seq_base, const uint64_t *seq_begin
     int rc = ensure_text_docs(ix);
     if (rc) return rc;
     hipStream_t st = hipStreamPerThread;
-    double lap_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double lap_t[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     auto lap_from = std::chrono::steady_clock::now();
     auto lap = [&](int slot) {
-        if (!g_sam_trace.on) return;
+        if (!g_trace.on) return;
         (void)hipStreamSynchronize(st);
         const auto now = std::chrono::steady_clock::now();
         lap_t[slot] += std::chrono::duration<double>(now - lap_from).count();
@@ -120,20 +136,57 @@ int rbg_align_sam(rbg_index *ix, const char *seq_base, const uint64_t *seq_begin
     const auto &D = ix->text_docs;
     const SamBatch B{N, E, p_lo, p_hi, p_a, p_b, drev.as<uint8_t>(), line_off, dloff.as<uint64_t>(), dlocs.as<uint64_t>(), d_seq, d_qual, d_roff, d_names, d_noff,
                      D.start, D.names, D.name_off, D.n, D.size};
-    if (launch_sam_plan(B, dws.p, ws_bytes, dbad.as<unsigned int>(), cap, st)) return RBG_ENODEV;
+    DevBuf ditem, dext;
+    if (extend) {
+        // per line 24 bytes of item {row, limit, sequence, a} and the 56-byte record; the second word of dbad is the walk's error word (never set here:
+        // the items come from the call's own arrays)
+        if ((rc = ditem.alloc(E * 24)) || (rc = dext.alloc(E * sizeof(SamExtend)))) return rc;
+        uint64_t *i_row = ditem.as<uint64_t>(), *i_lim = i_row + E;
+        uint32_t *i_seq = reinterpret_cast<uint32_t *>(i_lim + E), *i_a = i_seq + E;
+        if (launch_sam_ext_items(B, dws.p, i_seq, i_a, i_row, i_lim, dbad.as<unsigned int>(), cap, st)) return RBG_ENODEV;
+        if (launch_extend_left(ix->dev, dseq2.as<uint8_t>(), doff2.as<uint64_t>(), 2 * N, i_seq, i_a, i_row, i_lim, E, static_cast<uint32_t>(max_mismatch), dext.p,
+                               dbad.as<unsigned int>() + 1, cap, st))
+            return RBG_ENODEV;
+        lap(8);
+        if (g_trace.on) {   // the records' sums, outside every column (the clock starts again once the host copies are gone)
+            {
+            std::vector<SamExtend> hx(E);
+            std::vector<uint32_t> ha(E);
+            HIP_TRY(hipMemcpyAsync(hx.data(), dext.p, E * sizeof(SamExtend), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(ha.data(), i_a, E * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            uint64_t w[7] = {E, 0, 0, 0, 0, 0, 0};
+            for (uint64_t e = 0; e < E; ++e) {
+                w[1] += ha[e] > 0;
+                w[2] += hx[e].steps;
+                for (int j = 0; j < RBG_SAM_MAX_MISMATCH; ++j) w[3] += hx[e].mis_ref[j] != 0;
+                w[4] += hx[e].ext > 0;
+                w[5] += hx[e].ext;
+                w[6] += ha[e] > 0 && hx[e].ext == ha[e];
+            }
+            std::lock_guard<std::mutex> g(g_trace.mu);
+            for (int j = 0; j < 7; ++j) g_trace.walks[j] += w[j];
+            }
+            lap_from = std::chrono::steady_clock::now();
+        }
+        if (launch_sam_ext_len(B, dws.p, dext.p, cap, st) || launch_sam_offsets(dws.p, E, st)) return RBG_ENODEV;
+    } else if (launch_sam_plan(B, dws.p, ws_bytes, dbad.as<unsigned int>(), cap, st)) {
+        return RBG_ENODEV;
+    }
     const uint64_t *p_at = nullptr, *p_len = nullptr;
     sam_total_ptrs(dws.p, E, &p_at, &p_len);
     uint64_t last_at = 0, last_len = 0;
-    uint32_t bad = 0;
+    uint32_t bad[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(&last_at, p_at, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&last_len, p_len, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&bad, dbad.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(bad, dbad.p, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     lap(5);
-    if (bad) return RBG_EARG;   // a location before every document: rbg_resolve_offset's error, as rbg_align_text answers
+    if (extend && bad[1]) return RBG_ENODEV;   // (an item of the call's own making refused by the walk: cannot happen)
+    if (bad[0]) return RBG_EARG;   // a location before every document: rbg_resolve_offset's error, as rbg_align_text answers
     const uint64_t total = last_at + last_len;
     if ((rc = dtext.alloc(total))) return rc;
-    if (launch_sam_fill(B, dws.p, total, dtext.as<char>(), cap, st)) return RBG_ENODEV;
+    if (extend ? launch_sam_ext_fill(B, dws.p, dext.p, total, dtext.as<char>(), cap, st) : launch_sam_fill(B, dws.p, total, dtext.as<char>(), cap, st)) return RBG_ENODEV;
     lap(6);
     char *out = nullptr;
     if ((rc = take_text_out(ix, total, &out))) return rc;
@@ -149,17 +202,63 @@ int rbg_align_sam(rbg_index *ix, const char *seq_base, const uint64_t *seq_begin
         t->d_text = dtext.p; t->d_cls = dtext.cls; t->d_dev = dtext.dev;
         dtext.p = nullptr;   // (the record owns the device block until the copy has been waited for)
     }
-    if (g_sam_trace.on) {
+    if (g_trace.on) {
         (void)rbg_wait_text(ix, out);
         lap(7);
-        std::lock_guard<std::mutex> g(g_sam_trace.mu);
-        for (int j = 0; j < 8; ++j) g_sam_trace.t[j] += lap_t[j];
-        g_sam_trace.calls += 1;
-        g_sam_trace.bytes += total;
+        std::lock_guard<std::mutex> g(g_trace.mu);
+        for (int j = 0; j < 9; ++j) g_trace.t[j] += lap_t[j];
+        g_trace.calls += 1;
+        g_trace.bytes += total;
     }
     *text = out;
     *text_len = total;
     return RBG_OK;
+}
+}  // namespace
+extern "C" {
+
+int rbg_align_sam(rbg_index *ix, const char *seq_base, const uint64_t *seq_begin, const uint32_t *seq_len, const char *qual_base, const uint64_t *qual_begin,
+                  const char *name_base, const uint64_t *name_begin, const uint32_t *name_len, uint64_t N, uint64_t min_length, uint64_t max_hits,
+                  uint32_t flags, const char **text, uint64_t *text_len) {
+    return guarded([&]() -> int {
+        return align_sam_lines(ix, seq_base, seq_begin, seq_len, qual_base, qual_begin, name_base, name_begin, name_len, N, min_length, max_hits, flags, -1, text,
+                               text_len);
+    });
+}
+
+int rbg_align_sam_extend(rbg_index *ix, const char *seq_base, const uint64_t *seq_begin, const uint32_t *seq_len, const char *qual_base, const uint64_t *qual_begin,
+                         const char *name_base, const uint64_t *name_begin, const uint32_t *name_len, uint64_t N, uint64_t min_length, uint64_t max_hits,
+                         uint32_t flags, uint32_t max_mismatch, const char **text, uint64_t *text_len) {
+    return guarded([&]() -> int {
+        if (!ix || max_mismatch > RBG_SAM_MAX_MISMATCH) return RBG_EARG;   // (a null handle is an argument error here; a handle without a device: RBG_ENODEV)
+        return align_sam_lines(ix, seq_base, seq_begin, seq_len, qual_base, qual_begin, name_base, name_begin, name_len, N, min_length, max_hits, flags,
+                               static_cast<int>(max_mismatch), text, text_len);
+    });
+}
+
+int rbg_extend_left_dev(rbg_index *ix, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, const uint32_t *d_item_seq, const uint32_t *d_item_a,
+                        const uint64_t *d_item_row, const uint64_t *d_item_limit, uint64_t M, uint32_t max_mismatch, rbg_extend_t *d_out, void *stream) {
+    return guarded([&]() -> int {
+    if (!ix || max_mismatch > RBG_SAM_MAX_MISMATCH) return RBG_EARG;
+    if (!queryable(ix)) return RBG_ENODEV;
+    if (M && (!d_seqs || !d_off || !d_item_seq || !d_item_a || !d_item_row || !d_item_limit || !d_out)) return RBG_EARG;
+    if ((reinterpret_cast<uintptr_t>(d_seqs) & 15) || (reinterpret_cast<uintptr_t>(d_out) & 3)) return RBG_EARG;   // reads are fetched as aligned 16-byte chunks
+    if (M == 0) return RBG_OK;
+    DeviceScope scope(ix->device);
+    if (scope.rc) return scope.rc;
+    const uint32_t cap = [] { const char *e = std::getenv("RBG_SAM_GRID_CAP"); const long long v = e && *e ? std::atoll(e) : 0;
+                              return v > 0 && v < (1ll << 31) ? static_cast<uint32_t>(v) : 0u; }();
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    DevBuf derr;   // (released after the wait below: nothing of this call still runs on it)
+    int rc = derr.alloc(16);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(derr.p, 0, 16, st));
+    if (launch_extend_left(ix->dev, d_seqs, d_off, N, d_item_seq, d_item_a, d_item_row, d_item_limit, M, max_mismatch, d_out, derr.as<unsigned int>(), cap, st))
+        return RBG_ENODEV;
+    uint32_t err = 0;
+    HIP_TRY(hipMemcpyAsync(&err, derr.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return err ? RBG_EARG : RBG_OK;
     });
 }
 

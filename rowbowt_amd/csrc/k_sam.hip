@@ -15,36 +15,13 @@
 // Grids are capped (kSamGridCap workgroups, or the launcher's `cap` argument when it is not 0: rbg_align_sam reads RBG_SAM_GRID_CAP once per call) and every kernel strides over its work.
 #include <hipcub/hipcub.hpp>
 
-#include "rbg_device.hpp"
-#include "rbg_sam.hpp"
+#include "rbg_sam_dev.hpp"   // the batch, the parts of a line and the write body, shared with sam_extend.hip
 
 namespace rbg {
 namespace {
 
 constexpr uint32_t kSamLines = 128;        // lines per workgroup of k_sam_write (= its threads)
 constexpr uint32_t kSamLds = 48 * 1024;    // bytes of text a workgroup stages
-constexpr uint32_t kSamGridCap = 4096;     // workgroups per launch, at most
-
-struct SamArgs {
-    uint64_t N, E;                                  // reads, lines
-    const uint64_t *lo, *hi, *a, *b;                // [N] the picked seed (unmapped: lo = 1, hi = 0)
-    const uint8_t *rev;                             // [N]
-    const uint64_t *line_off, *loc_off, *locs;      // [N + 1], [N + 1], [loc_off[N]]
-    const char *seqs, *quals;                       // the reads' original bytes; quals nullable, same offsets
-    const uint64_t *roff;                           // [N + 1]
-    const char *names;
-    const uint32_t *name_off;                       // [N + 1]
-    const uint64_t *doc_start;                      // [ndocs] sorted
-    const char *doc_names;
-    const uint32_t *doc_name_off;                   // [ndocs + 1]
-    uint64_t ndocs, text_size;
-};
-
-int sam_grid(const uint64_t work, const uint32_t per_block, const uint32_t cap_arg) {
-    const uint64_t cap = cap_arg ? cap_arg : kSamGridCap;
-    const uint64_t g = (work + per_block - 1) / per_block;
-    return static_cast<int>(std::max<uint64_t>(1, std::min(g, cap)));
-}
 
 // One lane makes one aligned 16-byte piece of the output, cut where a strand ends (k_read_strands' layout; the source is read byte by byte)
 __global__ __launch_bounds__(256) void k_sam_strands(const uint8_t *__restrict__ seqs, const uint64_t *__restrict__ off, const uint64_t N,
@@ -109,39 +86,6 @@ __global__ __launch_bounds__(256) void k_sam_mark(const uint64_t *__restrict__ l
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < N; i += stride) mark[line_off[i]] = static_cast<uint32_t>(i);
 }
 
-// k_text.hip's doc_of: the number of sorted starts below min(pos + 1, size); 0: no document
-__device__ __forceinline__ uint64_t sam_doc_of(const SamArgs &s, const uint64_t pos) {
-    const uint64_t q = pos + 1 > s.text_size ? s.text_size : pos + 1;
-    uint64_t lo = 0, hi = s.ndocs;
-    while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (s.doc_start[mid] < q) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// the parts of line e of read i (d: its document, for a mapped line)
-__device__ __forceinline__ SamLine sam_line_of(const SamArgs &s, const uint64_t e, const uint64_t i, const uint32_t d) {
-    SamLine L;
-    L.name_len = s.name_off[i + 1] - s.name_off[i];
-    L.mapped = s.hi[i] >= s.lo[i];
-    L.reverse = s.rev[i] != 0;
-    L.hit = e - s.line_off[i] + 1;
-    L.occ = s.hi[i] - s.lo[i] + 1;
-    L.m = s.roff[i + 1] - s.roff[i];
-    L.a = s.a[i];
-    L.b = s.b[i];
-    L.has_qual = s.quals != nullptr;
-    L.rname_len = 0;
-    L.pos = 0;
-    if (L.mapped) {
-        const uint64_t pos = s.locs[s.loc_off[i] + (L.hit - 1)];
-        L.rname_len = s.doc_name_off[d + 1] - s.doc_name_off[d];
-        L.pos = pos - s.doc_start[d] + 1;
-    }
-    return L;
-}
-
 __global__ __launch_bounds__(256) void k_sam_len(const SamArgs s, const uint32_t *__restrict__ eread, uint64_t *__restrict__ len, uint32_t *__restrict__ doc,
                                                  unsigned int *__restrict__ bad) {
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
@@ -158,53 +102,16 @@ __global__ __launch_bounds__(256) void k_sam_len(const SamArgs s, const uint32_t
     }
 }
 
-__device__ __forceinline__ void sam_put(const SamArgs &s, const uint64_t e, const uint64_t i, const uint32_t d, char *p) {
-    const SamLine L = sam_line_of(s, e, i, d);
-    sam_put_line(p, L, s.names + s.name_off[i], s.doc_names + s.doc_name_off[d], s.seqs + s.roff[i], s.quals ? s.quals + s.roff[i] : nullptr);
-}
-
 __global__ __launch_bounds__(kSamLines) void k_sam_write(const SamArgs s, const uint32_t *__restrict__ eread, const uint32_t *__restrict__ doc,
                                                          const uint64_t *__restrict__ at, const uint64_t total, char *__restrict__ text) {
     __shared__ __align__(16) char s_buf[kSamLds + 16];
-    const uint64_t nblocks = (s.E + kSamLines - 1) / kSamLines;
-    for (uint64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
-        const uint64_t e0 = blk * kSamLines, e1 = e0 + kSamLines < s.E ? e0 + kSamLines : s.E;
-        const uint64_t t0 = at[e0], t1 = e1 < s.E ? at[e1] : total;
-        const uint64_t e = e0 + threadIdx.x;
-        const uint32_t shift = static_cast<uint32_t>((reinterpret_cast<uintptr_t>(text) + t0) & 15u);   // LDS and memory addresses congruent mod 16
-        if (t1 - t0 <= kSamLds) {
-            if (e < e1) sam_put(s, e, eread[e], doc[e], s_buf + shift + (at[e] - t0));
-            __syncthreads();
-            const uint32_t nbytes = static_cast<uint32_t>(t1 - t0);
-            char *dst = text + t0;
-            const char *src = s_buf + shift;
-            const uint32_t head = (16u - shift) & 15u;                      // bytes before the first 16-byte boundary
-            const uint32_t h = head < nbytes ? head : nbytes;
-            if (threadIdx.x < h) dst[threadIdx.x] = src[threadIdx.x];
-            const uint32_t body = (nbytes - h) >> 4;
-            for (uint32_t j = threadIdx.x; j < body; j += kSamLines)
-                reinterpret_cast<uint4 *>(dst + h)[j] = reinterpret_cast<const uint4 *>(src + h)[j];
-            const uint32_t done = h + (body << 4);
-            if (threadIdx.x < nbytes - done) dst[done + threadIdx.x] = src[done + threadIdx.x];
-            __syncthreads();
-        } else if (e < e1) {
-            sam_put(s, e, eread[e], doc[e], text + at[e]);                  // (a long name or read: straight to memory, byte by byte)
-        }
-    }
+    sam_write_lines<kSamLines, kSamLds>(s, eread, doc, at, total, text, s_buf, nullptr);
 }
 
 struct SamMaxOp {
     __device__ __forceinline__ uint32_t operator()(uint32_t x, uint32_t y) const { return x > y ? x : y; }
 };
 
-size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
-// the workspace: eread / doc (4 bytes per line), len / at (8), the scans' temporaries
-struct SamWs {
-    uint32_t *eread, *doc;
-    uint64_t *len, *at;
-    void *tmp;
-    size_t tmp_bytes;
-};
 size_t sam_scan_bytes(uint64_t E) {
     size_t s1 = 0, s2 = 0;
     (void)hipcub::DeviceScan::InclusiveScan(nullptr, s1, static_cast<uint32_t *>(nullptr), static_cast<uint32_t *>(nullptr), SamMaxOp(), static_cast<int64_t>(E ? E : 1));
@@ -212,20 +119,9 @@ size_t sam_scan_bytes(uint64_t E) {
     return std::max(s1, s2);
 }
 SamWs sam_ws_of(void *ws, uint64_t E) {
-    char *b = static_cast<char *>(ws);
-    SamWs w;
-    w.eread = reinterpret_cast<uint32_t *>(b);
-    w.doc = reinterpret_cast<uint32_t *>(b + up256(E * 4));
-    w.len = reinterpret_cast<uint64_t *>(b + 2 * up256(E * 4));
-    w.at = reinterpret_cast<uint64_t *>(b + 2 * up256(E * 4) + up256(E * 8));
-    w.tmp = b + 2 * up256(E * 4) + 2 * up256(E * 8);
+    SamWs w = sam_ws_ptrs(ws, E);
     w.tmp_bytes = up256(sam_scan_bytes(E));
     return w;
-}
-
-SamArgs sam_args(const SamBatch &B) {
-    return SamArgs{B.N, B.E, B.lo, B.hi, B.a, B.b, B.rev, B.line_off, B.loc_off, B.locs, B.seqs, B.quals, B.roff, B.names, B.name_off,
-                   B.doc_start, B.doc_names, B.doc_name_off, B.ndocs, B.text_size};
 }
 
 }  // namespace
@@ -273,6 +169,13 @@ int launch_sam_plan(const SamBatch &B, void *ws, size_t ws_bytes, unsigned int *
     e = hipcub::DeviceScan::ExclusiveSum(w.tmp, tb, w.len, w.at, static_cast<int64_t>(B.E), st);
     if (e != hipSuccess) return static_cast<int>(e);
     return static_cast<int>(hipGetLastError());
+}
+// the second half of the plan alone: every line's offset from the lengths already in the workspace (sam_extend.hip writes them with its own kernel)
+int launch_sam_offsets(void *ws, uint64_t E, void *stream) {
+    const SamWs w = sam_ws_of(ws, E);
+    size_t tb = w.tmp_bytes;
+    const hipError_t e = hipcub::DeviceScan::ExclusiveSum(w.tmp, tb, w.len, w.at, static_cast<int64_t>(E), static_cast<hipStream_t>(stream));
+    return static_cast<int>(e != hipSuccess ? e : hipGetLastError());
 }
 // where the total is: at[E - 1] + len[E - 1]
 void sam_total_ptrs(void *ws, uint64_t E, const uint64_t **last_at, const uint64_t **last_len) {

@@ -9,7 +9,8 @@
 //                      | { "<pos>/<allele> " } ) "\n"
 // --format sam (not the reference's: its -s/--sam keeps its meaning and output) writes SAM instead: the header once (rbg_sam_header), then per batch the
 // lines rbg_align_sam makes on the device -- both strands, the longer greedy seed of --min-seed-length located, soft-clipped, --max-hits secondary lines
-// with --secondary.  QUAL is "*" for a batch in which any record has no quality string (FASTA).
+// with --secondary.  QUAL is "*" for a batch in which any record has no quality string (FASTA).  --extend [--max-mismatches n] asks for rbg_align_sam_extend's
+// lines instead: every seed extended leftwards through up to n mismatches by an LF walk (no right extension); without --extend not one byte changes.
 // stderr keeps the reference's shape ("will load SA and DA", "<load_s> <query_s>").
 // Input parsing follows kseq.h semantics (name = header up to the first whitespace; FASTA or FASTQ,
 // plain or gzip; kseq_read's -2 "truncated quality string" error is reported the same way).
@@ -49,6 +50,9 @@ struct RbAlignArgs {  // rb_align.cpp:17-24
     bool format_sam = false;                       // --format sam
     uint64_t min_seed_length = 20, max_hits = 16;  // --min-seed-length, --max-hits
     bool secondary = false;                        // --secondary
+    bool extend = false;                           // --extend: every line's seed extended leftwards through mismatches (rbg_align_sam_extend)
+    uint64_t max_mismatches = 4;                   // --max-mismatches
+    bool max_mismatches_given = false;
     int device = 0;
     int gpus = 1;     // replicas: devices device .. device + gpus - 1; every batch is sharded over them
     std::vector<int> devices;  // --devices a,b,...: the replicas' devices, in shard order (overrides --gpu/--gpus)
@@ -69,6 +73,8 @@ void print_help() {  // rb_align.cpp:26-35
     fprintf(stderr, "    --min-seed-length <n>            --format sam: shortest seed that maps a read (default 20)\n");
     fprintf(stderr, "    --max-hits <n>                   --format sam --secondary: lines per read, at most (default 16)\n");
     fprintf(stderr, "    --secondary                      --format sam: also one line per further location\n");
+    fprintf(stderr, "    --extend                         --format sam: extend every seed leftwards through mismatches (POS, CIGAR, NM / MD / AS); no right extension\n");
+    fprintf(stderr, "    --max-mismatches <n>             --format sam --extend: mismatches an extension may take, 0..8 (default 4)\n");
     fprintf(stderr, "    --gpu <n>                        HIP device ordinal (default 0)\n");
     fprintf(stderr, "    --gpus <G>                       replicate the index on G devices (from --gpu on) and shard every batch over them\n");
     fprintf(stderr, "    --devices <a,b,...>              the same with an explicit device list\n");
@@ -94,6 +100,8 @@ RbAlignArgs parse_args(int argc, char **argv) {  // rb_align.cpp:37-84
                                            {"min-seed-length", required_argument, 0, 'L'},
                                            {"max-hits", required_argument, 0, 'H'},
                                            {"secondary", no_argument, 0, 'S'},
+                                           {"extend", no_argument, 0, 'X'},
+                                           {"max-mismatches", required_argument, 0, 'K'},
                                            {0, 0, 0, 0}};
     int c, long_index = 0;
     while ((c = getopt_long(argc, argv, "o:smh", long_options, &long_index)) != -1) {
@@ -121,6 +129,8 @@ RbAlignArgs parse_args(int argc, char **argv) {  // rb_align.cpp:37-84
             case 'L': args.min_seed_length = strtoull(optarg, nullptr, 10); break;
             case 'H': args.max_hits = strtoull(optarg, nullptr, 10); break;
             case 'S': args.secondary = true; break;
+            case 'X': args.extend = true; break;
+            case 'K': args.max_mismatches = strtoull(optarg, nullptr, 10); args.max_mismatches_given = true; break;
             default: print_help(); exit(1);
         }
     }
@@ -135,6 +145,9 @@ RbAlignArgs parse_args(int argc, char **argv) {  // rb_align.cpp:37-84
     if (!args.batch_given && args.sam) args.batch = 1u << 19;
     if (args.format_sam && (args.sam || args.markers)) { fprintf(stderr, "--format sam goes without -s and -m\n"); exit(1); }
     if (args.format_sam && args.min_seed_length == 0) { fprintf(stderr, "--min-seed-length must be at least 1\n"); exit(1); }
+    if (args.extend && !args.format_sam) { fprintf(stderr, "--extend goes with --format sam\n"); exit(1); }
+    if (args.max_mismatches_given && !args.extend) { fprintf(stderr, "--max-mismatches goes with --extend\n"); exit(1); }
+    if (args.max_mismatches > RBG_SAM_MAX_MISMATCH) { fprintf(stderr, "--max-mismatches must be at most %d\n", RBG_SAM_MAX_MISMATCH); exit(1); }
     if (args.gpus < 1) args.gpus = 1;
     if (args.threads < 1) args.threads = 1;
     if (args.window_mb < 1) args.window_mb = 1;
@@ -190,9 +203,16 @@ ShardError query_shard(rbg_index *ix, const RbAlignArgs &args, const BatchView &
         if (args.format_sam) {   // the whole of it in one call: the finished lines come back like -s's text
             const bool quals = b.all_have_qual();   // (of the whole batch, so that the text does not depend on how it is sharded)
             r.text_owner = ix;
-            if ((rc = rbg_align_sam(ix, b.w->base, sb, sl, quals ? b.w->base : nullptr, quals ? b.w->recs.qual_begin.data() + b.w0 + begin : nullptr, b.w->base,
-                                    b.w->recs.name_begin.data() + b.w0 + begin, b.w->recs.name_len.data() + b.w0 + begin, N, args.min_seed_length, args.max_hits,
-                                    args.secondary ? RBG_SAM_SECONDARY : 0u, &r.text, &r.text_len)))
+            const uint64_t *qb = quals ? b.w->recs.qual_begin.data() + b.w0 + begin : nullptr, *nb = b.w->recs.name_begin.data() + b.w0 + begin;
+            const uint32_t *nl = b.w->recs.name_len.data() + b.w0 + begin, flags = args.secondary ? RBG_SAM_SECONDARY : 0u;
+            if (args.extend) {
+                if ((rc = rbg_align_sam_extend(ix, b.w->base, sb, sl, quals ? b.w->base : nullptr, qb, b.w->base, nb, nl, N, args.min_seed_length, args.max_hits, flags,
+                                               static_cast<uint32_t>(args.max_mismatches), &r.text, &r.text_len)))
+                    return {rc, "rbg_align_sam_extend"};
+                return {};
+            }
+            if ((rc = rbg_align_sam(ix, b.w->base, sb, sl, quals ? b.w->base : nullptr, qb, b.w->base, nb, nl, N, args.min_seed_length, args.max_hits, flags, &r.text,
+                                    &r.text_len)))
                 return {rc, "rbg_align_sam"};
             return {};
         }

@@ -555,6 +555,18 @@ size_t sam_ws_bytes(uint64_t E);
 int launch_sam_plan(const SamBatch &B, void *ws, size_t ws_bytes, unsigned int *d_bad, uint32_t cap, void *stream);
 void sam_total_ptrs(void *ws, uint64_t E, const uint64_t **last_at, const uint64_t **last_len);
 int launch_sam_fill(const SamBatch &B, void *ws, uint64_t total, char *text, uint32_t cap, void *stream);
+int launch_sam_offsets(void *ws, uint64_t E, void *stream);   // the plan's second half alone: offsets from the lengths already in the workspace
+// the left extension of located seeds (sam_extend.hip; rbg_extend_left_dev, rbg_align_sam_extend; the rule: rbg_sam.hpp).  launch_extend_left: M items {sequence
+// of the N-sequence batch (seqs 16-byte aligned), seed start a, row, limit} -> M records of 56 bytes (rbg_sam.hpp SamExtend) at `out`; *d_err |= 1 for an item
+// whose sequence is >= N, whose a lies beyond its sequence or whose row is >= n (its record is zero).  Then rbg_align_sam_extend's three phases over the
+// workspace of sam_ws_bytes(E): every line's read, document and item; the extended lines' lengths (launch_sam_offsets follows); the text.
+int launch_extend_left(const DevIndex &ix, const uint8_t *seqs, const uint64_t *off, uint64_t N, const uint32_t *item_seq, const uint32_t *item_a,
+                       const uint64_t *item_row, const uint64_t *item_limit, uint64_t M, uint32_t max_mismatch, void *out, unsigned int *d_err, uint32_t cap,
+                       void *stream);
+int launch_sam_ext_items(const SamBatch &B, void *ws, uint32_t *item_seq, uint32_t *item_a, uint64_t *item_row, uint64_t *item_limit, unsigned int *d_bad,
+                         uint32_t cap, void *stream);
+int launch_sam_ext_len(const SamBatch &B, void *ws, const void *ext, uint32_t cap, void *stream);
+int launch_sam_ext_fill(const SamBatch &B, void *ws, const void *ext, uint64_t total, char *text, uint32_t cap, void *stream);
 // run-indexed layout from run lists already on the device (k_build.hip): the tables' directories, 8-byte samples packed to 6
 int launch_run_dirs(uint32_t pos_bytes, const void *ent, const uint64_t *first, const uint64_t *nruns, const uint64_t *doff, const uint32_t *dshift,
                     uint32_t T, uint64_t total, uint32_t *dir, void *stream);

@@ -12,6 +12,25 @@
 // when the call has no qualities.  POS is 1 + the offset of the seed's own text position in its document (nothing is subtracted for the clipped
 // bases), and the document is that of this first aligned base: a seed that runs over a document boundary is NOT detected.
 //
+// LEFT EXTENSION (rbg_align_sam_extend, rbg_extend_left_dev; sam_extend.hip walks it, one lane per line).  Inputs of one line: the searched orientation s of
+// the read (m bytes), the seed [a, b), the line's row r0 (line j of the range [lo, hi] is row hi - (j - 1)), offs = its location's offset in its document,
+// the budget K (0 <= K <= RBG_SAM_MAX_MISMATCH).
+//     L = min(a, offs)                       never leaves the read, never crosses the document's start
+//     score = best = 0; e = 0; nm = 0; mm = 0; r = r0
+//     for t in 0 .. L-1:
+//         c = BWT[r]                         one of the bytes A C G T, else stop (terminator, separator, N, anything else)
+//         x = s[a-1-t]                       bytes compared as they are: a lower-case or N read base is a mismatch
+//         if c == x: score += 1
+//         else: mm += 1; if mm > K: stop     the (K+1)-th mismatch is not taken
+//               score -= 4; remember (t, c)
+//         if score >= best: best = score; e = t + 1; nm = mm
+//         r = LF(r, c)                       the one-row range [r, r] stepped by c
+// e is the extension: it ends on a match, trailing mismatches fall away; nm counts the mismatches inside it; AS = (b - a) + best.  `steps` counts the bases
+// taken (every iteration that reaches its LF).  The record lists EVERY taken mismatch in the order met (mm of them; the first nm lie inside the extension).
+// The extended line: POS = offs + 1 - e, CIGAR [(a-e)S] (b-a+e)M [(m-b)S], and after HI:i: the tags NM:i:<nm>, MD:Z:<...> over the read positions [a-e, b)
+// (match counts separated by the reference base of each mismatch; it starts and ends with a number) and AS:i:<AS> -- on every mapped line, also at e = 0.
+// THERE IS NO RIGHT EXTENSION: LF only goes left and the index holds no FL structure; the right flank stays soft-clipped.
+//
 // HEADER.  "@HD\tVN:1.6\tSO:unsorted\n", then per document in sorted-start order "@SQ\tSN:<name>\tLN:<len>\n" with len = the next sorted start - this one,
 // and n - start for the last (n: the index's text length; 0 if the start lies beyond it).  That is an UPPER BOUND of the sequence's length: it includes
 // the separators between documents and the terminator.  Names pair with sorted starts by position, as rbg_doc_table lists them.
@@ -31,6 +50,47 @@
 namespace rbg {
 
 constexpr uint32_t kSamFlagReverse = 16, kSamFlagSecondary = 256, kSamFlagUnmapped = 4;
+
+#ifndef RBG_SAM_MAX_MISMATCH
+#define RBG_SAM_MAX_MISMATCH 8
+#endif
+// what the left extension of one line leaves behind (include/rbg.h rbg_extend_t has the same layout)
+struct SamExtend {
+    uint32_t ext, nm;                           // e, and the mismatches inside it
+    int32_t score;                              // best
+    uint32_t steps;                             // bases taken
+    uint32_t mis_t[RBG_SAM_MAX_MISMATCH];       // the taken mismatches in the order met: t ...
+    uint8_t mis_ref[RBG_SAM_MAX_MISMATCH];      // ... and the reference base c; unused entries are zero
+};
+static_assert(sizeof(SamExtend) == 56, "four words, eight words, eight bytes");
+
+RBG_SAM_HD bool sam_is_acgt(const uint32_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
+// the rule above, one base per call
+struct SamExtendWalk {
+    uint32_t L, K, t, mm, e, nm, steps;
+    int32_t score, best;
+};
+RBG_SAM_HD SamExtendWalk sam_extend_begin(const uint64_t a, const uint64_t offs, const uint32_t K) {
+    return SamExtendWalk{static_cast<uint32_t>(a < offs ? a : offs), K, 0u, 0u, 0u, 0u, 0u, 0, 0};
+}
+// c = BWT[r] (any value that is not A C G T: stop), x = s[a-1-t].  false: the walk ends here, the base is not taken.  true: the base is taken (the caller
+// steps r = LF(r, c)); *mismatch: remember (t, c) as entry mm - 1 -- t is w.t - 1 after the call
+RBG_SAM_HD bool sam_extend_take(SamExtendWalk &w, const uint32_t c, const uint32_t x, bool *mismatch) {
+    *mismatch = false;
+    if (w.t >= w.L || !sam_is_acgt(c)) return false;
+    if (c == x) {
+        w.score += 1;
+    } else {
+        if (w.mm + 1 > w.K) return false;
+        w.mm += 1;
+        w.score -= 4;
+        *mismatch = true;
+    }
+    w.t += 1;
+    w.steps += 1;
+    if (w.score >= w.best) { w.best = w.score; w.e = w.t; w.nm = w.mm; }
+    return true;
+}
 
 RBG_SAM_HD uint8_t sam_comp(const uint8_t c) {
     switch (c) {
@@ -87,10 +147,36 @@ RBG_SAM_HD uint32_t sam_flag(const SamLine &L) {
 RBG_SAM_HD uint64_t sam_seq_len(const SamLine &L) { return (L.mapped && L.hit > 1) || L.m == 0 ? 1 : L.m; }
 RBG_SAM_HD uint64_t sam_qual_len(const SamLine &L) { return (L.mapped && L.hit > 1) || L.m == 0 || !L.has_qual ? 1 : L.m; }
 constexpr uint32_t kSamUnmappedMid = 17;   // "\t4\t*\t0\t0\t*\t*\t0\t0\t"
-RBG_SAM_HD uint64_t sam_line_len(const SamLine &L) {
+// MD:Z: of an extended line: the read positions [a - e, b) from the left, u = e - 1 - t the position of the mismatch met at t
+RBG_SAM_HD uint32_t sam_md_len(const SamExtend *x, const uint64_t seed_len) {
+    uint32_t n = 0, prev = 0;
+    for (uint32_t i = x->nm; i-- > 0;) {
+        const uint32_t u = x->ext - 1 - x->mis_t[i];
+        n += sam_dec_len(u - prev) + 1;
+        prev = u + 1;
+    }
+    return n + sam_dec_len(static_cast<uint64_t>(x->ext - prev) + seed_len);
+}
+template <typename Ptr>
+RBG_SAM_HD uint32_t sam_put_md(Ptr p, const SamExtend *x, const uint64_t seed_len) {
+    uint32_t n = 0, prev = 0;
+    for (uint32_t i = x->nm; i-- > 0;) {
+        const uint32_t u = x->ext - 1 - x->mis_t[i];
+        n += sam_put_dec(p + n, u - prev);
+        p[n++] = static_cast<char>(x->mis_ref[i]);
+        prev = u + 1;
+    }
+    return n + sam_put_dec(p + n, static_cast<uint64_t>(x->ext - prev) + seed_len);
+}
+// x (nullable): the line's left extension -- POS and the clip move by x->ext, the tags NM, MD and AS follow HI (mapped lines only)
+RBG_SAM_HD uint64_t sam_line_len(const SamLine &L, const SamExtend *x = nullptr) {
     if (!L.mapped) return L.name_len + kSamUnmappedMid + sam_seq_len(L) + 1 + sam_qual_len(L) + 1;
-    return L.name_len + 1 + sam_dec_len(sam_flag(L)) + 1 + L.rname_len + 1 + sam_dec_len(L.pos) + 5 /* \t255\t */ + sam_cigar_len(L.m, L.a, L.b) +
-           7 /* \t*\t0\t0\t */ + sam_seq_len(L) + 1 + sam_qual_len(L) + 6 /* \tNH:i: */ + sam_dec_len(L.occ) + 6 /* \tHI:i: */ + sam_dec_len(L.hit) + 1;
+    const uint64_t e = x ? x->ext : 0;
+    uint64_t n = L.name_len + 1 + sam_dec_len(sam_flag(L)) + 1 + L.rname_len + 1 + sam_dec_len(L.pos - e) + 5 /* \t255\t */ + sam_cigar_len(L.m, L.a - e, L.b) +
+                 7 /* \t*\t0\t0\t */ + sam_seq_len(L) + 1 + sam_qual_len(L) + 6 /* \tNH:i: */ + sam_dec_len(L.occ) + 6 /* \tHI:i: */ + sam_dec_len(L.hit) + 1;
+    if (x) n += 6 /* \tNM:i: */ + sam_dec_len(x->nm) + 6 /* \tMD:Z: */ + sam_md_len(x, L.b - L.a) + 6 /* \tAS:i: */ +
+                sam_dec_len(L.b - L.a + static_cast<uint64_t>(x->score));
+    return n;
 }
 
 template <typename Ptr>
@@ -108,9 +194,9 @@ RBG_SAM_HD Ptr sam_put_bases(Ptr p, const char *src, const uint64_t m, const boo
     }
     return p + m;
 }
-// the sam_line_len(L) bytes of the line at p; seq / qual: the read's ORIGINAL bytes (qual unused without has_qual)
+// the sam_line_len(L, x) bytes of the line at p; seq / qual: the read's ORIGINAL bytes (qual unused without has_qual)
 template <typename Ptr>
-RBG_SAM_HD void sam_put_line(Ptr p, const SamLine &L, const char *name, const char *rname, const char *seq, const char *qual) {
+RBG_SAM_HD void sam_put_line(Ptr p, const SamLine &L, const char *name, const char *rname, const char *seq, const char *qual, const SamExtend *x = nullptr) {
     for (uint64_t j = 0; j < L.name_len; ++j) p[j] = name[j];
     p += L.name_len;
     const bool star = (L.mapped && L.hit > 1) || L.m == 0;
@@ -128,9 +214,10 @@ RBG_SAM_HD void sam_put_line(Ptr p, const SamLine &L, const char *name, const ch
     for (uint64_t j = 0; j < L.rname_len; ++j) p[j] = rname[j];
     p += L.rname_len;
     *p = '\t'; p += 1;
-    p += sam_put_dec(p, L.pos);
+    const uint64_t e = x ? x->ext : 0;
+    p += sam_put_dec(p, L.pos - e);
     p = sam_put_lit(p, "\t255\t", 5);
-    p += sam_put_cigar(p, L.m, L.a, L.b);
+    p += sam_put_cigar(p, L.m, L.a - e, L.b);
     p = sam_put_lit(p, "\t*\t0\t0\t", 7);
     p = sam_put_bases(p, seq, L.m, star, L.reverse, L.reverse);
     *p = '\t'; p += 1;
@@ -139,6 +226,14 @@ RBG_SAM_HD void sam_put_line(Ptr p, const SamLine &L, const char *name, const ch
     p += sam_put_dec(p, L.occ);
     p = sam_put_lit(p, "\tHI:i:", 6);
     p += sam_put_dec(p, L.hit);
+    if (x) {
+        p = sam_put_lit(p, "\tNM:i:", 6);
+        p += sam_put_dec(p, x->nm);
+        p = sam_put_lit(p, "\tMD:Z:", 6);
+        p += sam_put_md(p, x, L.b - L.a);
+        p = sam_put_lit(p, "\tAS:i:", 6);
+        p += sam_put_dec(p, L.b - L.a + static_cast<uint64_t>(x->score));
+    }
     *p = '\n';
 }
 

@@ -211,6 +211,18 @@ class RowBowt {
     // as one string; quals: a quality string per read of the read's length, or empty for QUAL "*"; names: one per read
     std::string align_sam(const std::vector<std::string> &seqs, const std::vector<std::string> &quals, const std::vector<std::string> &names,
                           uint64_t min_length = 20, uint64_t max_hits = 16, bool secondary = false) const {
+        return sam_lines(seqs, quals, names, min_length, max_hits, secondary, -1);
+    }
+    // the same lines with every seed extended leftwards through up to max_mismatch mismatches by an LF walk (rbg_align_sam_extend: POS and the left clip move,
+    // NM / MD / AS follow HI on every mapped line; there is no right extension)
+    std::string align_sam_extend(const std::vector<std::string> &seqs, const std::vector<std::string> &quals, const std::vector<std::string> &names,
+                                 uint64_t min_length = 20, uint64_t max_hits = 16, bool secondary = false, uint32_t max_mismatch = 4) const {
+        return sam_lines(seqs, quals, names, min_length, max_hits, secondary, static_cast<int>(max_mismatch > 0x7FFFFFFFu ? 0x7FFFFFFFu : max_mismatch));
+    }
+
+  private:
+    std::string sam_lines(const std::vector<std::string> &seqs, const std::vector<std::string> &quals, const std::vector<std::string> &names, uint64_t min_length,
+                          uint64_t max_hits, bool secondary, int max_mismatch /* < 0: rbg_align_sam */) const {
         const uint64_t N = seqs.size();
         if (names.size() != N || (!quals.empty() && quals.size() != N)) detail::die("align_sam: a name (and a quality string, if any) per read", RBG_EARG);
         std::string sblob, qblob, nblob;
@@ -224,14 +236,21 @@ class RowBowt {
         }
         const char *text = nullptr;
         uint64_t n = 0;
-        detail::check(rbg_align_sam(ix_.get(), sblob.data(), sbeg.data(), slen.data(), quals.empty() ? nullptr : qblob.data(), sbeg.data(), nblob.data(),
-                                    nbeg.data(), nlen.data(), N, min_length, max_hits, secondary ? RBG_SAM_SECONDARY : 0u, &text, &n), "rbg_align_sam");
+        if (max_mismatch < 0)
+            detail::check(rbg_align_sam(ix_.get(), sblob.data(), sbeg.data(), slen.data(), quals.empty() ? nullptr : qblob.data(), sbeg.data(), nblob.data(),
+                                        nbeg.data(), nlen.data(), N, min_length, max_hits, secondary ? RBG_SAM_SECONDARY : 0u, &text, &n), "rbg_align_sam");
+        else
+            detail::check(rbg_align_sam_extend(ix_.get(), sblob.data(), sbeg.data(), slen.data(), quals.empty() ? nullptr : qblob.data(), sbeg.data(), nblob.data(),
+                                               nbeg.data(), nlen.data(), N, min_length, max_hits, secondary ? RBG_SAM_SECONDARY : 0u,
+                                               static_cast<uint32_t>(max_mismatch), &text, &n), "rbg_align_sam_extend");
         const int rc = rbg_wait_text(ix_.get(), text);
         std::string out = rc == RBG_OK && n ? std::string(text, n) : std::string();
         (void)rbg_release_text(ix_.get(), text);
         detail::check(rc, "rbg_wait_text");
         return out;
     }
+
+  public:
     std::string align_sam(const std::vector<std::string> &seqs, const std::vector<std::string> &names) const { return align_sam(seqs, {}, names); }
     // the header that goes with those lines (rbg_sam_header): @HD, one @SQ per document, then pg_line as given
     std::string sam_header(const std::string &pg_line = std::string()) const {
