@@ -462,6 +462,51 @@ typedef struct rbg_extend_t {
 int rbg_extend_left_dev(rbg_index *, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, const uint32_t *d_item_seq /* [M] */,
                         const uint32_t *d_item_a /* [M] */, const uint64_t *d_item_row /* [M] */, const uint64_t *d_item_limit /* [M]: offs */, uint64_t M,
                         uint32_t max_mismatch, rbg_extend_t *d_out /* [M] */, void *stream);
+/* ---- the FL index, and the same lines extended on BOTH sides -----------------------------------------------------------------------------------
+ * FL(i) = select_c(BWT, i - F[c]) is the inverse of LF: from the row of the suffix at text position p it gives T[p] -- the row's F symbol c -- and the row of
+ * the suffix at p + 1.  rbg_fl_prepare builds it from the handle's run heads and run starts and uploads it to THIS handle's device (rbg_fl.hpp): per base of
+ * A C G T the c-runs of the BWT in BWT order as {symbols of c before the run, BWT position of its start} (2 x 4 bytes at 4-byte positions, else 2 x 8) with a
+ * closing sentinel, and a directory over rank, dir[k >> shift] = the run that holds rank (k >> shift) << shift, shift = max(0, floor(log2(n_c / runs_c))), of
+ * (n_c >> shift) + 2 entries of the position width.  Its bytes: the sum over the bases present of (runs_c + 1) * 2 * pos_bytes + ((n_c >> shift) + 2) *
+ * pos_bytes -- proportional to r.  Opt-in: no load builds it.  Idempotent; the allocation counts in rbg_info's hbm_bytes.  Per handle: a replica prepares
+ * its own copy (from its root's host arrays).  RBG_ENOTLOADED when the host run arrays are not there.  It must not overlap queries on the handle.
+ * rbg_fl_info: out[0] = prepared (0 / 1), out[1] = the structure's bytes on the device (the formula above), out[2 .. 5] = the runs of A C G T, out[6] =
+ * their shifts, 8 bits each (A in the lowest), out[7] = the directory entries of all four.  Every *_dev call below and rbg_align_sam_extend_both answer
+ * RBG_ENOTLOADED until the handle has been prepared. */
+int rbg_fl_prepare(rbg_index *);
+int rbg_fl_info(const rbg_index *, uint64_t out[8]);
+/* FL of M rows, one lane per row: d_sym[j] = the F byte of row d_rows[j] when it is one of A C G T, else 0 (terminator, separator, N, anything else);
+ * d_next[j] = FL(row), 2^64 - 1 when there is no base.  A row >= n gives sym 0 and next 0 and is reported when the kernel has run: the call WAITS for `stream`
+ * and returns RBG_EARG (the other rows are answered).  RBG_SAM_GRID_CAP caps the grid. */
+int rbg_fl_dev(rbg_index *, const uint64_t *d_rows, uint64_t M, uint8_t *d_sym, uint64_t *d_next, void *stream);
+/* The right walk alone, one lane per item: item j extends rightwards from position d_item_b[j] (the seed's end) of sequence d_item_seq[j] of the batch (d_seqs
+ * 16-byte aligned, d_off[N + 1]); d_item_row[j] is the row of the suffix at which the walk starts and d_item_skip[j] the FL steps it first takes without comparing
+ * -- from the row of the seed's first base, skip = b - a crosses the seed; a row without a base on the way ends the item with a zero record (no error).  Then,
+ * with s the sequence, m its length and K = max_mismatch:
+ *     L = min(m - b, limit); score = best = 0; e = 0; nm = 0; mm = 0
+ *     for t in 0 .. L-1:
+ *         c = the F symbol of r                one of the bytes A C G T, else stop
+ *         x = s[b + t]                         bytes compared as they are
+ *         if c == x: score += 1
+ *         else: mm += 1; if mm > K: stop; score -= 4; remember (t, c)
+ *         if score >= best: best = score; e = t + 1; nm = mm
+ *         r = FL(r)
+ * d_out[j] as rbg_extend_left_dev's record with t counted rightwards from b; `steps` counts the compared bases only.  Item errors (the record is zero, the
+ * others are walked, RBG_EARG after the kernel has run): a sequence index >= N, a b beyond its sequence, skip > b, a row >= n.  Works on prepared replicas. */
+int rbg_extend_right_dev(rbg_index *, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N, const uint32_t *d_item_seq /* [M] */,
+                         const uint32_t *d_item_b /* [M] */, const uint64_t *d_item_row /* [M] */, const uint32_t *d_item_skip /* [M] */,
+                         const uint64_t *d_item_limit /* [M] */, uint64_t M, uint32_t max_mismatch, rbg_extend_t *d_out /* [M] */, void *stream);
+/* rbg_align_sam_extend through its left walk, unchanged, then per LINE that has a right clip (m > b; other lines make no item and cost no walk) the right walk
+ * above with row = the line's own row, skip = b - a, limit = doc_end - (location + (b - a)) -- doc_end the next sorted document start, n for the last
+ * document -- and the budget K - nmL, so a line's NM never exceeds max_mismatch.  The line: POS as rbg_align_sam_extend gives it, CIGAR = [(a-eL)S]
+ * (b-a+eL+eR)M [(m-b-eR)S], NM = nmL + nmR, MD over the read positions [a-eL, b+eR) (left part, seed, right part), AS = (b-a) + bestL + bestR.  A line
+ * without a right clip is rbg_align_sam_extend's line.  Unchanged: the strand pick (the longer SEED, not the longer alignment), and a seed that spans a
+ * document boundary stays undetected (nothing is walked right of it).  Arguments, text-buffer protocol, errors and counters as rbg_align_sam_extend;
+ * RBG_ENOTLOADED without rbg_fl_prepare on this handle.  RBG_SAM_TRACE=1 prints a line of its own with an `extend right` column and the walks' sums. */
+int rbg_align_sam_extend_both(rbg_index *, const char *seq_base, const uint64_t *seq_begin, const uint32_t *seq_len,
+                              const char *qual_base /* nullable */, const uint64_t *qual_begin, const char *name_base, const uint64_t *name_begin,
+                              const uint32_t *name_len, uint64_t N, uint64_t min_length, uint64_t max_hits, uint32_t flags, uint32_t max_mismatch,
+                              const char **text, uint64_t *text_len);
 /* The header that goes with those lines (host): "@HD\tVN:1.6\tSO:unsorted\n", then per document in sorted-start order "@SQ\tSN:<name>\tLN:<len>\n", then
  * pg_line as given (nullable).  len = the next sorted start - this one, for the last document rbg_info().n - its start: an UPPER BOUND of the
  * sequence's length, which includes the separators between documents and the terminator.  *text: NUL-terminated, through rbg_free_buffer.

@@ -240,6 +240,11 @@ _PROTOS = [
     ("rbg_sam_header", C.c_int, [VP, C.c_char_p, C.POINTER(VP), C.POINTER(U64)]),
     ("rbg_align_sam_extend", C.c_int, [VP, VP, VP, VP, VP, VP, VP, VP, VP, U64, U64, U64, C.c_uint32, C.c_uint32, C.POINTER(VP), C.POINTER(U64)]),
     ("rbg_extend_left_dev", C.c_int, [VP, VP, VP, U64, VP, VP, VP, VP, U64, C.c_uint32, VP, VP]),
+    ("rbg_fl_prepare", C.c_int, [VP]),
+    ("rbg_fl_info", C.c_int, [VP, VP]),
+    ("rbg_fl_dev", C.c_int, [VP, VP, U64, VP, VP, VP]),
+    ("rbg_extend_right_dev", C.c_int, [VP, VP, VP, U64, VP, VP, VP, VP, VP, U64, C.c_uint32, VP, VP]),
+    ("rbg_align_sam_extend_both", C.c_int, [VP, VP, VP, VP, VP, VP, VP, VP, VP, U64, U64, U64, C.c_uint32, C.c_uint32, C.POINTER(VP), C.POINTER(U64)]),
     ("rbg_set_default_option", C.c_int, [C.c_int, C.c_int64]),
     ("rbg_get_default_option", C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
 ]
@@ -784,10 +789,59 @@ class RowBowt:
         finally:
             self.L.rbg_release_text(self.h, text)
 
-    def align_sam_extend(self, seqs, quals, names, min_length=20, max_hits=16, secondary=False, max_mismatch=4):
+    def align_sam_extend(self, seqs, quals, names, min_length=20, max_hits=16, secondary=False, max_mismatch=4, right=False):
         """rbg_align_sam_extend: align_sam's lines with every seed extended leftwards through up to max_mismatch mismatches by an LF walk (POS and the left
-        clip move, NM / MD / AS follow HI on every mapped line); there is no right extension"""
-        return self._sam_lines(seqs, quals, names, min_length, max_hits, secondary, max_mismatch)
+        clip move, NM / MD / AS follow HI on every mapped line); right=True: rbg_align_sam_extend_both, the right clip extended too by an FL walk with what
+        the left walk left of the budget (fl_prepare first)"""
+        return self._sam_lines(seqs, quals, names, min_length, max_hits, secondary, max_mismatch, right)
+
+    def fl_prepare(self):
+        """rbg_fl_prepare: the FL index (per-base run lists keyed by rank, and their directories) on this handle's device; idempotent, opt-in"""
+        _check(self.L.rbg_fl_prepare(self.h), "rbg_fl_prepare")
+
+    def fl_info(self):
+        """rbg_fl_info -> dict: prepared, bytes, runs (A C G T), shift (A C G T), dir_entries"""
+        out = np.zeros(8, np.uint64)
+        _check(self.L.rbg_fl_info(self.h, _p(out)), "rbg_fl_info")
+        return dict(prepared=bool(out[0]), bytes=int(out[1]), runs=[int(v) for v in out[2:6]], shift=[(int(out[6]) >> (8 * j)) & 0xFF for j in range(4)],
+                    dir_entries=int(out[7]))
+
+    def fl(self, rows):
+        """rbg_fl_dev: (sym uint8[M], next uint64[M]) -- the F byte of each row (0: not one of A C G T) and FL(row) (2^64 - 1 then).  Through torch"""
+        import torch
+        rows = _u64(rows)
+        M = len(rows)
+        with torch.cuda.device(self.info().device):
+            d_rows = torch.from_numpy(rows.view(np.int64)).cuda()
+            d_sym = torch.full((max(M, 1),), 0xA5, dtype=torch.uint8, device="cuda")
+            d_next = torch.full((max(M, 1),), -6, dtype=torch.int64, device="cuda")
+            rc = self.L.rbg_fl_dev(self.h, d_rows.data_ptr() if M else None, M, d_sym.data_ptr(), d_next.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            sym, nxt = d_sym.cpu().numpy()[:M].copy(), d_next.cpu().numpy()[:M].view(np.uint64).copy()
+        _check(rc, "rbg_fl_dev")
+        return sym, nxt
+
+    def extend_right(self, seqs, off, item_seq, item_b, item_row, item_skip, item_limit, max_mismatch=4):
+        """rbg_extend_right_dev: the FL walk alone -- item j takes item_skip[j] FL steps from row item_row[j], then goes right from position item_b[j] of
+        sequence item_seq[j] of the packed batch (seqs, off), at most item_limit[j] bases -> a numpy array of EXTEND records.  Through torch"""
+        import torch
+        seqs, off = np.ascontiguousarray(seqs, dtype=np.uint8), _u64(off)
+        N, M = len(off) - 1, len(item_seq)
+        pad = (-len(seqs)) % 16 + 16
+        with torch.cuda.device(self.info().device):
+            dev = lambda a, t: torch.from_numpy(np.ascontiguousarray(a).view(t)).cuda()
+            d_seqs = dev(np.concatenate([seqs, np.zeros(pad, np.uint8)]), np.uint8)
+            d_off = dev(off, np.int64)
+            d_seq, d_b, d_skip = (dev(np.asarray(a, np.uint32), np.int32) for a in (item_seq, item_b, item_skip))
+            d_row, d_lim = dev(_u64(item_row), np.int64), dev(_u64(item_limit), np.int64)
+            d_out = torch.full((max(M, 1) * EXTEND.itemsize,), 0xA5, dtype=torch.uint8, device="cuda")
+            ptr = lambda t: t.data_ptr() if M else None
+            rc = self.L.rbg_extend_right_dev(self.h, d_seqs.data_ptr(), d_off.data_ptr(), N, ptr(d_seq), ptr(d_b), ptr(d_row), ptr(d_skip), ptr(d_lim), M,
+                                             max_mismatch, d_out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            out = d_out.cpu().numpy()[:M * EXTEND.itemsize].view(EXTEND).copy()
+        _check(rc, "rbg_extend_right_dev")
+        return out
 
     def extend_left(self, seqs, off, item_seq, item_a, item_row, item_limit, max_mismatch=4):
         """rbg_extend_left_dev: the LF walk alone -- item j goes left from position item_a[j] of sequence item_seq[j] of the packed batch (seqs, off), whose
@@ -818,8 +872,8 @@ class RowBowt:
         quals: a list of bytes of the reads' lengths, or None (every QUAL is "*")"""
         return self._sam_lines(seqs, quals, names, min_length, max_hits, secondary, None)
 
-    def _sam_lines(self, seqs, quals, names, min_length, max_hits, secondary, _max_mismatch):
-        """the spans of a batch, then rbg_align_sam (_max_mismatch None) or rbg_align_sam_extend, then the text"""
+    def _sam_lines(self, seqs, quals, names, min_length, max_hits, secondary, _max_mismatch, _right=False):
+        """the spans of a batch, then rbg_align_sam (_max_mismatch None), rbg_align_sam_extend or rbg_align_sam_extend_both (_right), then the text"""
         def spans(items):
             ln = np.array([len(x) for x in items], dtype=np.uint32)
             beg = np.zeros(len(items), dtype=np.uint64)
@@ -839,6 +893,9 @@ class RowBowt:
         if _max_mismatch is None:
             _check(self.L.rbg_align_sam(self.h, sbuf, _p(sbeg), _p(slen), qbuf, _p(qbeg), nbuf, _p(nbeg), _p(nlen), len(seqs), min_length, max_hits,
                                         flags, C.byref(text), C.byref(n)), "rbg_align_sam")
+        elif _right:
+            _check(self.L.rbg_align_sam_extend_both(self.h, sbuf, _p(sbeg), _p(slen), qbuf, _p(qbeg), nbuf, _p(nbeg), _p(nlen), len(seqs), min_length, max_hits,
+                                                    flags, _max_mismatch, C.byref(text), C.byref(n)), "rbg_align_sam_extend_both")
         else:
             _check(self.L.rbg_align_sam_extend(self.h, sbuf, _p(sbeg), _p(slen), qbuf, _p(qbeg), nbuf, _p(nbeg), _p(nlen), len(seqs), min_length, max_hits,
                                                flags, _max_mismatch, C.byref(text), C.byref(n)), "rbg_align_sam_extend")

@@ -87,7 +87,10 @@ struct rbg_index {
     // (which counts docs_gen up on the root) makes every handle's copy stale, and the *_dev calls answer RBG_ENOTLOADED until the next prepare
     struct DocDev { const uint64_t *sorted = nullptr; const uint32_t *dir = nullptr; uint64_t size = 0, gen = 0; uint32_t ndocs = 0, shift = 0, ndir = 0; } doc_dev;
     uint64_t docs_gen = 0;
-    std::mutex mu;               // guards marker/doc attachment only; queries are lock-free
+    // rbg_fl_prepare: the FL index (rbg_fl.hpp) on THIS handle's device, one allocation of its own (also in `allocs`).  Per handle and not in DevIndex, like
+    // doc_dev: a replica prepares its own copy from the root's host run arrays, which never change after the load
+    struct FlDev { void *blob = nullptr; FlView view{}; uint64_t bytes = 0, runs[kFlBases] = {}, dir_entries = 0; double build_ms = 0.0; } fl_dev;
+    std::mutex mu;              // guards marker/doc attachment only; queries are lock-free
 };
 
 namespace {

@@ -3,44 +3,58 @@
 // rbg_capi.hip.  The steps: the call's inputs through one pinned block (launch_copy16), k_sam_strands, launch_greedy_seed over the 2N sequences, k_sam_pick,
 // the locate plan / order / fill of seeds.ipp over the picked ranges, then k_sam.hip's plan and fill; the text leaves through the handle's pinned text
 // buffers as rbg_align_text's does (text.ipp).  The extended call runs the same steps through the locate fill, then sam_extend.hip's: every line's read,
-// document and walk item, k_extend_left over the lines, the extended lengths, k_sam.hip's offsets, the extended text.
+// document and walk item, k_extend_left over the lines, the extended lengths, k_sam.hip's offsets, the extended text.  rbg_align_sam_extend_both adds, behind
+// the left walks, fl_extend.hip's right items and k_extend_right over the lines with a right clip (the handle's FL index: capi/fl.ipp), and takes the lengths
+// and the text from the kernels that format both records.
 namespace {
 // RBG_SAM_TRACE=1: where rbg_align_sam spends its time (each step synchronised), summed over the process's calls and printed at exit
 struct SamTrace {
     const char *what;
     bool extend;       // the extended call: one more column, the lines' LF walks
+    bool right = false;   // rbg_align_sam_extend_both: a further column, the lines' FL walks
     bool on = std::getenv("RBG_SAM_TRACE") != nullptr;
     std::mutex mu;
-    double t[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double t[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t calls = 0, bytes = 0;
     // the extended call, from the lines' records: lines, lines with a clipped prefix (a > 0: the walks), bases taken, mismatches taken, lines extended at
     // all, extended bases, lines whose left clip went to zero
     uint64_t walks[7] = {0, 0, 0, 0, 0, 0, 0};
-    SamTrace(const char *w, bool x) : what(w), extend(x) {}
+    // the call extended on both sides, from the right records: lines with a right clip, lines walked (an item), FL steps that cross seeds, FL steps compared,
+    // mismatches taken, lines extended at all, extended bases, right clips gone
+    uint64_t rwalks[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    SamTrace(const char *w, bool x, bool r = false) : what(w), extend(x), right(r) {}
     ~SamTrace() {
         if (!(on && calls)) return;
         std::fprintf(stderr, "%s: %llu calls, %.1f MB of text: copy in %.3f s, strands %.3f, search %.3f, pick %.3f, locate %.3f, ", what,
                      static_cast<unsigned long long>(calls), static_cast<double>(bytes) / 1e6, t[0], t[1], t[2], t[3], t[4]);
         if (extend) std::fprintf(stderr, "extend %.3f, ", t[8]);
+        if (right) std::fprintf(stderr, "extend right %.3f, ", t[9]);
         std::fprintf(stderr, "text plan %.3f, text fill %.3f, copy out %.3f\n", t[5], t[6], t[7]);
         if (extend)
             std::fprintf(stderr, "%s walks: %llu lines, %llu with a clipped prefix, %llu LF steps, %llu of them mismatches taken (the others hit at the first "
                                  "request), %llu lines extended by %llu bases, %llu left clips gone\n", what, static_cast<unsigned long long>(walks[0]),
                          static_cast<unsigned long long>(walks[1]), static_cast<unsigned long long>(walks[2]), static_cast<unsigned long long>(walks[3]),
                          static_cast<unsigned long long>(walks[4]), static_cast<unsigned long long>(walks[5]), static_cast<unsigned long long>(walks[6]));
+        if (right)
+            std::fprintf(stderr, "%s right walks: %llu lines, %llu walked (a right clip inside the document), %llu FL steps across seeds, %llu FL steps compared, %llu of them "
+                                 "mismatches taken, %llu lines extended by %llu bases, %llu right clips gone\n", what, static_cast<unsigned long long>(rwalks[0]),
+                         static_cast<unsigned long long>(rwalks[1]), static_cast<unsigned long long>(rwalks[2]), static_cast<unsigned long long>(rwalks[3]),
+                         static_cast<unsigned long long>(rwalks[4]), static_cast<unsigned long long>(rwalks[5]), static_cast<unsigned long long>(rwalks[6]),
+                         static_cast<unsigned long long>(rwalks[7]));
     }
 };
-SamTrace g_sam_trace("rbg_align_sam", false), g_sam_ext_trace("rbg_align_sam_extend", true);
+SamTrace g_sam_trace("rbg_align_sam", false), g_sam_ext_trace("rbg_align_sam_extend", true), g_sam_both_trace("rbg_align_sam_extend_both", true, true);
 static_assert(sizeof(rbg_extend_t) == sizeof(SamExtend) && offsetof(rbg_extend_t, mis_t) == offsetof(SamExtend, mis_t) &&
               offsetof(rbg_extend_t, mis_ref) == offsetof(SamExtend, mis_ref) && RBG_SAM_MAX_MISMATCH == 8, "rbg.h mirrors rbg_sam.hpp");
 
-// max_mismatch < 0: rbg_align_sam's lines; else the extended lines with that budget
+// max_mismatch < 0: rbg_align_sam's lines; else the extended lines with that budget, `right`: on both sides (the handle's FL index must be prepared)
 int align_sam_lines(rbg_index *ix, const char *seq_base, const uint64_t *seq_begin, const uint32_t *seq_len, const char *qual_base, const uint64_t *qual_begin,
                     const char *name_base, const uint64_t *name_begin, const uint32_t *name_len, uint64_t N, uint64_t min_length, uint64_t max_hits,
-                    uint32_t flags, int max_mismatch, const char **text, uint64_t *text_len) {
+                    uint32_t flags, int max_mismatch, bool right, const char **text, uint64_t *text_len) {
     const bool extend = max_mismatch >= 0;
-    SamTrace &g_trace = extend ? g_sam_ext_trace : g_sam_trace;
+    SamTrace &g_trace = right ? g_sam_both_trace : extend ? g_sam_ext_trace : g_sam_trace;
     if (!queryable(ix)) return RBG_ENODEV;
+    if (right && !fl_ready(ix)) return RBG_ENOTLOADED;
     if (flags & ~static_cast<uint32_t>(RBG_SAM_SECONDARY)) return RBG_EARG;
     if (!ix->H().has_tsa || !ix->H().has_dl) return RBG_ENOTLOADED;
     if (min_length == 0) return RBG_EARG;   // (a zero-length seed has the full range)
@@ -61,7 +75,7 @@ int align_sam_lines(rbg_index *ix, const char *seq_base, const uint64_t *seq_beg
     int rc = ensure_text_docs(ix);
     if (rc) return rc;
     hipStream_t st = hipStreamPerThread;
-    double lap_t[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double lap_t[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     auto lap_from = std::chrono::steady_clock::now();
     auto lap = [&](int slot) {
         if (!g_trace.on) return;
@@ -136,7 +150,7 @@ int align_sam_lines(rbg_index *ix, const char *seq_base, const uint64_t *seq_beg
     const auto &D = ix->text_docs;
     const SamBatch B{N, E, p_lo, p_hi, p_a, p_b, drev.as<uint8_t>(), line_off, dloff.as<uint64_t>(), dlocs.as<uint64_t>(), d_seq, d_qual, d_roff, d_names, d_noff,
                      D.start, D.names, D.name_off, D.n, D.size};
-    DevBuf ditem, dext;
+    DevBuf ditem, dext, dritem, drext;
     if (extend) {
         // per line 24 bytes of item {row, limit, sequence, a} and the 56-byte record; the second word of dbad is the walk's error word (never set here:
         // the items come from the call's own arrays)
@@ -169,24 +183,65 @@ int align_sam_lines(rbg_index *ix, const char *seq_base, const uint64_t *seq_beg
             }
             lap_from = std::chrono::steady_clock::now();
         }
-        if (launch_sam_ext_len(B, dws.p, dext.p, cap, st) || launch_sam_offsets(dws.p, E, st)) return RBG_ENODEV;
+        if (right) {
+            // per line 32 bytes of item {row, limit, sequence, b, skip, budget} and the right record; the third word of dbad is this walk's error word
+            if ((rc = dritem.alloc(E * 32)) || (rc = drext.alloc(E * sizeof(SamExtend)))) return rc;
+            uint64_t *r_row = dritem.as<uint64_t>(), *r_lim = r_row + E;
+            uint32_t *r_seq = reinterpret_cast<uint32_t *>(r_lim + E), *r_b = r_seq + E, *r_skip = r_b + E, *r_k = r_skip + E;
+            if (launch_sam_right_items(B, dws.p, dext.p, ix->H().n, static_cast<uint32_t>(max_mismatch), r_seq, r_b, r_row, r_skip, r_lim, r_k, cap, st)) return RBG_ENODEV;
+            if (launch_extend_right(ix->fl_dev.view, ix->H().pos_bytes, ix->H().n, dseq2.as<uint8_t>(), doff2.as<uint64_t>(), 2 * N, r_seq, r_b, r_row, r_skip, r_lim, r_k,
+                                    E, static_cast<uint32_t>(max_mismatch), drext.p, dbad.as<unsigned int>() + 2, cap, st))
+                return RBG_ENODEV;
+            lap(9);
+            if (g_trace.on) {
+                {
+                std::vector<SamExtend> hx(E);
+                std::vector<uint32_t> hs(E), hb(E), hk(E);
+                HIP_TRY(hipMemcpyAsync(hx.data(), drext.p, E * sizeof(SamExtend), hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(hs.data(), r_seq, E * 4, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(hb.data(), r_b, E * 4, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(hk.data(), r_skip, E * 4, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+                uint64_t w[8] = {E, 0, 0, 0, 0, 0, 0, 0};
+                for (uint64_t e = 0; e < E; ++e) {
+                    if (hs[e] == 0xFFFFFFFFu) continue;
+                    const uint64_t clip = seq_len[hs[e] >> 1] - hb[e];
+                    w[1] += 1;
+                    w[2] += hk[e];
+                    w[3] += hx[e].steps;
+                    for (int j = 0; j < RBG_SAM_MAX_MISMATCH; ++j) w[4] += hx[e].mis_ref[j] != 0;
+                    w[5] += hx[e].ext > 0;
+                    w[6] += hx[e].ext;
+                    w[7] += hx[e].ext == clip;
+                }
+                std::lock_guard<std::mutex> g(g_trace.mu);
+                for (int j = 0; j < 8; ++j) g_trace.rwalks[j] += w[j];
+                }
+                lap_from = std::chrono::steady_clock::now();
+            }
+        }
+        if ((right ? launch_sam_both_len(B, dws.p, dext.p, drext.p, cap, st) : launch_sam_ext_len(B, dws.p, dext.p, cap, st)) || launch_sam_offsets(dws.p, E, st))
+            return RBG_ENODEV;
     } else if (launch_sam_plan(B, dws.p, ws_bytes, dbad.as<unsigned int>(), cap, st)) {
         return RBG_ENODEV;
     }
     const uint64_t *p_at = nullptr, *p_len = nullptr;
     sam_total_ptrs(dws.p, E, &p_at, &p_len);
     uint64_t last_at = 0, last_len = 0;
-    uint32_t bad[2] = {0, 0};
+    uint32_t bad[3] = {0, 0, 0};
     HIP_TRY(hipMemcpyAsync(&last_at, p_at, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&last_len, p_len, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(bad, dbad.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(bad, dbad.p, 12, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     lap(5);
-    if (extend && bad[1]) return RBG_ENODEV;   // (an item of the call's own making refused by the walk: cannot happen)
+    if (extend && (bad[1] || bad[2])) return RBG_ENODEV;   // (an item of the call's own making refused by a walk: cannot happen)
     if (bad[0]) return RBG_EARG;   // a location before every document: rbg_resolve_offset's error, as rbg_align_text answers
     const uint64_t total = last_at + last_len;
     if ((rc = dtext.alloc(total))) return rc;
-    if (extend ? launch_sam_ext_fill(B, dws.p, dext.p, total, dtext.as<char>(), cap, st) : launch_sam_fill(B, dws.p, total, dtext.as<char>(), cap, st)) return RBG_ENODEV;
+    if (right    ? launch_sam_both_fill(B, dws.p, dext.p, drext.p, total, dtext.as<char>(), cap, st)
+        : extend ? launch_sam_ext_fill(B, dws.p, dext.p, total, dtext.as<char>(), cap, st)
+                 : launch_sam_fill(B, dws.p, total, dtext.as<char>(), cap, st))
+        return RBG_ENODEV;
     lap(6);
     char *out = nullptr;
     if ((rc = take_text_out(ix, total, &out))) return rc;
@@ -206,7 +261,7 @@ int align_sam_lines(rbg_index *ix, const char *seq_base, const uint64_t *seq_beg
         (void)rbg_wait_text(ix, out);
         lap(7);
         std::lock_guard<std::mutex> g(g_trace.mu);
-        for (int j = 0; j < 9; ++j) g_trace.t[j] += lap_t[j];
+        for (int j = 0; j < 10; ++j) g_trace.t[j] += lap_t[j];
         g_trace.calls += 1;
         g_trace.bytes += total;
     }
@@ -221,7 +276,7 @@ int rbg_align_sam(rbg_index *ix, const char *seq_base, const uint64_t *seq_begin
                   const char *name_base, const uint64_t *name_begin, const uint32_t *name_len, uint64_t N, uint64_t min_length, uint64_t max_hits,
                   uint32_t flags, const char **text, uint64_t *text_len) {
     return guarded([&]() -> int {
-        return align_sam_lines(ix, seq_base, seq_begin, seq_len, qual_base, qual_begin, name_base, name_begin, name_len, N, min_length, max_hits, flags, -1, text,
+        return align_sam_lines(ix, seq_base, seq_begin, seq_len, qual_base, qual_begin, name_base, name_begin, name_len, N, min_length, max_hits, flags, -1, false, text,
                                text_len);
     });
 }
@@ -232,7 +287,17 @@ int rbg_align_sam_extend(rbg_index *ix, const char *seq_base, const uint64_t *se
     return guarded([&]() -> int {
         if (!ix || max_mismatch > RBG_SAM_MAX_MISMATCH) return RBG_EARG;   // (a null handle is an argument error here; a handle without a device: RBG_ENODEV)
         return align_sam_lines(ix, seq_base, seq_begin, seq_len, qual_base, qual_begin, name_base, name_begin, name_len, N, min_length, max_hits, flags,
-                               static_cast<int>(max_mismatch), text, text_len);
+                               static_cast<int>(max_mismatch), false, text, text_len);
+    });
+}
+
+int rbg_align_sam_extend_both(rbg_index *ix, const char *seq_base, const uint64_t *seq_begin, const uint32_t *seq_len, const char *qual_base,
+                              const uint64_t *qual_begin, const char *name_base, const uint64_t *name_begin, const uint32_t *name_len, uint64_t N,
+                              uint64_t min_length, uint64_t max_hits, uint32_t flags, uint32_t max_mismatch, const char **text, uint64_t *text_len) {
+    return guarded([&]() -> int {
+        if (!ix || max_mismatch > RBG_SAM_MAX_MISMATCH) return RBG_EARG;
+        return align_sam_lines(ix, seq_base, seq_begin, seq_len, qual_base, qual_begin, name_base, name_begin, name_len, N, min_length, max_hits, flags,
+                               static_cast<int>(max_mismatch), true, text, text_len);
     });
 }
 

@@ -11,6 +11,8 @@
 // lines rbg_align_sam makes on the device -- both strands, the longer greedy seed of --min-seed-length located, soft-clipped, --max-hits secondary lines
 // with --secondary.  QUAL is "*" for a batch in which any record has no quality string (FASTA).  --extend [--max-mismatches n] asks for rbg_align_sam_extend's
 // lines instead: every seed extended leftwards through up to n mismatches by an LF walk (no right extension); without --extend not one byte changes.
+// --extend --extend-right asks for rbg_align_sam_extend_both's: the right clip extended too, by an FL walk with what the left walk left of the budget; the FL
+// index is prepared once after the load, on every replica.
 // stderr keeps the reference's shape ("will load SA and DA", "<load_s> <query_s>").
 // Input parsing follows kseq.h semantics (name = header up to the first whitespace; FASTA or FASTQ,
 // plain or gzip; kseq_read's -2 "truncated quality string" error is reported the same way).
@@ -51,6 +53,7 @@ struct RbAlignArgs {  // rb_align.cpp:17-24
     uint64_t min_seed_length = 20, max_hits = 16;  // --min-seed-length, --max-hits
     bool secondary = false;                        // --secondary
     bool extend = false;                           // --extend: every line's seed extended leftwards through mismatches (rbg_align_sam_extend)
+    bool extend_right = false;                     // --extend-right (with --extend): the right clip too, by an FL walk (rbg_align_sam_extend_both)
     uint64_t max_mismatches = 4;                   // --max-mismatches
     bool max_mismatches_given = false;
     int device = 0;
@@ -74,6 +77,7 @@ void print_help() {  // rb_align.cpp:26-35
     fprintf(stderr, "    --max-hits <n>                   --format sam --secondary: lines per read, at most (default 16)\n");
     fprintf(stderr, "    --secondary                      --format sam: also one line per further location\n");
     fprintf(stderr, "    --extend                         --format sam: extend every seed leftwards through mismatches (POS, CIGAR, NM / MD / AS); no right extension\n");
+    fprintf(stderr, "    --extend-right                   --format sam --extend: extend the right clip too, by an FL walk over an index built after the load\n");
     fprintf(stderr, "    --max-mismatches <n>             --format sam --extend: mismatches an extension may take, 0..8 (default 4)\n");
     fprintf(stderr, "    --gpu <n>                        HIP device ordinal (default 0)\n");
     fprintf(stderr, "    --gpus <G>                       replicate the index on G devices (from --gpu on) and shard every batch over them\n");
@@ -101,6 +105,7 @@ RbAlignArgs parse_args(int argc, char **argv) {  // rb_align.cpp:37-84
                                            {"max-hits", required_argument, 0, 'H'},
                                            {"secondary", no_argument, 0, 'S'},
                                            {"extend", no_argument, 0, 'X'},
+                                           {"extend-right", no_argument, 0, 'Y'},
                                            {"max-mismatches", required_argument, 0, 'K'},
                                            {0, 0, 0, 0}};
     int c, long_index = 0;
@@ -130,6 +135,7 @@ RbAlignArgs parse_args(int argc, char **argv) {  // rb_align.cpp:37-84
             case 'H': args.max_hits = strtoull(optarg, nullptr, 10); break;
             case 'S': args.secondary = true; break;
             case 'X': args.extend = true; break;
+            case 'Y': args.extend_right = true; break;
             case 'K': args.max_mismatches = strtoull(optarg, nullptr, 10); args.max_mismatches_given = true; break;
             default: print_help(); exit(1);
         }
@@ -146,6 +152,7 @@ RbAlignArgs parse_args(int argc, char **argv) {  // rb_align.cpp:37-84
     if (args.format_sam && (args.sam || args.markers)) { fprintf(stderr, "--format sam goes without -s and -m\n"); exit(1); }
     if (args.format_sam && args.min_seed_length == 0) { fprintf(stderr, "--min-seed-length must be at least 1\n"); exit(1); }
     if (args.extend && !args.format_sam) { fprintf(stderr, "--extend goes with --format sam\n"); exit(1); }
+    if (args.extend_right && !args.extend) { fprintf(stderr, "--extend-right goes with --extend\n"); exit(1); }
     if (args.max_mismatches_given && !args.extend) { fprintf(stderr, "--max-mismatches goes with --extend\n"); exit(1); }
     if (args.max_mismatches > RBG_SAM_MAX_MISMATCH) { fprintf(stderr, "--max-mismatches must be at most %d\n", RBG_SAM_MAX_MISMATCH); exit(1); }
     if (args.gpus < 1) args.gpus = 1;
@@ -205,6 +212,12 @@ ShardError query_shard(rbg_index *ix, const RbAlignArgs &args, const BatchView &
             r.text_owner = ix;
             const uint64_t *qb = quals ? b.w->recs.qual_begin.data() + b.w0 + begin : nullptr, *nb = b.w->recs.name_begin.data() + b.w0 + begin;
             const uint32_t *nl = b.w->recs.name_len.data() + b.w0 + begin, flags = args.secondary ? RBG_SAM_SECONDARY : 0u;
+            if (args.extend && args.extend_right) {
+                if ((rc = rbg_align_sam_extend_both(ix, b.w->base, sb, sl, quals ? b.w->base : nullptr, qb, b.w->base, nb, nl, N, args.min_seed_length, args.max_hits,
+                                                    flags, static_cast<uint32_t>(args.max_mismatches), &r.text, &r.text_len)))
+                    return {rc, "rbg_align_sam_extend_both"};
+                return {};
+            }
             if (args.extend) {
                 if ((rc = rbg_align_sam_extend(ix, b.w->base, sb, sl, quals ? b.w->base : nullptr, qb, b.w->base, nb, nl, N, args.min_seed_length, args.max_hits, flags,
                                                static_cast<uint32_t>(args.max_mismatches), &r.text, &r.text_len)))
@@ -439,6 +452,8 @@ int main(int argc, char **argv) {
             reps.push_back(r);
         }
     }
+    if (args.extend_right)   // the FL index, once, on every replica (each from the primary's host arrays)
+        for (rbg_index *r : reps) rbwt::detail::check(rbg_fl_prepare(r), "rbg_fl_prepare");
     if (args.sam) {   // load_rbwt asked for the DL flag: a missing .docs has already ended the run there (rowbowt_io.hpp:166-169)
         rbwt::detail::check(rbg_doc_table(rb.handle(), &g_docs.n, &g_docs.starts, &g_docs.names, &g_docs.size), "rbg_doc_table");
         for (uint64_t d = 0; d < g_docs.n; ++d) {

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "rbg_mkdir.hpp"
+#include "rbg_fl.hpp"
 
 namespace rbg {
 
@@ -567,6 +568,21 @@ int launch_sam_ext_items(const SamBatch &B, void *ws, uint32_t *item_seq, uint32
                          uint32_t cap, void *stream);
 int launch_sam_ext_len(const SamBatch &B, void *ws, const void *ext, uint32_t cap, void *stream);
 int launch_sam_ext_fill(const SamBatch &B, void *ws, const void *ext, uint64_t total, char *text, uint32_t cap, void *stream);
+// FL and the right extension of located seeds (fl_extend.hip; rbg_fl_dev, rbg_extend_right_dev, rbg_align_sam_extend_both; the structure: rbg_fl.hpp, the rule:
+// rbg_sam.hpp).  v: the FL index on the launch's device, n the text length.  launch_fl_rows: M rows -> their F bytes (0: no base) and FL rows; *d_err |= 1
+// for a row >= n (its outputs are zero).  launch_extend_right: M items {sequence, seed end b, row of the seed's first base, skip, limit} -> M records of 56
+// bytes; item_k (nullable): a budget per item, and then an item whose sequence is 0xFFFFFFFF is no item (a zero record, no error); *d_err |= 1 for an item
+// whose sequence is >= N, whose b lies beyond its sequence, whose skip exceeds b or whose row is >= n.  Then rbg_align_sam_extend_both's phases behind
+// launch_sam_ext_items and launch_extend_left: the right items of the lines with a right clip, the lengths, the text.
+int launch_fl_rows(const FlView &v, uint32_t pos_bytes, uint64_t n, const uint64_t *rows, uint64_t M, uint8_t *sym, uint64_t *next, unsigned int *d_err,
+                   uint32_t cap, void *stream);
+int launch_extend_right(const FlView &v, uint32_t pos_bytes, uint64_t n, const uint8_t *seqs, const uint64_t *off, uint64_t N, const uint32_t *item_seq,
+                        const uint32_t *item_b, const uint64_t *item_row, const uint32_t *item_skip, const uint64_t *item_limit, const uint32_t *item_k, uint64_t M,
+                        uint32_t max_mismatch, void *out, unsigned int *d_err, uint32_t cap, void *stream);
+int launch_sam_right_items(const SamBatch &B, void *ws, const void *ext_left, uint64_t n, uint32_t K, uint32_t *item_seq, uint32_t *item_b, uint64_t *item_row,
+                           uint32_t *item_skip, uint64_t *item_limit, uint32_t *item_k, uint32_t cap, void *stream);
+int launch_sam_both_len(const SamBatch &B, void *ws, const void *ext, const void *ext_right, uint32_t cap, void *stream);
+int launch_sam_both_fill(const SamBatch &B, void *ws, const void *ext, const void *ext_right, uint64_t total, char *text, uint32_t cap, void *stream);
 // run-indexed layout from run lists already on the device (k_build.hip): the tables' directories, 8-byte samples packed to 6
 int launch_run_dirs(uint32_t pos_bytes, const void *ent, const uint64_t *first, const uint64_t *nruns, const uint64_t *doff, const uint32_t *dshift,
                     uint32_t T, uint64_t total, uint32_t *dir, void *stream);

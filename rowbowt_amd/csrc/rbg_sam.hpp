@@ -31,6 +31,15 @@
 // (match counts separated by the reference base of each mismatch; it starts and ends with a number) and AS:i:<AS> -- on every mapped line, also at e = 0.
 // THERE IS NO RIGHT EXTENSION: LF only goes left and the index holds no FL structure; the right flank stays soft-clipped.
 //
+// RIGHT EXTENSION (rbg_align_sam_extend_both, rbg_extend_right_dev; fl_extend.hip walks it over the FL index of rbg_fl.hpp, which rbg_fl_prepare builds).  The
+// same rule with two substitutions: x = s[b + t] for t in 0 .. L-1, L = min(m - b, limit); the reference base is the F symbol of the current row and the
+// row moves by FL.  The walk starts at the line's own row (the occurrence of the seed's first base) and first takes skip = b - a FL steps without
+// comparing, which crosses the seed; a row without a base on the way ends the item with a zero extension.  limit = doc_end - (location + (b - a)), doc_end the
+// next sorted document start (n for the last document); the budget is K - nm of the line's left walk, so NM never exceeds K and the left walk is the one
+// above, unchanged.  Lines without a right clip (m == b) make no walk.  The line: POS as the left rule gives it, CIGAR [(a-eL)S] (b-a+eL+eR)M [(m-b-eR)S],
+// NM = nmL + nmR, MD over [a-eL, b+eR) (left part, seed, right part), AS = (b-a) + bestL + bestR.  The strand pick (the longer SEED) is unchanged, and a seed
+// that spans a document boundary stays undetected.
+//
 // HEADER.  "@HD\tVN:1.6\tSO:unsorted\n", then per document in sorted-start order "@SQ\tSN:<name>\tLN:<len>\n" with len = the next sorted start - this one,
 // and n - start for the last (n: the index's text length; 0 if the start lies beyond it).  That is an UPPER BOUND of the sequence's length: it includes
 // the separators between documents and the terminator.  Names pair with sorted starts by position, as rbg_doc_table lists them.
@@ -147,18 +156,29 @@ RBG_SAM_HD uint32_t sam_flag(const SamLine &L) {
 RBG_SAM_HD uint64_t sam_seq_len(const SamLine &L) { return (L.mapped && L.hit > 1) || L.m == 0 ? 1 : L.m; }
 RBG_SAM_HD uint64_t sam_qual_len(const SamLine &L) { return (L.mapped && L.hit > 1) || L.m == 0 || !L.has_qual ? 1 : L.m; }
 constexpr uint32_t kSamUnmappedMid = 17;   // "\t4\t*\t0\t0\t*\t*\t0\t0\t"
-// MD:Z: of an extended line: the read positions [a - e, b) from the left, u = e - 1 - t the position of the mismatch met at t
-RBG_SAM_HD uint32_t sam_md_len(const SamExtend *x, const uint64_t seed_len) {
+// MD:Z: of an extended line: the read positions [a - e, b) from the left, u = e - 1 - t the position of the mismatch met at t.  y (nullable): the line's
+// RIGHT extension -- the positions [b, b + y->ext) follow, the mismatch met at t sits t bases right of b; the number around the seed joins both flanks' matches
+RBG_SAM_HD uint32_t sam_md_len(const SamExtend *x, const uint64_t seed_len, const SamExtend *y = nullptr) {
     uint32_t n = 0, prev = 0;
     for (uint32_t i = x->nm; i-- > 0;) {
         const uint32_t u = x->ext - 1 - x->mis_t[i];
         n += sam_dec_len(u - prev) + 1;
         prev = u + 1;
     }
-    return n + sam_dec_len(static_cast<uint64_t>(x->ext - prev) + seed_len);
+    uint64_t run = static_cast<uint64_t>(x->ext - prev) + seed_len;
+    if (y) {
+        uint32_t at = 0;
+        for (uint32_t i = 0; i < y->nm; ++i) {
+            n += sam_dec_len(run + (y->mis_t[i] - at)) + 1;
+            run = 0;
+            at = y->mis_t[i] + 1;
+        }
+        run += y->ext - at;
+    }
+    return n + sam_dec_len(run);
 }
 template <typename Ptr>
-RBG_SAM_HD uint32_t sam_put_md(Ptr p, const SamExtend *x, const uint64_t seed_len) {
+RBG_SAM_HD uint32_t sam_put_md(Ptr p, const SamExtend *x, const uint64_t seed_len, const SamExtend *y = nullptr) {
     uint32_t n = 0, prev = 0;
     for (uint32_t i = x->nm; i-- > 0;) {
         const uint32_t u = x->ext - 1 - x->mis_t[i];
@@ -166,16 +186,28 @@ RBG_SAM_HD uint32_t sam_put_md(Ptr p, const SamExtend *x, const uint64_t seed_le
         p[n++] = static_cast<char>(x->mis_ref[i]);
         prev = u + 1;
     }
-    return n + sam_put_dec(p + n, static_cast<uint64_t>(x->ext - prev) + seed_len);
+    uint64_t run = static_cast<uint64_t>(x->ext - prev) + seed_len;
+    if (y) {
+        uint32_t at = 0;
+        for (uint32_t i = 0; i < y->nm; ++i) {
+            n += sam_put_dec(p + n, run + (y->mis_t[i] - at));
+            p[n++] = static_cast<char>(y->mis_ref[i]);
+            run = 0;
+            at = y->mis_t[i] + 1;
+        }
+        run += y->ext - at;
+    }
+    return n + sam_put_dec(p + n, run);
 }
-// x (nullable): the line's left extension -- POS and the clip move by x->ext, the tags NM, MD and AS follow HI (mapped lines only)
-RBG_SAM_HD uint64_t sam_line_len(const SamLine &L, const SamExtend *x = nullptr) {
+// x (nullable): the line's left extension -- POS and the clip move by x->ext, the tags NM, MD and AS follow HI (mapped lines only).  y (nullable, only
+// with x): its right extension -- the right clip shrinks by y->ext, NM, MD and AS take both flanks
+RBG_SAM_HD uint64_t sam_line_len(const SamLine &L, const SamExtend *x = nullptr, const SamExtend *y = nullptr) {
     if (!L.mapped) return L.name_len + kSamUnmappedMid + sam_seq_len(L) + 1 + sam_qual_len(L) + 1;
-    const uint64_t e = x ? x->ext : 0;
-    uint64_t n = L.name_len + 1 + sam_dec_len(sam_flag(L)) + 1 + L.rname_len + 1 + sam_dec_len(L.pos - e) + 5 /* \t255\t */ + sam_cigar_len(L.m, L.a - e, L.b) +
+    const uint64_t e = x ? x->ext : 0, er = y ? y->ext : 0;
+    uint64_t n = L.name_len + 1 + sam_dec_len(sam_flag(L)) + 1 + L.rname_len + 1 + sam_dec_len(L.pos - e) + 5 /* \t255\t */ + sam_cigar_len(L.m, L.a - e, L.b + er) +
                  7 /* \t*\t0\t0\t */ + sam_seq_len(L) + 1 + sam_qual_len(L) + 6 /* \tNH:i: */ + sam_dec_len(L.occ) + 6 /* \tHI:i: */ + sam_dec_len(L.hit) + 1;
-    if (x) n += 6 /* \tNM:i: */ + sam_dec_len(x->nm) + 6 /* \tMD:Z: */ + sam_md_len(x, L.b - L.a) + 6 /* \tAS:i: */ +
-                sam_dec_len(L.b - L.a + static_cast<uint64_t>(x->score));
+    if (x) n += 6 /* \tNM:i: */ + sam_dec_len(x->nm + (y ? y->nm : 0u)) + 6 /* \tMD:Z: */ + sam_md_len(x, L.b - L.a, y) + 6 /* \tAS:i: */ +
+                sam_dec_len(L.b - L.a + static_cast<uint64_t>(x->score) + (y ? static_cast<uint64_t>(y->score) : 0));
     return n;
 }
 
@@ -194,9 +226,10 @@ RBG_SAM_HD Ptr sam_put_bases(Ptr p, const char *src, const uint64_t m, const boo
     }
     return p + m;
 }
-// the sam_line_len(L, x) bytes of the line at p; seq / qual: the read's ORIGINAL bytes (qual unused without has_qual)
+// the sam_line_len(L, x, y) bytes of the line at p; seq / qual: the read's ORIGINAL bytes (qual unused without has_qual)
 template <typename Ptr>
-RBG_SAM_HD void sam_put_line(Ptr p, const SamLine &L, const char *name, const char *rname, const char *seq, const char *qual, const SamExtend *x = nullptr) {
+RBG_SAM_HD void sam_put_line(Ptr p, const SamLine &L, const char *name, const char *rname, const char *seq, const char *qual, const SamExtend *x = nullptr,
+                             const SamExtend *y = nullptr) {
     for (uint64_t j = 0; j < L.name_len; ++j) p[j] = name[j];
     p += L.name_len;
     const bool star = (L.mapped && L.hit > 1) || L.m == 0;
@@ -214,10 +247,10 @@ RBG_SAM_HD void sam_put_line(Ptr p, const SamLine &L, const char *name, const ch
     for (uint64_t j = 0; j < L.rname_len; ++j) p[j] = rname[j];
     p += L.rname_len;
     *p = '\t'; p += 1;
-    const uint64_t e = x ? x->ext : 0;
+    const uint64_t e = x ? x->ext : 0, er = y ? y->ext : 0;
     p += sam_put_dec(p, L.pos - e);
     p = sam_put_lit(p, "\t255\t", 5);
-    p += sam_put_cigar(p, L.m, L.a - e, L.b);
+    p += sam_put_cigar(p, L.m, L.a - e, L.b + er);
     p = sam_put_lit(p, "\t*\t0\t0\t", 7);
     p = sam_put_bases(p, seq, L.m, star, L.reverse, L.reverse);
     *p = '\t'; p += 1;
@@ -228,11 +261,11 @@ RBG_SAM_HD void sam_put_line(Ptr p, const SamLine &L, const char *name, const ch
     p += sam_put_dec(p, L.hit);
     if (x) {
         p = sam_put_lit(p, "\tNM:i:", 6);
-        p += sam_put_dec(p, x->nm);
+        p += sam_put_dec(p, x->nm + (y ? y->nm : 0u));
         p = sam_put_lit(p, "\tMD:Z:", 6);
-        p += sam_put_md(p, x, L.b - L.a);
+        p += sam_put_md(p, x, L.b - L.a, y);
         p = sam_put_lit(p, "\tAS:i:", 6);
-        p += sam_put_dec(p, L.b - L.a + static_cast<uint64_t>(x->score));
+        p += sam_put_dec(p, L.b - L.a + static_cast<uint64_t>(x->score) + (y ? static_cast<uint64_t>(y->score) : 0));
     }
     *p = '\n';
 }

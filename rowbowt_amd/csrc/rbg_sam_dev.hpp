@@ -1,7 +1,7 @@
 // rbg_sam_dev.hpp -- what the SAM kernels of k_sam.hip and sam_extend.hip share: the batch as a kernel sees it, the parts of a line, the body of the write
 // kernels (kSamLines lines per workgroup formatted into LDS at their offsets, the workgroup's stretch leaving in aligned 16-byte stores; a stretch
 // longer than kSamLds goes straight to memory, lane by lane), the workspace's layout.  `ext` (nullable): one SamExtend per line -- the extended lines of
-// rbg_align_sam_extend; nullptr gives rbg_align_sam's lines.  Everything lives in an anonymous namespace: each unit gets its own inlined copy.
+// rbg_align_sam_extend; nullptr gives rbg_align_sam's lines; `ext_right` (nullable, with ext): the lines' right extensions (fl_extend.hip).  Everything lives in an anonymous namespace: each unit gets its own inlined copy.
 #pragma once
 
 #include "rbg_device.hpp"
@@ -66,16 +66,18 @@ __device__ __forceinline__ SamLine sam_line_of(const SamArgs &s, const uint64_t 
     return L;
 }
 
-__device__ __forceinline__ void sam_put(const SamArgs &s, const uint64_t e, const uint64_t i, const uint32_t d, char *p, const SamExtend *ext) {
+__device__ __forceinline__ void sam_put(const SamArgs &s, const uint64_t e, const uint64_t i, const uint32_t d, char *p, const SamExtend *ext,
+                                        const SamExtend *ext_right = nullptr) {
     const SamLine L = sam_line_of(s, e, i, d);
     sam_put_line(p, L, s.names + s.name_off[i], s.doc_names + s.doc_name_off[d], s.seqs + s.roff[i], s.quals ? s.quals + s.roff[i] : nullptr,
-                 ext && L.mapped ? ext + e : nullptr);
+                 ext && L.mapped ? ext + e : nullptr, ext && ext_right && L.mapped ? ext_right + e : nullptr);
 }
 
 // the body of k_sam_write: kSamLines lines per workgroup (= its threads), s_buf its kSamLds + 16 bytes of LDS, 16-byte aligned (the including unit's constants)
 template <uint32_t kSamLines, uint32_t kSamLds>
 __device__ __forceinline__ void sam_write_lines(const SamArgs &s, const uint32_t *__restrict__ eread, const uint32_t *__restrict__ doc, const uint64_t *__restrict__ at,
-                                                const uint64_t total, char *__restrict__ text, char *s_buf, const SamExtend *__restrict__ ext) {
+                                                const uint64_t total, char *__restrict__ text, char *s_buf, const SamExtend *__restrict__ ext,
+                                                const SamExtend *__restrict__ ext_right = nullptr) {
     const uint64_t nblocks = (s.E + kSamLines - 1) / kSamLines;
     for (uint64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
         const uint64_t e0 = blk * kSamLines, e1 = e0 + kSamLines < s.E ? e0 + kSamLines : s.E;
@@ -83,7 +85,7 @@ __device__ __forceinline__ void sam_write_lines(const SamArgs &s, const uint32_t
         const uint64_t e = e0 + threadIdx.x;
         const uint32_t shift = static_cast<uint32_t>((reinterpret_cast<uintptr_t>(text) + t0) & 15u);   // LDS and memory addresses congruent mod 16
         if (t1 - t0 <= kSamLds) {
-            if (e < e1) sam_put(s, e, eread[e], doc[e], s_buf + shift + (at[e] - t0), ext);
+            if (e < e1) sam_put(s, e, eread[e], doc[e], s_buf + shift + (at[e] - t0), ext, ext_right);
             __syncthreads();
             const uint32_t nbytes = static_cast<uint32_t>(t1 - t0);
             char *dst = text + t0;
@@ -98,7 +100,7 @@ __device__ __forceinline__ void sam_write_lines(const SamArgs &s, const uint32_t
             if (threadIdx.x < nbytes - done) dst[done + threadIdx.x] = src[done + threadIdx.x];
             __syncthreads();
         } else if (e < e1) {
-            sam_put(s, e, eread[e], doc[e], text + at[e], ext);             // (a long name or read: straight to memory, byte by byte)
+            sam_put(s, e, eread[e], doc[e], text + at[e], ext, ext_right);  // (a long name or read: straight to memory, byte by byte)
         }
     }
 }

@@ -219,10 +219,17 @@ class RowBowt {
                                  uint64_t min_length = 20, uint64_t max_hits = 16, bool secondary = false, uint32_t max_mismatch = 4) const {
         return sam_lines(seqs, quals, names, min_length, max_hits, secondary, static_cast<int>(max_mismatch > 0x7FFFFFFFu ? 0x7FFFFFFFu : max_mismatch));
     }
+    // the FL index on this handle's device (rbg_fl_prepare: idempotent, opt-in), which align_sam_extend_both needs
+    void fl_prepare() { detail::check(rbg_fl_prepare(ix_.get()), "rbg_fl_prepare"); }
+    // align_sam_extend's lines with the right clip extended too, by an FL walk with what the left walk left of the budget (rbg_align_sam_extend_both)
+    std::string align_sam_extend_both(const std::vector<std::string> &seqs, const std::vector<std::string> &quals, const std::vector<std::string> &names,
+                                      uint64_t min_length = 20, uint64_t max_hits = 16, bool secondary = false, uint32_t max_mismatch = 4) const {
+        return sam_lines(seqs, quals, names, min_length, max_hits, secondary, static_cast<int>(max_mismatch > 0x7FFFFFFFu ? 0x7FFFFFFFu : max_mismatch), true);
+    }
 
   private:
     std::string sam_lines(const std::vector<std::string> &seqs, const std::vector<std::string> &quals, const std::vector<std::string> &names, uint64_t min_length,
-                          uint64_t max_hits, bool secondary, int max_mismatch /* < 0: rbg_align_sam */) const {
+                          uint64_t max_hits, bool secondary, int max_mismatch /* < 0: rbg_align_sam */, bool right = false) const {
         const uint64_t N = seqs.size();
         if (names.size() != N || (!quals.empty() && quals.size() != N)) detail::die("align_sam: a name (and a quality string, if any) per read", RBG_EARG);
         std::string sblob, qblob, nblob;
@@ -239,6 +246,10 @@ class RowBowt {
         if (max_mismatch < 0)
             detail::check(rbg_align_sam(ix_.get(), sblob.data(), sbeg.data(), slen.data(), quals.empty() ? nullptr : qblob.data(), sbeg.data(), nblob.data(),
                                         nbeg.data(), nlen.data(), N, min_length, max_hits, secondary ? RBG_SAM_SECONDARY : 0u, &text, &n), "rbg_align_sam");
+        else if (right)
+            detail::check(rbg_align_sam_extend_both(ix_.get(), sblob.data(), sbeg.data(), slen.data(), quals.empty() ? nullptr : qblob.data(), sbeg.data(),
+                                                    nblob.data(), nbeg.data(), nlen.data(), N, min_length, max_hits, secondary ? RBG_SAM_SECONDARY : 0u,
+                                                    static_cast<uint32_t>(max_mismatch), &text, &n), "rbg_align_sam_extend_both");
         else
             detail::check(rbg_align_sam_extend(ix_.get(), sblob.data(), sbeg.data(), slen.data(), quals.empty() ? nullptr : qblob.data(), sbeg.data(), nblob.data(),
                                                nbeg.data(), nlen.data(), N, min_length, max_hits, secondary ? RBG_SAM_SECONDARY : 0u,
