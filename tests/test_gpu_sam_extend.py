@@ -39,7 +39,8 @@ def _same(got, want):
                          f"want {want[max(at - 80, 0):at + 80]!r}")
 
 
-@pytest.fixture(scope="module", params=[(capi.LAYOUT_SLOTS, 0), (capi.LAYOUT_RUNS, 0), (capi.LAYOUT_RUNS, 8)], ids=["slots", "runs", "runs-8-byte"])
+@pytest.fixture(scope="module", params=[(capi.LAYOUT_SLOTS, 0), (capi.LAYOUT_RUNS, 0), (capi.LAYOUT_SLOTS, 8), (capi.LAYOUT_RUNS, 8)],
+                ids=["slots", "runs", "slots-8-byte", "runs-8-byte"])
 def toy(request):
     S, o = XC.toy()
     layout, pos_bytes = request.param

@@ -110,7 +110,8 @@ def test_inputs_hold_every_kind_of_line():
                 assert er == 0 or ref[er - 1] == mine[er - 1]
 
 
-@pytest.fixture(scope="module", params=[(capi.LAYOUT_SLOTS, 0), (capi.LAYOUT_RUNS, 0), (capi.LAYOUT_RUNS, 8)], ids=["slots", "runs", "runs-8-byte"])
+@pytest.fixture(scope="module", params=[(capi.LAYOUT_SLOTS, 0), (capi.LAYOUT_RUNS, 0), (capi.LAYOUT_SLOTS, 8), (capi.LAYOUT_RUNS, 8)],
+                ids=["slots", "runs", "slots-8-byte", "runs-8-byte"])
 def toy(request):
     S, o = XC.toy()
     layout, pos_bytes = request.param

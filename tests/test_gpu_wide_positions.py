@@ -1,5 +1,6 @@
 """Positions at and across the width edges -- 2^31, the top of the 4-byte range, 2^32, 2^38 -- through everything that is built on locate: the
-device locate chain with its order, document hits, SAM, the seed lists and toehold checkpoints, the markers at located positions.
+device locate chain with its order, document hits, SAM, the seed lists and toehold checkpoints, the markers at located positions, and the seed extensions:
+FL, the LF and FL walks by themselves, the SAM lines extended to the left and on both sides.
 
 Three run lists of 2 000 runs (gpu_common._random_run_index: the arrays define every answer, no text is needed):
   A  n = 2^32 - 17, the largest index with 4-byte positions;
@@ -10,20 +11,28 @@ at A, 0.7 GB at B), C on the run-indexed layout with the phi list and with phi s
 most 64: ranges of such an index are millions of rows wide), and the handles step one symbol at a time, without a jump table (the samples of a random
 run list define toeholds for single-symbol steps only).
 
-Every comparison is exact, against the oracle and the CPU models (sam_model, doc_hits_model, seeds_model, rb_locs_model).  The expected values are made
-by plain functions (expected(name) below: no device is touched), each leg's values in a function of its own that also asserts, from the EXPECTED values,
-that the leg reaches the edges it is for."""
+Every comparison is exact, against the oracle and the CPU models (sam_model, doc_hits_model, seeds_model, rb_locs_model, sam_extend_model, fl_model).  The
+expected values are made by plain functions (expected(name) below: no device is touched; 5.3 s of CPU time for A, 6.1 s for B, 5.4 s for C), each leg's values in a function
+of its own that also asserts, from the EXPECTED values, that the leg reaches the edges it is for (tests/test_wide_positions_expected.py runs them where no
+GPU exists).
+
+The extension legs read their reads off the models.  Reads that were walked hardly extend here -- a range is millions of rows wide, the primary line's row
+is hi and not the row the read was walked from, so the clipped half of a substituted read meets another flank -- so a read is built from the row itself:
+BWT[r], BWT[LF(r)], ... is what lies left of row r's position, the F bytes of the FL walk from r what lies right of it."""
 import bisect
 import contextlib
 import functools
 import types
+from unittest import mock
 
 import numpy as np
 import pytest
 
 import doc_hits_model as M
+import fl_model as FM
 import orc
 import rowbowt_amd as ra
+import sam_extend_model as XM
 import sam_model as SAM
 from rowbowt_amd import capi
 from gpu_common import _lf_walk_reads, _pin_run_end_samples, _random_run_index, _random_run_index_exact, _with_layout, split
@@ -47,6 +56,8 @@ FORMS = {"A": ((capi.LAYOUT_RUNS, 0, ()), (capi.LAYOUT_SLOTS, 0, WIDE)), "B": ((
          "C": ((capi.LAYOUT_RUNS, 1, ()), (capi.LAYOUT_RUNS, 2, ()))}
 HITS = (1, 8, 64)            # every max_hits of the locate legs
 MIN_LENGTH = 10
+WALK_KS = (0, 4, 8)         # the budgets of the walks alone
+SAM_KS = (0, 2, 4)          # ... and of the extended SAM lines
 
 
 # ---- the CPU half: indices, reads, tables and every expected value --------------------------------------------------------------------------
@@ -255,6 +266,342 @@ def _marker_values(E):
     _reaches(E.name, "run hit through the greedy locations", [v & (2**48 - 1) for w in E.loc_mk for v in w[1]])
 
 
+# ---- the two extension legs: walks read off the models, reads built from a line's own row -----------------------------------------------------
+class _Memo:
+    """the oracle with its pure queries remembered: the models ask the same ones again for every call that is expected (the document table is not
+    among them: resolve_offset goes to the oracle itself)"""
+
+    def __init__(self, o):
+        self.h, self.L, self.n = o.h, o.L, o.n
+        self.LF, self.access, self.find_range_w_toehold = (functools.lru_cache(maxsize=None)(f) for f in (o.LF, o.access, o.find_range_w_toehold))
+        self._locs = functools.lru_cache(maxsize=None)(lambda lo, hi, k, mh: tuple(o.locs_at(lo, hi, k, mh)))
+
+    def locs_at(self, lo, hi, k, max_hits=MAXU):
+        return list(self._locs(lo, hi, k, max_hits))
+
+
+def _other(c, d):
+    """another base than c (d = 1, 2, 3)"""
+    return b"ACGT"[(b"ACGT".index(c) + d) % 4]
+
+
+def _left_flank(o, r, L):
+    """BWT[r], BWT[LF(r)], ...: the up to L bases left of row r's position, nearest first, and the rows they are read at (it ends at the terminator)"""
+    out, rows = bytearray(), []
+    while len(out) < L:
+        c = o.access(r)
+        if c not in b"ACGT":
+            break
+        out.append(c)
+        rows.append(r)
+        r = o.LF(r, r, c)[0]
+    return bytes(out), rows
+
+
+def _right_flank(fl, r, skip, L):
+    """the F bytes of the FL walk from row r after `skip` steps: the up to L bases from `skip` positions right of row r's position on, and their rows;
+    None when a skipped row has no base"""
+    for _ in range(skip):
+        c, r = fl.step(r)
+        if not c:
+            return None, []
+    out, rows = bytearray(), []
+    while len(out) < L:
+        c, nr = fl.step(r)
+        if not c:
+            break
+        out.append(c)
+        rows.append(r)
+        r = nr
+    return bytes(out), rows
+
+
+def _lf_chain(o, r, k):
+    """LF^k(r), or None when the terminator is on the way"""
+    for _ in range(k):
+        c = o.access(r)
+        if c not in b"ACGT":
+            return None
+        r = o.LF(r, r, c)[0]
+    return r
+
+
+def _fl_chain(fl, r, k):
+    for _ in range(k):
+        c, r = fl.step(r)
+        if not c:
+            return None
+    return r
+
+
+def _crossings(name, rows):
+    """{(edge, upwards)} for every edge that the rows of one walk cross in the order visited: a row below it and a LATER one at or above it, or the reverse"""
+    out = set()
+    for edge in EDGES[name]:
+        above = [r >= edge for r in rows]
+        if True in above and False in above[above.index(True):]:
+            out.add((edge, False))
+        if False in above and True in above[above.index(False):]:
+            out.add((edge, True))
+    return out
+
+
+def _plant(body, lo, hi, j, rng):
+    """j % 11 substitutions at random places of body[lo:hi] (in place)"""
+    for p in rng.choice(hi - lo, min(j % 11, hi - lo), replace=False):
+        body[lo + int(p)] = _other(body[lo + int(p)], 1 + j % 3)
+
+
+def _extend_values(E):
+    """leg 6: items of rbg_extend_left_dev and rbg_extend_right_dev -- a row, the row's own flank read off the models with 0 to 10 substitutions, a skip, a
+    limit -- at the width edges, at rows whose walks cross an edge on their way, at rows whose walks meet "no base"; the rows of rbg_fl_dev"""
+    o, fl, n, name = E.xo, E.fl, E.n, E.name
+    rng = np.random.default_rng(SEEDS[name] + 50)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    rows = [0, 1, n - 1] + [e - d for e in EDGES[name] for d in (1, 0)] + ([2**32 + d for d in (-40, -1, 0, 1, 40)] if name == "C" else [])
+    rows += [int(v) for v in rng.integers(0, n, 300)]
+    generic = [dict(row=r) for r in rows]
+    # rows found by search: the walk from FL^k(z) (left) or LF^k(z) (right) reaches z after k steps; z at or above an edge and the start below it, and the
+    # reverse (z below, the start above).  Such walks get a long flank, the whole limit and at most two substitutions, so that they arrive.
+    zone = {e: [int(v) for v in rng.integers(e, n, 12)] + [int(v) for v in rng.integers(max(e - 2**20, 0), e, 12)] for e in EDGES[name]}
+    term = int(E.lens[:int(np.flatnonzero(E.heads == 1)[0])].sum())
+    assert o.access(term) == 1 and fl.step(0) == (0, FM.NONE)
+    E.left, E.right = {}, {}
+    for side, items in (("left", E.left), ("right", E.right)):
+        chain = (lambda r, k: _fl_chain(fl, r, k)) if side == "left" else (lambda r, k: _lf_chain(o, r, k))
+        spec = list(generic)
+        for e, zs in zone.items():
+            for i, z in enumerate(zs):
+                k = 2 + 3 * (i % 6)
+                spec.append(dict(row=z, far=k, z=z, edge=e))           # (the start is resolved below: a right item's skip goes on top of k)
+        # the walk ends on "no base": k steps after the start, at the terminator (left, BWT[term]) or at row 0 (right, whose F byte is the terminator)
+        end = term if side == "left" else 0
+        spec += [dict(row=end, far=k, z=end, nobase=True) for k in (0, 1, 5, 30)]
+        if side == "right":
+            spec += [dict(row=0, far=k, z=0, nobase=True, into=True) for k in (0, 1, 5, 30)]   # ... and a skip that itself meets row 0: the zero record
+        seqs, pos, row_, skip_, lim_, frows = [], [], [], [], [], []
+        for j, it in enumerate(spec):
+            tail = 10 + (j * 11) % 61                                  # the compared bases: 10 .. 70
+            skip = (j * 7) % 61 if side == "right" else 0              # 0 .. 60, neighbours far apart
+            row = it["row"]
+            if "far" in it:
+                tail = max(tail, it["far"] + 12)
+                if it.get("into"):
+                    skip, row = it["far"] + 1 + j % 3, chain(it["z"], it["far"])
+                else:
+                    row = chain(it["z"], it["far"] + skip)
+                assert row is not None, (side, it)
+            if side == "left":
+                ref, at = _left_flank(o, row, tail)
+            else:
+                ref, at = _right_flank(fl, row, skip, tail)
+                ref = ref or b""
+            body = bytearray(ref) + bytearray(rng.choice(acgt, tail - len(ref)).tobytes())      # (beyond "no base": any bases)
+            if "far" in it:
+                for p in rng.choice(np.arange(it["far"] + 2, tail), j % 3, replace=False):
+                    body[int(p)] = _other(body[int(p)], 1 + j % 3)
+                limit = 2**40
+            else:
+                _plant(body, 0, tail, j, rng)
+                if j % 13 == 5:
+                    body[3] = ord("N")
+                if j % 17 == 3:
+                    body[6] = ord(chr(body[6]).lower())
+                limit = (0, 1, tail, tail + 5, 2**33, 2**40)[j % 6]
+            if side == "left":                                         # the flank reversed, then six bases that no walk reads
+                seqs.append(bytes(body[::-1]) + bytes(rng.choice(acgt, 6).tobytes()))
+                pos.append(tail)
+            else:                                                      # b bases that no walk reads (b >= skip), then the flank
+                b = skip + j % 4
+                seqs.append(bytes(rng.choice(acgt, b).tobytes()) + bytes(body))
+                pos.append(b)
+            row_.append(row)
+            skip_.append(skip)
+            lim_.append(limit)
+            frows.append(at)
+        perm = rng.permutation(len(seqs))                              # item j reads sequence perm[j]
+        items["packed"], items["off"] = ra.pack_reads([seqs[j] for j in np.argsort(perm)])
+        items.update(seq=perm.astype(np.uint32), pos=np.array(pos, np.uint32), row=np.array(row_, np.uint64), skip=np.array(skip_, np.uint32),
+                     limit=np.array(lim_, np.uint64), want={})
+        for K in WALK_KS:
+            if side == "left":
+                items["want"][K] = [XM.extend(o, seqs[j], pos[j], row_[j], lim_[j], K) for j in range(len(seqs))]
+            else:
+                items["want"][K] = [FM.extend_right(fl, seqs[j], pos[j], row_[j], skip_[j], lim_[j], K) for j in range(len(seqs))]
+        # what the expected walks reach
+        ends = {"length", "budget", "base"} | ({"skip"} if side == "right" else set())
+        visited, crossed = [], []
+        for K in WALK_KS:
+            w = items["want"][K]
+            assert {x["why"] for x in w} == ends, (side, K, {x["why"] for x in w})
+            assert max(len(x["mis"]) for x in w) == K
+            visited += [r for x, at in zip(w, frows) for r in at[:x["steps"]]]
+            crossed += [_crossings(name, at[:x["steps"]]) for x, at in zip(w, frows)]
+        assert any(len(x["mis"]) > x["nm"] for x in items["want"][8]), "no record with trimmed mismatches"
+        _reaches(name, f"row of a {side} walk", visited)
+        assert sum(1 for c in crossed if c) >= 20
+        # (both ways over the first edge; the top 2^16 rows of A lie in its last run, a run of T: LF and FL map those rows to themselves, no walk enters or
+        # leaves them, and the walks that start there stay -- they are the ones that reach that edge)
+        assert set().union(*crossed) >= {(EDGES[name][0], up) for up in (False, True)}, (side, set().union(*crossed))
+        for it, x in zip(spec, items["want"][8]):                      # the "no base" items end where they were aimed
+            if it.get("nobase"):
+                assert (x["why"], x["steps"]) == (("skip", 0) if it.get("into") else ("base", it["far"])), (side, it, x)
+        assert {int(v) for v in items["limit"]} >= {0, 1, 2**33, 2**40} and (side == "left" or int(np.abs(np.diff(items["skip"][:64].astype(np.int64))).min()) >= 7)
+    # FL rows: those of the items, the first and last row of every base's F interval, rows whose FL value is a zone row
+    fr = set(int(r) for r in E.left["row"]) | set(int(r) for r in E.right["row"])
+    for c in b"ACGT":
+        fr |= {fl.F[c], fl.F[c] + fl.count[c] - 1}
+    fr |= {_lf_chain(o, z, 1) for zs in zone.values() for z in zs} - {None}
+    E.fl_rows = np.array(sorted(fr), np.uint64)
+    want = [fl.step(int(r)) for r in E.fl_rows]
+    E.fl_sym, E.fl_next = np.array([w[0] for w in want], np.uint8), np.array([w[1] for w in want], np.uint64)
+    base = E.fl_sym != 0
+    assert (~base).any() and (E.fl_next[~base] == np.uint64(MAXU)).all() and int(E.fl_next[base].max()) < n
+    _reaches(name, "row given to FL", E.fl_rows)
+    _reaches(name, "FL value", E.fl_next[base])
+    if name == "C":                                                    # FL values above 2^32 from rows below it, and the reverse
+        assert ((E.fl_rows < 2**32) & base & (E.fl_next >= 2**32)).any() and ((E.fl_rows >= 2**32) & base & (E.fl_next < 2**32)).any()
+    else:                                                              # A, and B (n = 2^32 - 16: no value of B reaches 2^32): the 2^16 values below 2^32
+        assert (E.fl_next[base] >= 2**32 - 2**16).any() and (E.fl_rows >= 2**32 - 2**16).any()
+
+
+def _ext_kinds(reads, recs, starts, n, K):
+    """test_gpu_sam_extend_both.kinds over records of read_records_both, with the left walk's kinds and those of the limits"""
+    seen, last, srt = set(), max(starts), sorted(starts)
+    for q, rr in zip(reads, recs):
+        if rr == [None]:
+            continue
+        m = len(q)
+        for (lo, hi, k, a, b, rev), j, l, dn, offs, x, y in rr:
+            if x["ext"] > 0:
+                seen.add("left clip moved")
+            if m > b and y["ext"] == m - b:
+                seen.add("right clip gone")
+            if m > b and 0 < y["ext"] < m - b:
+                seen.add("right clip shortened")
+            if x["ext"] > 0 and y["ext"] > 0:
+                seen.add("both clips moved")
+            if x["nm"] > 0 and y["nm"] > 0 and x["nm"] + y["nm"] == K:
+                seen.add("budget split")
+            if rev and y["ext"] > 0:
+                seen.add("reverse")
+            if x["why"] == "length" and x["steps"] < a:
+                seen.add("cut by the document's start")
+            if y["why"] == "length" and y["steps"] < m - b:
+                seen.add("cut by the document's end")
+            if y["ext"] > 0 and l - offs == last:
+                seen.add("a right walk in the last document")
+            if offs >= 2**32 and x["steps"] > offs % 2**32:
+                seen.add("a left limit above 2^32 whose low word would end the walk")
+            limit = (srt[bisect.bisect_right(srt, l)] if l - offs != last else n) - (l + b - a)
+            if limit >= 2**32 and y["steps"] > limit % 2**32:
+                seen.add("a right limit above 2^32 whose low word would end the walk")
+    return seen
+
+
+def _sam_extend_texts(E, seen, lines):
+    """the model's text of every call of leg 7 into E.x_sam; the kinds of line into seen[K], (row, location, offset, left record, right record) of every line
+    at K = 4 into lines"""
+    o, fl = E.xo, E.fl
+    for table, (names, starts) in E.x_tables.items():
+        E.o.set_docs(names, starts)
+        for K in SAM_KS:
+            ql = E.x_quals if K == 4 else None
+            for secondary in (False, True):
+                for max_hits in (1, 8):
+                    E.x_sam[table, False, secondary, max_hits, K] = XM.text(o, E.x_names, E.x_reads, ql, MIN_LENGTH, max_hits, secondary, K)
+                    both = FM.lines_both(o, fl, starts, E.x_names, E.x_reads, ql, MIN_LENGTH, max_hits, secondary, K)
+                    assert both is not None
+                    E.x_sam[table, True, secondary, max_hits, K] = b"".join(both)
+            if K:
+                recs = [FM.read_records_both(o, fl, starts, q, MIN_LENGTH, 8, True, K) for q in E.x_reads]
+                kinds = _ext_kinds(E.x_reads, recs, starts, E.n, K)
+                seen[K] |= kinds
+                if table == "cut":
+                    assert {"cut by the document's start", "cut by the document's end"} <= kinds, kinds
+                if K == 4:
+                    lines += [(hi - (j - 1), l, offs, x, y) for rr in recs if rr != [None] for (lo, hi, k, a, b, rev), j, l, dn, offs, x, y in rr]
+
+
+def _sam_extend_values(E):
+    """leg 7: the reads of leg 3 and 150 reads built from a line's own row -- the row's left flank reversed, a seed, its right flank, the base nearest the seed
+    replaced on either side --, under the two tables and a third cut from the constructed reads' locations; the model's text of every call"""
+    o, fl, n, name = E.xo, E.fl, E.n, E.name
+    rng = np.random.default_rng(SEEDS[name] + 60)
+    top = EDGES[name][-1]
+    # seeds: what the FL walk of 28 to 40 steps from a row z spells (z is then a row of its range); a quarter of the z at or above the last edge
+    cand = []
+    for i in range(900):
+        z = int(rng.integers(top, n)) if i % 4 == 0 else int(rng.integers(0, n))
+        m = int(rng.integers(28, 41))
+        s, _ = _right_flank(fl, z, 0, m)
+        if s is not None and len(s) == m:
+            cand.append(s)
+    seqs, off = ra.pack_reads(cand)
+    clo, chi, ck = E.o.find_range_w_toehold_batch(seqs, off)
+    assert (chi >= clo).all()
+    first = np.flatnonzero((ck >= np.uint64(top)) & (ck < np.uint64(n - 100)))                # toeholds at or above the last edge first, as leg 4's `top`
+    order = first.tolist()[:50] + [i for i in range(len(cand)) if i not in set(first.tolist()[:50])]
+    assert len(first) >= 10
+    built = []                                                         # (read as given, lo, hi, seed length, primary location)
+    for i in order:
+        if len(built) == 150:
+            break
+        s, lo, hi, k = cand[i], int(clo[i]), int(chi[i]), int(ck[i])
+        t = len(built)
+        r = hi - 2 if t % 4 == 3 and hi - lo >= 2 else hi
+        left, _ = _left_flank(o, r, int(rng.integers(8, 20)))
+        right, _ = _right_flank(fl, r, len(s), int(rng.integers(8, 20)))
+        if right is None or min(len(left), len(right)) < 8:
+            continue
+        for d in (1, 2, 3):                                            # up to three choices of the replaced bases: the seed must stay the read's pick
+            lf, rt = bytearray(left), bytearray(right)
+            lf[0], rt[0] = _other(lf[0], d), _other(rt[0], 1 + (d + t) % 3)
+            if t % 5 == 0:
+                rt[-1] = _other(rt[-1], d)                             # (the right clip is shortened, not gone)
+            read = bytes(lf[::-1]) + s + bytes(rt)
+            given = SAM.revcomp(read) if t % 2 else read
+            p = SAM.pick(o, given, MIN_LENGTH)
+            if p is not None and (p[0], p[1], p[3], p[4], p[5]) == (lo, hi, len(lf), len(lf) + len(s), t % 2):
+                built.append((given, lo, hi, len(s), o.locs_at(lo, hi, p[2], 1)[0]))
+                break
+    assert len(built) == 150, len(built)
+    E.x_reads = list(E.sam_reads) + [b[0] for b in built]
+    E.x_names = [b"x%d" % i for i in range(len(E.x_reads))]
+    E.x_quals = _quals(E.x_reads)
+    # the third table: a document starts 3 positions before a third of the locations, 2 positions after the seed's end of another third
+    cut = {0}
+    for t, (_, lo, hi, sl, l) in enumerate(built):
+        if t % 3 == 0 and l >= 3:
+            cut.add(l - 3)
+        elif t % 3 == 1 and l + sl + 2 < n:
+            cut.add(l + sl + 2)
+    cut = sorted(cut)
+    if n > 2**33:              # C: limits above 2^32 whose low word alone would cut the walk short -- a document that starts 2^32 + 3 positions before the
+        for t, (_, lo, hi, sl, l) in enumerate(built):                 # location and the next one 2^32 + 2 positions after the seed's end, no start between them
+            before, after = l - 2**32 - 3, l + sl + 2 + 2**32
+            if t % 3 == 2 and before > 0 and after < n and bisect.bisect_left(cut, before) == bisect.bisect_left(cut, after):
+                cut = sorted(set(cut) | {before, after})
+    assert 60 < len(cut) < capi.DOCS_MAX // 100 and cut[-1] < n
+    E.x_tables = dict(E.tables, cut=([f"c{j}" for j in range(len(cut))], cut))
+    E.x_sam, seen, lines = {}, {K: set() for K in SAM_KS}, []
+    with mock.patch.object(SAM, "pick", functools.lru_cache(maxsize=None)(SAM.pick)):       # (a read's pick is the same in every call: the models' own, remembered)
+        _sam_extend_texts(E, seen, lines)
+    assert seen[4] >= {"left clip moved", "right clip gone", "right clip shortened", "both clips moved", "reverse", "cut by the document's start",
+                       "cut by the document's end", "a right walk in the last document"}, seen[4]
+    assert "budget split" in seen[2], seen[2]
+    if name == "C":
+        assert {"a left limit above 2^32 whose low word would end the walk", "a right limit above 2^32 whose low word would end the walk"} <= seen[4], seen[4]
+    per = len(E.x_tables)                                              # (every table gives the same walks but for the cuts: count the lines of one table)
+    for side, pick in (("left", 3), ("right", 4)):
+        ext = [ln for ln in lines if ln[pick]["ext"] > 0 and ln[pick]["nm"] > 0]
+        assert len(ext) >= 100 * per, (side, len(ext))
+        _reaches(name, f"row of a line extended to the {side}", [ln[0] for ln in ext])
+        _reaches(name, f"location of a line extended to the {side}", [ln[1] for ln in ext])
+    if name == "C":
+        assert any(x["ext"] > 0 and offs + 1 - x["ext"] >= 10**10 for _, _, offs, x, _ in lines), "no extended line whose POS has 11 digits"
+
+
 @functools.lru_cache(maxsize=None)
 def expected(name):
     """everything the legs compare against, for index "A", "B" or "C"; nothing here touches a device"""
@@ -268,6 +615,10 @@ def expected(name):
     _sam_values(E)
     _seed_values(E)
     _marker_values(E)
+    E.fl, E.xo = FM.FL(E.heads, E.lens), _Memo(E.o)
+    E.fl.step = functools.lru_cache(maxsize=None)(E.fl.step)
+    _extend_values(E)
+    _sam_extend_values(E)
     return E
 
 
@@ -505,3 +856,68 @@ def test_markers_at_located_positions(case):
     loc_off, locs, mk_off, got = rb.find_loc_markers_greedy_seeding(seqs, off, MIN_LENGTH, 8)
     assert split(loc_off, locs) == [w[0] for w in E.loc_mk]
     assert split(mk_off, got) == [w[1] for w in E.loc_mk]
+
+
+def _records(got):
+    return [(int(g["ext"]), int(g["nm"]), int(g["score"]), int(g["steps"]), tuple(int(v) for v in g["mis_t"]), tuple(int(v) for v in g["mis_ref"])) for g in got]
+
+
+def _same_records(got, want, what):
+    got = _records(got)
+    assert len(got) == len(want), what
+    for j, (g, x) in enumerate(zip(got, want)):
+        assert g == XM.record_tuple(x), (what, j, g, XM.record_tuple(x))
+
+
+def test_extension_walks(case, monkeypatch):
+    """leg 6: rbg_fl_info and rbg_fl_dev against fl_model, rbg_extend_left_dev against sam_extend_model.extend over the oracle, rbg_extend_right_dev against
+    fl_model.extend_right, for every budget; each once with one workgroup striding"""
+    E, rb = case
+    fl, pb = E.fl, POS_BYTES[E.name]
+    rb.fl_prepare()
+    info = rb.fl_info()
+    assert info["prepared"] and info["bytes"] == fl.bytes(pb) and info["runs"] == [fl.runs(c) for c in b"ACGT"] and info["shift"] == [fl.shift(c) for c in b"ACGT"]
+    assert info["dir_entries"] == sum((fl.count[c] >> fl.shift(c)) + 2 for c in b"ACGT")
+    left = lambda K: rb.extend_left(E.left["packed"], E.left["off"], E.left["seq"], E.left["pos"], E.left["row"], E.left["limit"], K)
+    right = lambda K: rb.extend_right(E.right["packed"], E.right["off"], E.right["seq"], E.right["pos"], E.right["row"], E.right["skip"], E.right["limit"], K)
+
+    def rows():
+        gs, gn = rb.fl(E.fl_rows)
+        bad = np.flatnonzero((gs != E.fl_sym) | (gn != E.fl_next))
+        assert len(bad) == 0, [(int(E.fl_rows[j]), int(gs[j]), int(gn[j]), int(E.fl_sym[j]), int(E.fl_next[j])) for j in bad[:5]]
+
+    rows()
+    for K in WALK_KS:
+        _same_records(left(K), E.left["want"][K], ("left", K))
+        _same_records(right(K), E.right["want"][K], ("right", K))
+    monkeypatch.setenv("RBG_SAM_GRID_CAP", "1")
+    rows()
+    _same_records(left(8), E.left["want"][8], ("left", 8, "one workgroup"))
+    _same_records(right(8), E.right["want"][8], ("right", 8, "one workgroup"))
+    monkeypatch.delenv("RBG_SAM_GRID_CAP")
+
+
+def test_sam_extended(case, monkeypatch):
+    """leg 7: rbg_align_sam_extend and rbg_align_sam_extend_both under the two tables and the cut one, with and without secondaries, max_hits 1 and 8, budgets
+    0, 2 and 4 (qualities at 4): the models' bytes; once with one workgroup striding over the batch three times"""
+    E, rb = case
+    rb.fl_prepare()
+    for table in ("small", "large", "cut"):
+        names, starts = E.x_tables[table]
+        rb.set_docs(names, starts)
+        rb.docs_prepare()
+        for K in SAM_KS:
+            ql = E.x_quals if K == 4 else None
+            for secondary in (False, True):
+                for max_hits in (1, 8):
+                    for right in (False, True):
+                        got = rb.align_sam_extend(E.x_reads, ql, E.x_names, MIN_LENGTH, max_hits, secondary, K, right=right)
+                        _same_text(got, E.x_sam[table, right, secondary, max_hits, K], (table, right, secondary, max_hits, K))
+        assert E.x_sam[table, True, True, 8, 4] != E.x_sam[table, False, True, 8, 4]
+    left = rb.align_sam_extend(E.x_reads, None, E.x_names, MIN_LENGTH, 8, True, 2)
+    both = rb.align_sam_extend(E.x_reads, None, E.x_names, MIN_LENGTH, 8, True, 2, right=True)
+    assert left != both and len(left.splitlines()) == len(both.splitlines())            # this handle's right walks moved something
+    monkeypatch.setenv("RBG_SAM_GRID_CAP", "1")
+    _same_text(rb.align_sam_extend(E.x_reads * 3, None, E.x_names * 3, MIN_LENGTH, 8, True, 2, right=True), E.x_sam["cut", True, True, 8, 2] * 3, "one workgroup")
+    _same_text(rb.align_sam_extend(E.x_reads * 3, None, E.x_names * 3, MIN_LENGTH, 8, True, 2), E.x_sam["cut", False, True, 8, 2] * 3, "one workgroup, left")
+    monkeypatch.delenv("RBG_SAM_GRID_CAP")
