@@ -146,6 +146,108 @@ def _device_locate(rb, r, order, fill32):
     return d_loc_off.cpu().numpy().view(np.uint64), locs
 
 
+# Sweeps D to G (seeds, checkpoints, marker windows, lmems) read neither the jump table (only k_runs.hip and k_jump.hip name DevIndex::jump) nor
+# the packed-read option (only find_range_host_core, capi/hostpath.ipp, loads g_opt_packed_reads): these cases build the index of another case.
+SEED_DUPLICATES = {"runs-jump16": "runs-default", "runs-default-bytes": "runs-default", "runs-default-packed": "runs-default",
+                   "slots-ks5-pos4-bytes": "slots-ks5-pos4", "slots-ks5-pos4-packed": "slots-ks5-pos4"}
+# (the four crowded-* cases: D1, D2 and D5 of a text of 637 501 symbols, 1 274 919 reads per call, the expected values made once for the four)
+SEED_CASES = [c for c in CASES if c.values[0]["text"] in ("synth", "crowded") and c.values[0]["id"] not in SEED_DUPLICATES]
+
+
+def _seed_sweeps(name, synth):
+    """the reads of sweeps D to G over a text with what the text says, made once: the session's synthetic pangenome with its markers, all reads; the
+    crowded text with sweeps.strided_markers, D1, D2 and D5 (lmems on D5)"""
+    if "seeds-" + name not in _shared:
+        X = _text(name, synth)["X"]
+        if name == "synth":
+            S = sweeps.SeedSweeps(X, synth.markers(10), sweeps.SeedItems(X))
+        else:
+            S = sweeps.SeedSweeps(X, sweeps.strided_markers(X, stride=sweeps.CROWDED_MARKER_STRIDE), sweeps.SeedItems(X, parts="12", lmem_windows=False))
+        print("sweeps D to G on %s: expected values from the text in %.1f s: %s" % (name, S.seconds, S.assert_not_vacuous(name, two_run_windows=(name == "crowded"))))
+        _shared["seeds-" + name] = S
+    return _shared["seeds-" + name]
+
+
+def _dev_reads(seqs, off):
+    import torch
+    dev = torch.device("cuda:0")
+    d_seqs = torch.from_numpy(np.concatenate([seqs, np.zeros(16 + (-len(seqs)) % 16, np.uint8)])).to(dev)
+    return d_seqs, torch.from_numpy(off.view(np.int64).copy()).to(dev)
+
+
+class _DevicePairs:
+    """rbg_greedy_seeds_plan_dev / _fill_dev and rbg_marker_seeds_plan_dev / _fill_dev behind the host calls' signatures: every output slot
+    pre-filled with -1 and one spare slot given, so that a missed or a stray write shows"""
+
+    def __init__(self, rb):
+        self.rb = rb
+
+    def get_seeds_greedy(self, seqs, off, min_length, w_sample=True):
+        import torch
+        d_seqs, d_off = _dev_reads(seqs, off)
+        dev, N, L = d_seqs.device, len(off) - 1, ra.lib()
+        st = torch.cuda.current_stream().cuda_stream
+        flags = capi.SEEDS_W_SAMPLE if w_sample else 0
+        tmp_bytes = int(L.rbg_greedy_seeds_tmp_bytes(N))
+        d_tmp = torch.empty(max(tmp_bytes, 1), dtype=torch.uint8, device=dev)
+        d_soff = torch.full((N + 1,), -1, dtype=torch.int64, device=dev)
+        assert L.rbg_greedy_seeds_plan_dev(self.rb.h, d_seqs.data_ptr(), d_off.data_ptr(), N, min_length, flags, d_soff.data_ptr(), d_tmp.data_ptr(), tmp_bytes, st) == 0
+        soff = d_soff.cpu().numpy().view(np.uint64)
+        S = int(soff[-1])
+        d_out = [torch.full((S + 1,), -1, dtype=torch.int64, device=dev) for _ in range(5)]
+        assert L.rbg_greedy_seeds_fill_dev(self.rb.h, d_seqs.data_ptr(), d_off.data_ptr(), N, min_length, flags, d_soff.data_ptr(), *[t.data_ptr() for t in d_out], st) == 0
+        torch.cuda.synchronize()
+        cols = [t.cpu().numpy() for t in d_out]
+        assert all(int(c[S]) == -1 for c in cols), "a write past the last record"
+        return (soff,) + tuple(c[:S].view(np.uint64) for c in cols)
+
+    def get_markers_greedy_seeding(self, seqs, off, wsize, max_range=MAXU, ftab_k=0):
+        import torch
+        d_seqs, d_off = _dev_reads(seqs, off)
+        dev, N, L = d_seqs.device, len(off) - 1, ra.lib()
+        st = torch.cuda.current_stream().cuda_stream
+        tmp_bytes = int(L.rbg_locate_plan_tmp_bytes(N))
+        d_tmp = torch.empty(max(tmp_bytes, 1), dtype=torch.uint8, device=dev)
+        d_soff, d_moff = (torch.full((N + 1,), -1, dtype=torch.int64, device=dev) for _ in range(2))
+        assert L.rbg_marker_seeds_plan_dev(self.rb.h, d_seqs.data_ptr(), d_off.data_ptr(), N, wsize, max_range, ftab_k, d_soff.data_ptr(), d_moff.data_ptr(),
+                                           d_tmp.data_ptr(), tmp_bytes, st) == 0
+        ns, nm = int(d_soff[-1].item()), int(d_moff[-1].item())
+        d_rec = torch.full(((ns + 1) * 6,), -1, dtype=torch.int64, device=dev)
+        d_mk = torch.full((nm + 1,), -1, dtype=torch.int64, device=dev)
+        assert L.rbg_marker_seeds_fill_dev(self.rb.h, d_seqs.data_ptr(), d_off.data_ptr(), N, wsize, max_range, ftab_k, d_soff.data_ptr(), d_moff.data_ptr(),
+                                           d_rec.data_ptr(), d_mk.data_ptr(), st) == 0
+        torch.cuda.synchronize()
+        rec, mk = d_rec.cpu().numpy(), d_mk.cpu().numpy()
+        assert (rec[ns * 6:] == -1).all() and int(mk[nm]) == -1, "a write past the last record or marker"
+        return d_soff.cpu().numpy().view(np.uint64), rec[:ns * 6].view(np.uint64).reshape(ns, 6), mk[:nm].view(np.uint64)
+
+
+@pytest.mark.parametrize("case", SEED_CASES)
+def test_seed_sweeps(synth, case):
+    """sweeps D to G (tests/sweeps.py) through the host API on one index build per configuration: every seed list, longest seed, greedy location,
+    checkpoint, marker window, marker seed and lmem record of the sweeps' reads against the text; on runs-default the device pairs too.  Exact,
+    nothing subsampled; the configurations of SEED_DUPLICATES are left out."""
+    S = _seed_sweeps(case["text"], synth)
+    X = _text(case["text"], synth)["X"]
+    rb = _load(X, case["opts"], case["env"])
+    try:
+        info = rb.info()
+        cfg = "%s (n = %d, r = %d, layout %d, %d symbols per step, %d-byte positions)" % (case["id"], X.n, len(X.heads), info.rank_layout, info.kmer_steps, info.pos_bytes)
+        assert info.rank_layout == case["opts"][O.OPT_RANK_LAYOUT] and info.n == X.n, cfg
+        if case["expect"] is not None:
+            assert case["expect"](rb) is not False, cfg
+        rb.set_markers(*S.markers)
+        took = sweeps.run_sweep_d(cfg, rb, S)
+        if case["device_api"]:
+            t = sweeps.run_sweep_d(cfg + " device pairs", _DevicePairs(rb), S, parts="df")
+            took["device pairs"] = sum(v for k, v in t.items() if k != "compared")
+        compared = took.pop("compared")
+        assert compared["G"] > (10 ** 6 if case["text"] == "synth" else 10 ** 3) and compared["D"] > 10 ** 5 and compared["F"] > 10 ** 5 and compared["E"] > 10 ** 5, (cfg, compared)
+        print("%s: seconds per sweep %s, expected records and values compared %s" % (case["id"], {k: round(v, 2) for k, v in took.items()}, compared))
+    finally:
+        rb.close()
+
+
 @pytest.mark.parametrize("case", CASES)
 def test_sweeps(synth, case):
     """sweeps A to C (tests/sweeps.py) on one index build per configuration; `parts`: A = all of sweep A, a = its lengths 1..9, B, C"""
