@@ -617,7 +617,8 @@ int rbg_tally_read_info(rbg_tally *, uint64_t out[4]);
 /* d_seqs: the reads back to back as in the host calls, in device memory, 16-BYTE ALIGNED (RBG_EARG otherwise), and the allocation must reach the next
  * multiple of 16 bytes at or past its last read's end: the kernels fetch reads as aligned 16-byte chunks (the bytes beyond a read's end are never used).
  * d_off[N + 1]: byte offsets.  Same answers as the host calls (find_range rowbowt.hpp:121-131, find_range_w_toehold :169-184); nothing is allocated, nothing
- * synchronised: graph-capturable. */
+ * synchronised: graph-capturable.  A workspace, scratch or log area declared smaller than its size function reports (tmp_bytes, ws_bytes, log_bytes) is
+ * answered with RBG_EARG before anything is enqueued: no output is touched. */
 
 int rbg_find_range_dev(rbg_index *, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t N,
                        uint64_t *d_lo, uint64_t *d_hi, void *stream);

@@ -121,6 +121,7 @@ int rbg_locate_plan_dev(rbg_index *ix, const uint64_t *d_lo, const uint64_t *d_h
     if (!queryable(ix)) return RBG_ENODEV;
     if (!ix->H().has_tsa) return RBG_ENOTLOADED;
     if (!d_loc_off || (N && (!d_lo || !d_hi || !d_tmp))) return RBG_EARG;
+    if (tmp_bytes < scan_tmp_bytes(N)) return RBG_EARG;   // (before the launcher, which has zeroed d_loc_off[0] by the time it looks)
     return launch_locate_plan(ix->dev, ix->cfg, d_lo, d_hi, N, max_hits, d_loc_off, d_tmp, tmp_bytes, stream) ? RBG_ENODEV : RBG_OK;
     });
 }
@@ -164,6 +165,7 @@ int rbg_markers_plan_dev(rbg_index *ix, const uint64_t *d_lo, const uint64_t *d_
     if (!queryable(ix)) return RBG_ENODEV;
     if (!ix->H().has_ma) return RBG_ENOTLOADED;
     if (!d_mk_off || (N && (!d_lo || !d_hi || !d_tmp))) return RBG_EARG;
+    if (tmp_bytes < scan_tmp_bytes(N)) return RBG_EARG;   // (before the count kernel is enqueued)
     return launch_markers_plan(ix->dev, ix->cfg, d_lo, d_hi, N, d_mk_off, d_tmp, tmp_bytes, stream) ? RBG_ENODEV : RBG_OK;
     });
 }

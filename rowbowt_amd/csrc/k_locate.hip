@@ -342,6 +342,7 @@ int launch_locate_plan(const DevIndex &ix, const LaunchCfg &cfg, const uint64_t 
     hipcub::TransformInputIterator<uint64_t, OccOf, hipcub::CountingInputIterator<uint64_t>> in(hipcub::CountingInputIterator<uint64_t>(0), OccOf{lo, hi, max_hits});
     size_t need = 0;
     (void)hipcub::DeviceScan::InclusiveSum(nullptr, need, in, loc_off + 1, static_cast<int64_t>(N));
+    tmp = scan_scratch(tmp, tmp_bytes);
     if (need > tmp_bytes) return static_cast<int>(hipErrorInvalidValue);
     return static_cast<int>(hipcub::DeviceScan::InclusiveSum(tmp, need, in, loc_off + 1, static_cast<int64_t>(N), st));
 }

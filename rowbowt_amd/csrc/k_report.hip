@@ -539,9 +539,8 @@ int launch_report_select(const uint64_t *seeds, const uint64_t *seed_off, const 
     if (N == 0) return static_cast<int>(hipMemsetAsync(rep_off, 0, 8, st));
     const SelectArgs a{seeds, seed_off, off2, N, first_fwd, read_len, min_seed_len, flags};
     hipLaunchKernelGGL(k_report_select_count, dim3(grid_for(N)), dim3(256), 0, st, a, rep_off);
-    size_t tb = tmp_bytes;
-    const hipError_t e = hipcub::DeviceScan::InclusiveSum(tmp, tb, rep_off + 1, rep_off + 1, static_cast<int64_t>(N), st);
-    if (e != hipSuccess) return static_cast<int>(e);
+    const int e = scan_in_place(rep_off + 1, N, tmp, tmp_bytes, st);   // (the caller's scratch: aligned and checked against the scan's need there)
+    if (e) return e;
     hipLaunchKernelGGL(k_report_select, dim3(grid_for(N)), dim3(256), 0, st, a, rep_off, static_cast<rbg_report_seed_t *>(out), out_read);
     return static_cast<int>(hipGetLastError());
 }
@@ -551,9 +550,8 @@ int launch_report_melem(const void *recs, uint64_t R, uint64_t *melem, void *tmp
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (R == 0) return static_cast<int>(hipMemsetAsync(melem, 0, 8, st));
     hipLaunchKernelGGL(k_report_mcount, dim3(grid_for(R)), dim3(256), 0, st, static_cast<const rbg_report_seed_t *>(recs), R, melem);
-    size_t tb = tmp_bytes;
-    const hipError_t e = hipcub::DeviceScan::InclusiveSum(tmp, tb, melem + 1, melem + 1, static_cast<int64_t>(R), st);
-    return static_cast<int>(e != hipSuccess ? e : hipGetLastError());
+    const int e = scan_in_place(melem + 1, R, tmp, tmp_bytes, st);   // (the caller's scratch, as above)
+    return e ? e : static_cast<int>(hipGetLastError());
 }
 
 // workspace of E elements: erec / len (4 bytes each), at (8), the scans' temporaries

@@ -145,6 +145,7 @@ int launch_sam_pick(const uint64_t *lo2, const uint64_t *hi2, const uint64_t *qs
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_sam_pick, dim3(sam_grid(N + 1, 256, cap)), dim3(256), 0, st, lo2, hi2, qs2, qe2, ss2, N, max_hits, lo, hi, k, a, b, rev, nlines, counters);
     size_t tb = tmp_bytes;
+    // (tmp and the workspace of launch_sam_plan are the library's own allocations, 256-byte aligned: never a caller's pointer)
     const hipError_t e = hipcub::DeviceScan::ExclusiveSum(tmp, tb, nlines, line_off, static_cast<int64_t>(N + 1), st);
     if (e != hipSuccess) return static_cast<int>(e);
     return static_cast<int>(hipGetLastError());

@@ -356,6 +356,7 @@ size_t tally_compact_tmp_bytes(uint64_t cap) {
     return bytes + 256;
 }
 // pos[cap + 1]: pos[i] = live slots before slot i; pos[cap] = their number
+// (tmp is the tally's own allocation -- 256-byte aligned, never a caller's pointer: no scan_scratch() needed)
 int launch_tally_compact_plan(const uint64_t *slots, uint64_t cap, uint64_t *pos, void *tmp, size_t tmp_bytes, void *stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_tally_live, dim3(tally_grid(cap)), dim3(256), 0, st, slots, cap, pos);

@@ -231,6 +231,7 @@ int launch_text_plan(const uint64_t *lo, const uint64_t *hi, const uint64_t *loc
     if (e != hipSuccess) return static_cast<int>(e);
     const int gN = static_cast<int>(std::min<uint64_t>((N + 255) / 256, 256ull * 32)), gE = static_cast<int>(std::min<uint64_t>((E + 255) / 256, 256ull * 32));
     hipLaunchKernelGGL(k_text_mark, dim3(gN), dim3(256), 0, st, loc_off, N, a.per_read, eread);
+    // (ws is the library's own allocation and every part of it starts on a 256-byte boundary: the scans' 16-byte states are aligned)
     size_t tb = tmp_bytes;
     e = hipcub::DeviceScan::InclusiveScan(tmp, tb, eread, eread, MaxOp(), static_cast<int64_t>(E), st);
     if (e != hipSuccess) return static_cast<int>(e);

@@ -541,10 +541,21 @@ void raise_lds(Kernel kernel, size_t bytes, size_t static_bytes = 0) {
     else std::fprintf(stderr, "rbg: raising a kernel's dynamic LDS limit to %zu bytes failed: %s\n", bytes, hipGetErrorString(e));
 }
 
+// A caller's scan scratch, put on a 16-byte boundary (inside the 256 spare bytes scan_tmp_bytes() adds): the scan keeps a block's {prefix, flag} state in
+// 16-byte units it reads and writes atomically, so on a scratch that is only 8-byte aligned (all the header asks for) a scan of more than one block reads
+// torn states and gets its later prefixes wrong.  A scratch that is 16-byte aligned already is used as it is.
+inline void *scan_scratch(void *tmp, size_t &tmp_bytes) {
+    const size_t skip = (0 - reinterpret_cast<uintptr_t>(tmp)) & 15;
+    if (skip > tmp_bytes) { tmp_bytes = 0; return tmp; }
+    tmp_bytes -= skip;
+    return static_cast<char *>(tmp) + skip;
+}
+
 inline int scan_in_place(uint64_t *vals, uint64_t N, void *tmp, size_t tmp_bytes, hipStream_t st) {
     if (N == 0) return 0;
     size_t need = 0;
     (void)hipcub::DeviceScan::InclusiveSum(nullptr, need, vals, vals, static_cast<int64_t>(N));
+    tmp = scan_scratch(tmp, tmp_bytes);
     if (need > tmp_bytes) return static_cast<int>(hipErrorInvalidValue);
     return static_cast<int>(hipcub::DeviceScan::InclusiveSum(tmp, need, vals, vals, static_cast<int64_t>(N), st));
 }
