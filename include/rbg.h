@@ -512,6 +512,38 @@ int rbg_align_sam_extend_both(rbg_index *, const char *seq_base, const uint64_t 
  * sequence's length, which includes the separators between documents and the terminator.  *text: NUL-terminated, through rbg_free_buffer.
  * RBG_ENOTLOADED without a document list. */
 int rbg_sam_header(rbg_index *, const char *pg_line /* nullable, appended as given */, char **text, uint64_t *text_len);
+/* ---- extract: the indexed text read back from the index -----------------------------------------------------------------------------------------
+ * The ISA sample (rbg_isa.hpp) maps a text position to the row of its suffix.  rbg_extract_prepare runs rbg_fl_prepare if needed, then builds the sample from
+ * the handle's host arrays and uploads it to THIS handle's device: pairs {tpos, row}, tpos = SA[row], of (1) the last row of every BWT run (the toehold's
+ * run-end samples) and (2) every row whose BWT symbol is not one of A C G T and that does not end its run (its SA by the host's phi rule from the run's last
+ * row downwards) -- the second group puts a sample right behind every non-base byte of the text, so no non-base byte lies between a position and the sample
+ * before it, and position 0 is always a sample.  Sorted by tpos, S entries of 2 x pos_bytes, with a directory over text position, dir[b] = the largest sample
+ * with tpos <= b << shift, shift = max(0, floor(log2(n / S))), (n >> shift) + 2 entries of the position width.  Its bytes: S * 2 * pos_bytes + ((n >> shift)
+ * + 2) * pos_bytes.  The row of p is p - q FL steps from the row of the sample {q, row_q} with the largest q <= p.  Opt-in: no load builds it, no load rule or
+ * budget changes.  Idempotent; one allocation, counted in rbg_info's hbm_bytes.  Per handle: a replica prepares its own copy (from its root's host arrays).
+ * RBG_ENOTLOADED when the handle has no toehold samples or no run arrays.  It must not overlap queries on the handle.
+ * rbg_extract_info: out[0] = prepared (0 / 1), out[1] = the sample's bytes on the device (the formula above), out[2] = S, out[3] = shift, out[4] = the
+ * directory's entries, out[5] = the samples of the second kind, out[6] = the largest gap between neighbouring samples (n closing the list): a walk-in takes
+ * fewer FL steps than that, out[7] = the build and upload time in microseconds.  Every call below answers RBG_ENOTLOADED until the handle has been prepared,
+ * and RBG_OK for M == 0 after that. */
+int rbg_extract_prepare(rbg_index *);
+int rbg_extract_info(const rbg_index *, uint64_t out[8]);
+/* The rows of M text positions, one lane per position: d_row[j] = the row of the suffix at d_pos[j] (ISA).  A position >= n gives row 0 and is reported
+ * when the kernel has run: the call WAITS for `stream` and returns RBG_EARG (the other positions are answered).  RBG_SAM_GRID_CAP caps the grid. */
+int rbg_isa_dev(rbg_index *, const uint64_t *d_pos, uint64_t M, uint64_t *d_row, void *stream);
+/* the same from host memory (RBG_EARG for a position >= n: nothing is written) */
+int rbg_isa(rbg_index *, const uint64_t *pos, uint64_t M, uint64_t *row);
+/* The text of M intervals, one lane per item: item j writes EXACTLY d_len[j] bytes at d_out + d_out_off[j] -- the bytes of the text from d_pos[j] on up to the
+ * first one that is not a base of A C G T (a separator, an N, the terminator), d_got[j] of them, then zeros.  An interval that would run past n ends at the
+ * terminator by that rule: no error.  A position >= n writes zeros, got 0, and is reported when the kernel has run: the call WAITS for `stream` and returns
+ * RBG_EARG (the other items are answered).  The items' stretches of d_out must not overlap; nothing else of d_out is touched.  One lane walks one item, so a
+ * long interval is best given as many items (rbg_extract does that).  RBG_SAM_GRID_CAP caps the grid. */
+int rbg_extract_dev(rbg_index *, const uint64_t *d_pos, const uint32_t *d_len, const uint64_t *d_out_off, uint64_t M, uint8_t *d_out /* bytes */,
+                    uint32_t *d_got /* [M] */, void *stream);
+/* The same from host memory: `out` is the concatenation of the intervals in item order (interval j at the exclusive sum of len[0 .. j)), got[j] the bases of
+ * interval j, zeros behind them.  Every interval is cut into pieces of at most RBG_OPT_EXTRACT_CHUNK bases before the upload, each an item that finds its
+ * own row; the interval ends at its first short piece, so the result does not depend on the chunk.  RBG_EARG for a pos[j] >= n (nothing is written). */
+int rbg_extract(rbg_index *, const uint64_t *pos, const uint64_t *len, uint64_t M, uint8_t *out, uint64_t *got);
 /* ---- rb_markers' report (what the tool prints), made on the device --------------------------------------------------------------
  * Everything rb_markers does between get_markers_greedy_seeding / get_markers_lmems and its output (rb_markers.cpp:228-315, :365-382,
  * :396-413, :429-519), for a batch of RAW reads: both strands (sequence 2i = read i through seq_ntoa_table -- ACGT of either case, N/n -> 'A',
@@ -1028,6 +1060,8 @@ enum { RBG_OPT_BLOCK_THREADS = 1, RBG_OPT_RANK_BUCKET_SHIFT = 2, RBG_OPT_PHI_BUC
        RBG_OPT_RUN_REC_DEPTHS = 18 /* with RBG_OPT_RUN_REC = 2: bit d - 1 = the k-mer depth d gets bucket records, the other kept depths keep their
                                   directories (0, the default: every kept depth).  An index of r = 1e9 runs has room for the records of its deepest depth
                                   but not of all (profiles/r05_pangenome_stream_r1e9.json).  RBG_RUN_REC_DEPTHS gives the initial value. */,
+       RBG_OPT_EXTRACT_CHUNK = 20 /* rbg_extract: the bases per piece an interval is cut into before the upload (1 .. 2^30; default 128, the fastest of 64 .. 4096 in profiles/extract_rate.txt).  The result
+                                  does not depend on it */,
        RBG_OPT_JUMP_K = 19 /* the jump table (rbg_jump_info): 0 = none, 16..64 = a table of that many symbols per key, -1 (default) = 60 symbols
                                   when the replica is larger than the device's 256 MB last-level cache and the table adds at most half of it, none otherwise.  RBG_JUMP_K gives the initial value. */ };
 int rbg_set_default_option(int opt, int64_t value);

@@ -22,6 +22,7 @@ DEVICE_NONE = -1
 
 OPT_BLOCK_THREADS, OPT_RANK_BUCKET_SHIFT, OPT_PHI_BUCKET_SHIFT, OPT_POS_BYTES, OPT_KMER_STEPS, OPT_HBM_BUDGET_MB, OPT_FTAB_K, OPT_PACKED_READS, OPT_DEEP_BUCKET_SHIFT, OPT_DENSE_OVERFLOW, OPT_RANK_LAYOUT = range(1, 12)
 OPT_RUN_DEPTHS, OPT_RUN_PHI, OPT_RUN_REC, OPT_RUN_REC_DEPTHS = 14, 16, 17, 18   # (12, 13, 15 were TREE_TOP_KB, SLOT_BYTES, RUN_FMT: retired with ABI 3)
+OPT_EXTRACT_CHUNK = 20   # rbg_extract: bases per piece of a split interval (the result does not depend on it)
 OPT_JUMP_K = 19          # the jump table (rbg_jump_info): 0 = off, -1 = automatic, 16..64 = symbols per key
 ABI_VERSION = 3          # include/rbg.h RBG_ABI_VERSION this binding is written against
 MAX_KMER_DEPTH = 8       # RBG_OPT_KMER_STEPS / the depth arrays of Info and LayoutInfo
@@ -245,6 +246,12 @@ _PROTOS = [
     ("rbg_fl_dev", C.c_int, [VP, VP, U64, VP, VP, VP]),
     ("rbg_extend_right_dev", C.c_int, [VP, VP, VP, U64, VP, VP, VP, VP, VP, U64, C.c_uint32, VP, VP]),
     ("rbg_align_sam_extend_both", C.c_int, [VP, VP, VP, VP, VP, VP, VP, VP, VP, U64, U64, U64, C.c_uint32, C.c_uint32, C.POINTER(VP), C.POINTER(U64)]),
+    ("rbg_extract_prepare", C.c_int, [VP]),
+    ("rbg_extract_info", C.c_int, [VP, VP]),
+    ("rbg_isa_dev", C.c_int, [VP, VP, U64, VP, VP]),
+    ("rbg_isa", C.c_int, [VP, VP, U64, VP]),
+    ("rbg_extract_dev", C.c_int, [VP, VP, VP, VP, U64, VP, VP, VP]),
+    ("rbg_extract", C.c_int, [VP, VP, VP, U64, VP, VP]),
     ("rbg_set_default_option", C.c_int, [C.c_int, C.c_int64]),
     ("rbg_get_default_option", C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
 ]
@@ -820,6 +827,58 @@ class RowBowt:
             sym, nxt = d_sym.cpu().numpy()[:M].copy(), d_next.cpu().numpy()[:M].view(np.uint64).copy()
         _check(rc, "rbg_fl_dev")
         return sym, nxt
+
+    def extract_prepare(self):
+        """rbg_extract_prepare: the ISA sample (text position -> row, by samples and an FL walk) on this handle's device; runs fl_prepare if needed;
+        idempotent, opt-in"""
+        _check(self.L.rbg_extract_prepare(self.h), "rbg_extract_prepare")
+
+    def extract_info(self):
+        """rbg_extract_info -> dict: prepared, bytes, samples, shift, dir_entries, second_kind, max_gap, build_us"""
+        out = np.zeros(8, np.uint64)
+        _check(self.L.rbg_extract_info(self.h, _p(out)), "rbg_extract_info")
+        keys = ("bytes", "samples", "shift", "dir_entries", "second_kind", "max_gap", "build_us")
+        return dict(prepared=bool(out[0]), **{k: int(v) for k, v in zip(keys, out[1:])})
+
+    def isa(self, pos):
+        """rbg_isa_dev: uint64[M], the row of the suffix at each text position.  Through torch"""
+        import torch
+        pos = _u64(pos)
+        M = len(pos)
+        with torch.cuda.device(self.info().device):
+            d_pos = torch.from_numpy(pos.view(np.int64)).cuda()
+            d_row = torch.full((max(M, 1),), -6, dtype=torch.int64, device="cuda")
+            rc = self.L.rbg_isa_dev(self.h, d_pos.data_ptr() if M else None, M, d_row.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            row = d_row.cpu().numpy()[:M].view(np.uint64).copy()
+        _check(rc, "rbg_isa_dev")
+        return row
+
+    def extract_dev(self, d_pos, d_len, d_out_off, d_out, d_got):
+        """rbg_extract_dev over torch tensors on this handle's device: d_pos int64[M], d_len int32[M], d_out_off int64[M], d_out uint8[...], d_got int32[M];
+        item j writes exactly d_len[j] bytes at d_out[d_out_off[j]:] (the bases, then zeros) and d_got[j].  Waits for the current stream"""
+        import torch
+        M = int(d_pos.numel())
+        assert int(d_len.numel()) == M and int(d_out_off.numel()) == M and int(d_got.numel()) >= M
+        assert d_pos.element_size() == 8 and d_out_off.element_size() == 8 and d_len.element_size() == 4 and d_got.element_size() == 4 and d_out.element_size() == 1
+        with torch.cuda.device(self.info().device):
+            ptr = lambda t: t.data_ptr() if M else None
+            rc = self.L.rbg_extract_dev(self.h, ptr(d_pos), ptr(d_len), ptr(d_out_off), M, ptr(d_out), ptr(d_got), torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+        _check(rc, "rbg_extract_dev")
+
+    def extract(self, pos, length):
+        """rbg_extract from host memory: (bytes, got) -- the concatenation of the intervals in item order, interval j at the exclusive sum of the lengths: got[j]
+        bases from pos[j] on (up to the first byte that is no base), then zeros.  A single position and length give (bytes, int)"""
+        one = np.isscalar(pos)
+        pos, length = _u64(np.atleast_1d(pos)), _u64(np.atleast_1d(length))
+        if len(pos) != len(length):
+            raise ValueError("extract: a length per position")
+        out = np.full(max(int(length.sum()), 1), 0xA5, np.uint8)
+        got = np.zeros(max(len(pos), 1), np.uint64)
+        _check(self.L.rbg_extract(self.h, _p(pos), _p(length), len(pos), _p(out), _p(got)), "rbg_extract")
+        text = out[:int(length.sum())].tobytes()
+        return (text, int(got[0])) if one else (text, got[:len(pos)].copy())
 
     def extend_right(self, seqs, off, item_seq, item_b, item_row, item_skip, item_limit, max_mismatch=4):
         """rbg_extend_right_dev: the FL walk alone -- item j takes item_skip[j] FL steps from row item_row[j], then goes right from position item_b[j] of

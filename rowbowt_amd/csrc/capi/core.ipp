@@ -90,6 +90,8 @@ struct rbg_index {
     // rbg_fl_prepare: the FL index (rbg_fl.hpp) on THIS handle's device, one allocation of its own (also in `allocs`).  Per handle and not in DevIndex, like
     // doc_dev: a replica prepares its own copy from the root's host run arrays, which never change after the load
     struct FlDev { void *blob = nullptr; FlView view{}; uint64_t bytes = 0, runs[kFlBases] = {}, dir_entries = 0; double build_ms = 0.0; } fl_dev;
+    // rbg_extract_prepare: the ISA sample (rbg_isa.hpp) on THIS handle's device, one allocation of its own (also in `allocs`), per handle like fl_dev
+    struct IsaDev { void *blob = nullptr; IsaView view{}; uint64_t bytes = 0, samples = 0, dir_entries = 0, second_kind = 0, max_gap = 0; double build_ms = 0.0; } isa_dev;
     std::mutex mu;              // guards marker/doc attachment only; queries are lock-free
 };
 
@@ -142,6 +144,7 @@ std::atomic<int64_t> g_opt_run_depths{env_opt("RBG_RUN_DEPTHS", 0, 0, (1 << kMax
 std::atomic<int64_t> g_opt_run_phi{env_opt("RBG_RUN_PHI", 0, 0, 2)};   // run-indexed layout, format 2: 0 = automatic, 1 = phi over the sampled-position list (12-16 bytes per run), 2 = phi SLOTS of about n/r rows (about 54 bytes per run at 8-byte positions; one sector per step instead of two)
 std::atomic<int64_t> g_opt_run_rec_depths{env_opt("RBG_RUN_REC_DEPTHS", 0, 0, (1 << kMaxRunDepth) - 1)};   // with RBG_OPT_RUN_REC = 2: the depths (bit d - 1) that get bucket records; 0 = every kept depth
 std::atomic<int64_t> g_opt_run_rec{env_opt("RBG_RUN_REC", 0, 0, 2)};   // run-indexed layout, format 2: bucket records (rbg_dev.h RunRec2) -- 0 = automatic (when the replica with them stays within half the budget), 1 = off, 2 = on
+std::atomic<int64_t> g_opt_extract_chunk{128};   // rbg_extract: bases per piece of a split interval (RBG_OPT_EXTRACT_CHUNK)
 std::atomic<int64_t> g_opt_packed_reads{1};  // host-pointer calls: 0 bytes over PCIe, 1 (default) 2-bit codes for batches >= 4096, 2 always
 
 // RBG_ASSUME_FREE_HBM_MB (tests only; rbg_load_plan.hpp assumed_free_hbm): read HERE and nowhere else.  `given`: the variable is set at all -- the budget raise

@@ -680,6 +680,9 @@ int rbg_set_default_option(int opt, int64_t value) {
         case RBG_OPT_JUMP_K:
             if (value < -1 || value > static_cast<int64_t>(kJumpMaxK) || (value > 0 && value < static_cast<int64_t>(kJumpMinK))) return RBG_EARG;
             g_opt_jump_k = value; return RBG_OK;
+        case RBG_OPT_EXTRACT_CHUNK:
+            if (value < 1 || value > (int64_t(1) << 30)) return RBG_EARG;
+            g_opt_extract_chunk = value; return RBG_OK;
         default: return RBG_EARG;
     }
     });
@@ -705,6 +708,7 @@ int rbg_get_default_option(int opt, int64_t *value) {
         case RBG_OPT_RUN_REC: *value = g_opt_run_rec.load(); return RBG_OK;
         case RBG_OPT_RUN_REC_DEPTHS: *value = g_opt_run_rec_depths.load(); return RBG_OK;
         case RBG_OPT_JUMP_K: *value = g_opt_jump_k.load(); return RBG_OK;
+        case RBG_OPT_EXTRACT_CHUNK: *value = g_opt_extract_chunk.load(); return RBG_OK;
         default: return RBG_EARG;
     }
     });

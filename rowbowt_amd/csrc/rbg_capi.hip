@@ -30,6 +30,7 @@
 #include "rbg_jump.h"
 #include "rbg_docdir.hpp"
 #include "rbg_fl.hpp"
+#include "rbg_isa.hpp"
 #include "rbg_sam.hpp"
 #include "rbg_host.hpp"
 
@@ -49,5 +50,6 @@
 #include "capi/loc_markers.ipp"   // the text-position marker table, markers at located positions (rb_locs' path)
 #include "capi/docs.ipp"          // the document table on the device, documents of located positions (rbg_doc_hits*, rbg_resolve_offsets_dev*)
 #include "capi/fl.ipp"            // the FL index on the device (rbg_fl_prepare), FL of rows, the right extension of located seeds (fl_extend.hip)
+#include "capi/extract.ipp"       // the ISA sample on the device (rbg_extract_prepare), rows of text positions, the text of intervals (extract.hip)
 #include "capi/sam.ipp"           // rbg_align_sam: SAM lines of raw reads, both strands, written on the device; rbg_sam_header
 #include "capi/replicas.ipp"      // replicas in one process, counters, RCCL

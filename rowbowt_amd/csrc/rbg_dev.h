@@ -12,6 +12,7 @@
 
 #include "rbg_mkdir.hpp"
 #include "rbg_fl.hpp"
+#include "rbg_isa.hpp"
 
 namespace rbg {
 
@@ -583,6 +584,13 @@ int launch_sam_right_items(const SamBatch &B, void *ws, const void *ext_left, ui
                            uint32_t *item_skip, uint64_t *item_limit, uint32_t *item_k, uint32_t cap, void *stream);
 int launch_sam_both_len(const SamBatch &B, void *ws, const void *ext, const void *ext_right, uint32_t cap, void *stream);
 int launch_sam_both_fill(const SamBatch &B, void *ws, const void *ext, const void *ext_right, uint64_t total, char *text, uint32_t cap, void *stream);
+// the text read back from the index (extract.hip; rbg_isa_dev, rbg_extract_dev; the structures: rbg_isa.hpp, rbg_fl.hpp).  launch_isa_rows: M text positions ->
+// the rows of their suffixes; launch_extract: M items {pos, len, out_off} -> len bytes each at out + out_off (the bases up to the first row without one, then
+// zeros) and got[j] = the bases.  *d_err |= 1 for a position >= n (row 0 / len zeros, got 0), |= 2 for a walk-in that met a row without a base.
+int launch_isa_rows(const FlView &fl, const IsaView &isa, uint32_t pos_bytes, const uint64_t *pos, uint64_t M, uint64_t *row, unsigned int *d_err, uint32_t cap,
+                    void *stream);
+int launch_extract(const FlView &fl, const IsaView &isa, uint32_t pos_bytes, const uint64_t *pos, const uint32_t *len, const uint64_t *out_off, uint64_t M,
+                   uint8_t *out, uint32_t *got, unsigned int *d_err, uint32_t cap, void *stream);
 // run-indexed layout from run lists already on the device (k_build.hip): the tables' directories, 8-byte samples packed to 6
 int launch_run_dirs(uint32_t pos_bytes, const void *ent, const uint64_t *first, const uint64_t *nruns, const uint64_t *doff, const uint32_t *dshift,
                     uint32_t T, uint64_t total, uint32_t *dir, void *stream);

@@ -221,6 +221,30 @@ class RowBowt {
     }
     // the FL index on this handle's device (rbg_fl_prepare: idempotent, opt-in), which align_sam_extend_both needs
     void fl_prepare() { detail::check(rbg_fl_prepare(ix_.get()), "rbg_fl_prepare"); }
+    // the ISA sample on this handle's device (rbg_extract_prepare: runs fl_prepare if needed; idempotent, opt-in), which isa and extract need
+    void extract_prepare() { detail::check(rbg_extract_prepare(ix_.get()), "rbg_extract_prepare"); }
+    // the rows of the suffixes at text positions (rbg_isa)
+    std::vector<uint64_t> isa(const std::vector<uint64_t> &positions) const {
+        std::vector<uint64_t> rows(positions.size());
+        detail::check(rbg_isa(ix_.get(), positions.data(), positions.size(), rows.data()), "rbg_isa");
+        return rows;
+    }
+    uint64_t isa(uint64_t position) const { return isa(std::vector<uint64_t>{position})[0]; }
+    // the text of intervals (rbg_extract): text[j] holds the got[j] bases from pos[j] on -- up to len[j], ending before the first byte that is no base
+    struct Extracted { std::vector<std::string> text; std::vector<uint64_t> got; };
+    Extracted extract(const std::vector<uint64_t> &pos, const std::vector<uint64_t> &len) const {
+        if (pos.size() != len.size()) detail::die("extract: a length per position", RBG_EARG);
+        uint64_t total = 0;
+        for (const uint64_t l : len) total += l;
+        std::string out(total, '\0');
+        Extracted r;
+        r.got.resize(pos.size());
+        detail::check(rbg_extract(ix_.get(), pos.data(), len.data(), pos.size(), reinterpret_cast<uint8_t *>(&out[0]), r.got.data()), "rbg_extract");
+        uint64_t at = 0;
+        for (size_t j = 0; j < pos.size(); at += len[j], ++j) r.text.push_back(out.substr(at, r.got[j]));
+        return r;
+    }
+    std::string extract(uint64_t pos, uint64_t len) const { return extract(std::vector<uint64_t>{pos}, std::vector<uint64_t>{len}).text[0]; }
     // align_sam_extend's lines with the right clip extended too, by an FL walk with what the left walk left of the budget (rbg_align_sam_extend_both)
     std::string align_sam_extend_both(const std::vector<std::string> &seqs, const std::vector<std::string> &quals, const std::vector<std::string> &names,
                                       uint64_t min_length = 20, uint64_t max_hits = 16, bool secondary = false, uint32_t max_mismatch = 4) const {
