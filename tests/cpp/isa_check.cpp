@@ -24,6 +24,8 @@ static unsigned long long g_checks = 0;
 // what the shapes below must show at least once
 struct Seen {
     unsigned shift0 = 0, empty_bucket = 0, bisected = 0, first_last = 0, interior_other = 0, second_kind = 0;
+    unsigned long_other_run = 0;      // a non-base BWT run of at least 16 rows
+    unsigned other_pair = 0;          // two non-base bytes side by side in the text
 };
 
 struct Host {      // what HostIndex holds of a text
@@ -87,13 +89,15 @@ static void check_index(const Host &h, const IsaIndex &X, const FlIndex &FLX, Se
     }
     CHECK(gap == X.max_gap);
     uint64_t second = 0;
-    for (uint64_t g = 0; g + 1 < h.run_start.size(); ++g)
+    for (uint64_t g = 0; g + 1 < h.run_start.size(); ++g) {
+        seen.long_other_run += !isa_is_base(h.heads[g]) && h.run_start[g + 1] - h.run_start[g] >= 16;
         for (uint64_t row = h.run_start[g]; row < h.run_start[g + 1]; ++row) {
             const bool last = row + 1 == h.run_start[g + 1], other = !isa_is_base(h.heads[g]);
             CHECK(is_sample_row[row] == ((last || other) ? 1 : 0));
             second += other && !last;
             seen.interior_other += other && !last && row > h.run_start[g];      // neither the first nor the last row of its run
         }
+    }
     CHECK(second == X.second_kind && S == h.heads.size() + second);
     seen.second_kind += second > 0;
     // the directory: dir[b] = the largest sample at or before b << shift
@@ -123,6 +127,8 @@ static void check_index(const Host &h, const IsaIndex &X, const FlIndex &FLX, Se
 
 static void check_text(const std::string &text, Seen &seen) {
     const Host h = host_of(text);
+    for (size_t i = 0; i + 2 < text.size(); ++i)
+        seen.other_pair += !isa_is_base(static_cast<uint8_t>(text[i])) && !isa_is_base(static_cast<uint8_t>(text[i + 1]));
     for (uint32_t pb : {4u, 8u}) {
         IsaIndex X;
         FlIndex FLX;
@@ -187,6 +193,25 @@ int main() {
     std::string docs = unit + "#N" + unit.substr(10, 60) + "NNNNN" + unit.substr(40, 45) + "#" + unit.substr(0, 30) + "N" + unit.substr(31) + "#" + unit;
     check_text(docs + '\x01', seen);                                               // separators, a run of N, a document that starts with N
     check_text(std::string("NNNNNNNN") + unit + unit + "NNNNNNNN" + unit + '\x01', seen);
+    // a collection of near copies: 40 documents of 60 bases with two substitutions each, joined by '#'; every 7th starts with N (the text itself too), every
+    // 11th ends with N ("N#"), every 5th holds a run of 1 to 9 N, and one document is empty ("##")
+    const std::string stem = random_bases(60);
+    std::string many;
+    for (int d = 0; d < 40; ++d) {
+        std::string u = stem;
+        for (int k = 0; k < 2; ++k) { const size_t at = rnd() % 60; u[at] = "ACGT"[(std::string("ACGT").find(u[at]) + 1 + rnd() % 3) & 3]; }
+        if (d % 5 == 0) u.replace(10 + rnd() % 30, 1 + (d * 3) % 9, std::string(1 + (d * 3) % 9, 'N'));
+        if (d % 7 == 0) u[0] = 'N';
+        if (d % 11 == 0) u[u.size() - 1] = 'N';
+        if (d) many += '#';
+        if (d == 17) many += '#';
+        many += u;
+    }
+    CHECK(many[0] == 'N' && many.find("##") != std::string::npos && many.find("N#") != std::string::npos && many.find("NNNNNNN") != std::string::npos);
+    const Seen before_many = seen;
+    check_text(many + '\x01', seen);
+    CHECK(seen.long_other_run > before_many.long_other_run && seen.other_pair > before_many.other_pair);
+    CHECK(seen.long_other_run && seen.other_pair);
     CHECK(seen.shift0 && seen.empty_bucket && seen.bisected && seen.first_last && seen.interior_other && seen.second_kind);
     check_wide();
     std::printf("isa host ok %llu checks\n", g_checks);
