@@ -3,6 +3,7 @@
 
 #include "rbg_device.hpp"
 #include "rbg_launch.hpp"
+#include "rbg_chain_walk.hpp"
 #include "rbg_locate_docs.hpp"
 
 namespace rbg {
@@ -10,7 +11,8 @@ namespace {
 
 // ---- K3: locate (the counts of the plan are computed where its scan reads them: OccOf below) ---------
 // ---- the locus order's sort key (rbg_dev.h order_docs): k <-> {offset >> low, document, offset & (2^low - 1)} -----------------------------
-// A toehold outside the text (it wrapped below zero: k >= n) has no document: its key is all ones and K3 reads the toehold itself.
+// A toehold outside the text (it wrapped below zero: k >= n) has no document: its key is all ones and K3 reads the toehold itself.  The inverse, for the
+// chain walks, is rbg_chain_walk.hpp chain_toehold: the two change together.
 __device__ __forceinline__ uint64_t locus_key(const DevIndex &ix, const uint64_t k) {
     if (k >= ix.n) return ~uint64_t(0);
     uint32_t a = 0, z = ix.order_ndocs;          // the last document that starts at or before k (doclist.hpp:46-50: a predecessor query)
@@ -21,12 +23,6 @@ __device__ __forceinline__ uint64_t locus_key(const DevIndex &ix, const uint64_t
     const uint64_t o = k - ix.order_docs[a];
     const uint32_t low = ix.order_lowbits, db = ix.order_dbits;
     return ((o >> low) << (db + low)) | (static_cast<uint64_t>(a) << low) | (o & ((uint64_t(1) << low) - 1u));
-}
-__device__ __forceinline__ uint64_t locus_toehold(const DevIndex &ix, const uint64_t key, const uint64_t *__restrict__ k, const uint64_t i) {
-    if (key == ~uint64_t(0)) return k[i];
-    const uint32_t low = ix.order_lowbits, db = ix.order_dbits;
-    const uint64_t doc = (key >> low) & ((uint64_t(1) << db) - 1u);
-    return ix.order_docs[doc] + (((key >> (db + low)) << low) | (key & ((uint64_t(1) << low) - 1u)));
 }
 // 4-byte positions, absolute order: the sort moves 32-bit keys (a third fewer bytes per radix pass than 64-bit ones).  A toehold outside the text
 // (it wrapped below zero) travels as 0xFFFFFFFF -- no position of an index with 4-byte positions -- and K3 reads the toehold itself.
@@ -106,11 +102,18 @@ __device__ __forceinline__ uint64_t phi_step(const DevIndex &ix, uint64_t i, boo
     return s;
 }
 
-// One lane walks one read's phi chain (toehold_sa.hpp:37-49); the chain is serial, the reads are not.  The values are staged per wave in LDS,
-// kChunk steps at a time, and flushed as WINDOWS of kChunk locations on boundaries of the output array, kChunk lanes per read (rbg_device.hpp
-// ChainStage: what is staged, why, and what it costs in LDS).  Eight steps = 64-byte windows at both position widths since the windows are
-// aligned (profiles/r06_k3_ring_ab.txt); with unaligned segments sixteen steps were better at 4-byte positions (3.5 / 3.1 / 3.5 ms per 10 M
-// reads at 8 / 16 / 32, round 3) -- a 64-byte store on a 64-byte boundary runs at 2.9 TB/s, a 128-byte one wherever it falls at 1.2.
+// phi_step as the chain walks take it (rbg_chain_walk.hpp, rbg_locate_docs.hpp): under STATS a searched step (an overflowing slot) adds 1 to `cost`
+template <typename P, bool STATS = false>
+__device__ __forceinline__ uint64_t slot_phi(const DevIndex &ix, const uint64_t k1, unsigned long long &cost) {
+    if (!STATS) return phi_step<P>(ix, k1);
+    bool searched = false;
+    const uint64_t s = phi_step<P>(ix, k1, &searched);
+    cost += searched ? 1 : 0;
+    return s;
+}
+
+// K3 over the phi slots: rbg_chain_walk.hpp chain_fill_walk (the walk, its staging and what the template parameters mean) with phi_step as its phi.
+// Flush windows of eight locations = 64 bytes at both position widths (the measurements: rbg_chain_walk.hpp).
 #ifndef RBG_K3_CHUNK_U32
 #define RBG_K3_CHUNK_U32 8
 #endif
@@ -119,11 +122,6 @@ constexpr int kChunk = RBG_K3_CHUNK_U32;
 #define RBG_K3_CHUNK_U64 8
 #endif
 
-// STATS = the instrumented instantiation (rbg_locate_fill_stats_dev): the same walk plus the LocateStat sums.
-// OUT = the width a location is stored at: uint64_t (the API's, toehold_sa.hpp:37-49 fills a vector<uint64_t>) or, for
-// device pipelines on an index with 4-byte positions, uint32_t (rbg_locate_fill_dev32: half the write requests; the low
-// 32 bits of the same values, so a toehold that wrapped below zero reads 0xFFFFFFFF).
-// SUB = `sub` is subtracted from every location (locate_from_longest_seed, rowbowt.hpp:681-683).
 template <typename P, bool STATS = false, typename OUT = uint64_t, bool SUB = false, bool HI8 = false, int CH = (sizeof(P) == 8 ? RBG_K3_CHUNK_U64 : kChunk), bool RING = true>
 __global__ __launch_bounds__(256, (chain_stage_waves<ChainStage<P, CH, SUB, RING, HI8>>())) void k_locate_fill(const DevIndex ix, const uint64_t *__restrict__ lo,
                                                         const uint64_t *__restrict__ hi, const uint64_t *__restrict__ k,
@@ -134,91 +132,8 @@ __global__ __launch_bounds__(256, (chain_stage_waves<ChainStage<P, CH, SUB, RING
                                                         unsigned long long *__restrict__ stats = nullptr) {
     using Stage = ChainStage<P, CH, SUB, RING, HI8>;
     __shared__ Stage S;
-    const uint64_t out_elem0 = reinterpret_cast<uintptr_t>(locs) / sizeof(OUT);
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & (kWave - 1);
-    unsigned long long c_locs = 0;
-    unsigned long long st_phi = 0, st_ovf = 0, st_chains = 0;  // STATS only
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
-    for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * blockDim.x + wv * kWave; base < N; base += stride) {
-        // `order` (optional) lists the reads by toehold text position: neighbouring lanes then walk
-        // neighbouring phi slots (same DRAM rows / L2 lines) for the whole chain, because the chains of
-        // reads from nearby loci visit the haplotypes in the same order.  Results land at loc_off[i]
-        // whatever the processing order.
-        const uint64_t j = base + lane;
-        uint64_t i = j;
-        if (order && j < N) i = order[j];
-        uint64_t occ = 0, k1 = 0, dst = 0;
-        if (i < N) {
-            dst = loc_off[i];
-            if (skeys) {
-                // ordered walk: the toehold travels with the sort (sequential read) and the count is the
-                // planned one, loc_off[i+1] - loc_off[i] = min(occ, max_hits): one random 64-byte sector
-                // per read instead of four (lo, hi, k, loc_off)
-                if (ix.order_docs) k1 = locus_toehold(ix, skeys[j], k, i);
-                else if (sizeof(P) == 4) { const uint32_t k32 = reinterpret_cast<const uint32_t *>(skeys)[j]; k1 = k32 == 0xFFFFFFFFu ? k[i] : k32; }   // (k_keys32)
-                else k1 = skeys[j];
-                occ = loc_off[i + 1] - dst;
-            } else {
-                const uint64_t l = lo[i], h = hi[i];
-                occ = h >= l ? h - l + 1 : 0;  // toehold_sa.hpp:38-39
-                if (occ > max_hits) occ = max_hits;
-                k1 = k[i];
-            }
-        }
-        const uint64_t minus = (SUB && i < N) ? sub[i] : 0;
-        // the window grid of this read: its first location sits a elements past a CH-element boundary of the output array (RING; else a = 0)
-        const uint32_t a = (RING && occ) ? static_cast<uint32_t>((out_elem0 + dst) & static_cast<uint64_t>(CH - 1)) : 0u;
-        S.dst[wv][lane] = dst - a;   // (wraps for a read at the very start of a misaligned array; + v >= a brings it back)
-        if (SUB) S.minus[wv][lane] = minus;
-        // the toehold itself is not a text position when it wrapped (2^64 - 1): at 4-byte positions its owner stores that location (ChainStage)
-        const bool off_text = Stage::kSentinel && k1 >= ix.n;
-        if (off_text && occ) locs[dst] = static_cast<OUT>(k1 - minus);
-        c_locs += occ;
-        if (STATS && occ) st_chains += 1;
-        uint64_t wmax = occ + a;      // the chain's extent in virtual columns
-#pragma unroll
-        for (int o = kWave / 2; o > 0; o >>= 1) {
-            const uint64_t other = __shfl_xor(wmax, o, kWave);
-            wmax = other > wmax ? other : wmax;
-        }
-        for (uint64_t t0 = 0; t0 < wmax; t0 += CH) {
-            const uint32_t cnt = chain_round_count<CH>(occ, t0);
-            S.bounds[wv][lane] = chain_window_bounds<CH>(occ, a, t0);
-#pragma unroll
-            for (int e = 0; e < CH; ++e) {
-                if (static_cast<uint32_t>(e) < cnt) {
-                    if (e || t0) {   // every location but a read's first is phi of the one before (toehold_sa.hpp:44)
-                        if (STATS) {
-                            bool searched = false;
-                            k1 = phi_step<P>(ix, k1, &searched);
-                            st_phi += 1;
-                            st_ovf += searched ? 1 : 0;
-                        } else {
-                            k1 = phi_step<P>(ix, k1);
-                        }
-                    }
-                    chain_put(S, wv, lane, a + static_cast<uint32_t>(t0) + e, k1, e == 0 && t0 == 0 && off_text);
-                }
-            }
-            wave_lds_sync();
-            chain_flush(S, wv, lane, t0, locs);
-            wave_lds_sync();
-        }
-        wave_lds_sync();
-    }
-    c_locs = wave_sum(c_locs);
-    if (lane == 0 && c_locs) atomicAdd(&ix.counters[3], c_locs);
-    if (STATS) {
-        st_phi = wave_sum(st_phi);
-        st_ovf = wave_sum(st_ovf);
-        st_chains = wave_sum(st_chains);
-        if (lane == 0) {
-            if (st_phi) atomicAdd(&stats[kLsPhiSteps], st_phi);
-            if (st_ovf) atomicAdd(&stats[kLsPhiOvf], st_ovf);
-            if (st_chains) atomicAdd(&stats[kLsChains], st_chains);
-            if (c_locs) atomicAdd(&stats[kLsLocs], c_locs);
-        }
-    }
+    chain_fill_walk<P, OUT, STATS, SUB, HI8, CH, CH>(ix, S, lo, hi, k, N, max_hits, loc_off, locs, sub, order, skeys, stats,
+                                                     [&](const uint64_t k1, unsigned long long &cost) { return slot_phi<P, STATS>(ix, k1, cost); });
 }
 
 // ---- document hits from the walk itself (rbg_locate_docs.hpp): k_locate_fill's chains, the positions resolved and reduced instead of stored ----
@@ -231,7 +146,7 @@ __global__ __launch_bounds__(kLocDocBlock) void k_locate_docs(const DevIndex ix,
                                                              uint32_t *__restrict__ ndocs_out, uint32_t *__restrict__ nodoc_out,
                                                              unsigned long long *__restrict__ doc_reads, unsigned long long *__restrict__ doc_locs) {
     locate_docs_walk<P, LOCS>(ix, t, locate_docs_lds, lo, hi, k, N, max_hits, order, skeys, sets, ndocs_out, nodoc_out, doc_reads, doc_locs,
-                              [&](const uint64_t k1) { return phi_step<P>(ix, k1); });
+                              [&](const uint64_t k1, unsigned long long &cost) { return slot_phi<P>(ix, k1, cost); });
 }
 
 }  // namespace
@@ -357,30 +272,12 @@ int launch_locate_fill(const DevIndex &ix, const LaunchCfg &cfg, const uint64_t 
     // the order workspace also holds the toeholds in sorted order (launch_locate_order's key output)
     const uint64_t *skeys = order ? reinterpret_cast<const uint64_t *>(static_cast<const char *>(order) + order_layout(N).keys) : nullptr;
     const uint32_t *perm = static_cast<const uint32_t *>(order);
-    // (Line-aligned flush segments -- a lane waiting `dst mod CH` columns before its first step so that every flush writes whole lines -- lost twice
-    //  and were retired with the round-3 staging: on the bench index in round 3, and at r = 1.2e8 in round 6 (11.1 -> 14.9 ms, profiles/
-    //  r06_k3_align_ab.txt): lanes that wait a different number of columns fall out of PHASE, and chains of one locus walking in phase --
-    //  neighbouring lanes asking for the same phi sector in the same instruction -- is what K3's speed rests on.)
-    if ((stats || locs32) && sub) return static_cast<int>(hipErrorInvalidValue);
     if (ix.layout == 2 && !ix.phi_slots) {  // run-indexed layout (k_runs.hip); with phi slots (RBG_OPT_RUN_PHI) the slot kernels below answer its phi
         return launch_locate_fill_runs(ix, cfg, lo, hi, k, N, max_hits, loc_off, locs, sub, order, skeys, stream, stats, locs32);
     }
-    // (rbg_device.hpp ChainStage: a value as its low word + one high byte; RBG_K3_HI8=0 -- tests -- stages whole 8-byte values at any n)
-    const bool hi8 = ix.pos_bytes == 8 && ix.n < kChainHi8Limit && chain_hi8_enabled();
-    if (locs32 && ix.pos_bytes != 4) return static_cast<int>(hipErrorInvalidValue);   // 4-byte locations: 4-byte positions only (the caller checked)
-    return with_pos(ix.pos_bytes, [&](auto p) {
-        using P = pos_t<decltype(p)>;
-        // the variants that exist: instrumented, sub-ranges, plain, and at 4-byte positions 4-byte locations; HI8 at 8-byte positions only
-        auto fill = [&](auto sts, auto sb, auto *dst) {
-            return with_flag(hi8, [&](auto h8) {
-                return launch_grid(k_locate_fill<P, decltype(sts)::value, std::remove_pointer_t<decltype(dst)>, decltype(sb)::value, sizeof(P) == 8 && decltype(h8)::value>,
-                                   grid, block, 0, stream, ix, lo, hi, k, N, max_hits, loc_off, dst, sub, perm, skeys, stats);
-            });
-        };
-        if constexpr (sizeof(P) == 4) { if (locs32) return fill(no, no, locs32); }
-        if (stats) return fill(yes, no, locs);
-        if (sub) return fill(no, yes, locs);
-        return fill(no, no, locs);
+    return chain_fill_variants(ix, stats, sub, locs, locs32, [&](auto p, auto sts, auto sb, auto h8, auto *dst) {
+        return launch_grid(k_locate_fill<pos_t<decltype(p)>, decltype(sts)::value, std::remove_pointer_t<decltype(dst)>, decltype(sb)::value, decltype(h8)::value>,
+                           grid, block, 0, stream, ix, lo, hi, k, N, max_hits, loc_off, dst, sub, perm, skeys, stats);
     });
 }
 

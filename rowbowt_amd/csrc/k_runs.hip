@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "rbg_runs2_device.hpp"
+#include "rbg_chain_walk.hpp"
 #include "rbg_locate_docs.hpp"
 #include "rbg_jump.h"
 #include "rbg_launch.hpp"
@@ -336,17 +337,11 @@ __global__ __launch_bounds__(512, STATS ? 2 : 4) void k_find_range_runs(const De
 }
 
 template <typename P> struct ChunkR { static constexpr int v = 8; };   // as in k_locate.hip (flush windows of eight locations: 64 bytes)
-// the toehold of a locus key (k_locate.hip locus_key / locus_toehold: the chains' order by locus)
-__device__ __forceinline__ uint64_t locus_toehold_r(const DevIndex &ix, const uint64_t key, const uint64_t *__restrict__ k, const uint64_t i) {
-    if (key == ~uint64_t(0)) return k[i];
-    const uint32_t low = ix.order_lowbits, db = ix.order_dbits;
-    const uint64_t doc = (key >> low) & ((uint64_t(1) << db) - 1u);
-    return ix.order_docs[doc] + (((key >> (db + low)) << low) | (key & ((uint64_t(1) << low) - 1u)));
-}
 
 // ---- K3 over the run-indexed layout: ToeholdSA::locate_range (toehold_sa.hpp:37-49) -- every lane walks its own chain and
-// answers its own phi (toehold_sa.hpp:56-72; rbg_runs2_device.hpp lane_phi).  The chains, the staging of the values in LDS and
-// the coalesced flush are k_locate_fill's (k_locate.hip; chains in toehold order); a phi step is one directory
+// answers its own phi (toehold_sa.hpp:56-72; rbg_runs2_device.hpp run_phi).  The chains, the staging of the values in LDS and
+// the coalesced flush are k_locate_fill's: one body, rbg_chain_walk.hpp chain_fill_walk (chains in toehold order), its step
+// loop not unrolled here (the phi step is long); a phi step is one directory
 // gather (two neighbouring counts, plus the super count at 8-byte positions) and one scan of the bucket's few sampled
 // positions, no cross-lane traffic.  Works for ordered and unordered walks alike (the order only decides how well
 // neighbouring lanes share sectors).  STATS: [kLsPhiSteps] phi evaluations, [kLsPhiOvf] sampled positions the scans
@@ -359,98 +354,14 @@ __global__ __launch_bounds__(256, 4) void k_locate_fill_runs2(const DevIndex ix,
                                                           const uint64_t *__restrict__ sub, const uint32_t *__restrict__ order,
                                                           const uint64_t *__restrict__ skeys, unsigned long long *__restrict__ stats) {
     constexpr int kChunkR = ChunkR<P>::v;
-    constexpr bool RING = true;
-    using Stage = ChainStage<P, kChunkR, SUB, RING, HI8>;
+    using Stage = ChainStage<P, kChunkR, SUB, true, HI8>;
     __shared__ Stage S;   // (rbg_device.hpp: the staging and the flush are k_locate_fill's)
-    const uint64_t out_elem0 = reinterpret_cast<uintptr_t>(locs) / sizeof(OUT);
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & (kWave - 1);
-    unsigned long long c_locs = 0;
-    unsigned long long st_phi = 0, st_ent = 0, st_chains = 0;   // STATS only
-    const uint64_t n = ix.n;
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
-    for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * blockDim.x + wv * kWave; base < N; base += stride) {
-        const uint64_t j = base + lane;
-        uint64_t i = j;
-        if (order && j < N) i = order[j];
-        uint64_t occ = 0, k1 = 0, dst = 0;
-        if (i < N && j < N) {
-            dst = loc_off[i];
-            if (skeys) {
-                if (ix.order_docs) k1 = locus_toehold_r(ix, skeys[j], k, i);
-                else if (sizeof(P) == 4) { const uint32_t k32 = reinterpret_cast<const uint32_t *>(skeys)[j]; k1 = k32 == 0xFFFFFFFFu ? k[i] : k32; }   // (k_locate.hip k_keys32)
-                else k1 = skeys[j];
-                occ = loc_off[i + 1] - dst;
-            } else {
-                const uint64_t l = lo[i], h = hi[i];
-                occ = h >= l ? h - l + 1 : 0;                  // toehold_sa.hpp:38-39
-                if (occ > max_hits) occ = max_hits;
-                k1 = k[i];
-            }
-        }
-        const uint64_t minus = (SUB && i < N && j < N) ? sub[i] : 0;
-        // the window grid of this read: its first location sits a elements past a CH-element boundary of the output array (RING; else a = 0)
-        const uint32_t a = (RING && occ) ? static_cast<uint32_t>((out_elem0 + dst) & static_cast<uint64_t>(kChunkR - 1)) : 0u;
-        S.dst[wv][lane] = dst - a;   // (wraps for a read at the very start of a misaligned array; + v >= a brings it back)
-        if (SUB) S.minus[wv][lane] = minus;
-        const bool off_text = Stage::kSentinel && k1 >= n;     // a toehold below zero: its owner stores that location (ChainStage)
-        if (off_text && occ) locs[dst] = static_cast<OUT>(k1 - minus);
-        c_locs += occ;
-        if (STATS && occ) st_chains += 1;
-        uint64_t wmax = occ + a;      // the chain's extent in virtual columns
-#pragma unroll
-        for (int o = kWave / 2; o > 0; o >>= 1) {
-            const uint64_t other = __shfl_xor(wmax, o, kWave);
-            wmax = other > wmax ? other : wmax;
-        }
-        for (uint64_t t0 = 0; t0 < wmax; t0 += kChunkR) {
-            const uint32_t cnt = chain_round_count<kChunkR>(occ, t0);
-            S.bounds[wv][lane] = chain_window_bounds<kChunkR>(occ, a, t0);
-#pragma unroll 1
-            for (int e = 0; e < kChunkR; ++e) {
-                const bool mine = static_cast<uint32_t>(e) < cnt;
-                if (mine && (e || t0)) {                       // toehold_sa.hpp:44: k = phi(k)
-                    uint64_t s;
-                    if (k1 >= n) {
-                        // a toehold below zero (k_locate.hip phi_step): outside phi's domain -- the last sample is its predecessor
-                        s = (ix.phi_last_base + (k1 - ix.phi_last_pos)) % n;
-                    } else {
-                        bool found;
-                        uint64_t val;
-                        uint32_t ents, rounds;
-                        lane_phi<P>(ix, k1, found, val, ents, rounds);
-                        if (STATS) { st_phi += 1; st_ent += ents + 7u * rounds; }
-                        // no sampled position before k1: circular predecessor = the last one, delta = i + 1
-                        // (sparse_sd_vector.hpp:141-143, toehold_sa.hpp:59,65); else prev_sample + delta (toehold_sa.hpp:65-71)
-                        s = found ? val : ix.phi_last_base + k1 + 1;
-                        if (s >= n) s -= n;
-                    }
-                    k1 = s;
-                }
-                if (mine) chain_put(S, wv, lane, a + static_cast<uint32_t>(t0) + e, k1, e == 0 && t0 == 0 && off_text);
-            }
-            wave_lds_sync();
-            chain_flush(S, wv, lane, t0, locs);
-            wave_lds_sync();
-        }
-        wave_lds_sync();
-    }
-    c_locs = wave_sum(c_locs);
-    if (lane == 0 && c_locs) atomicAdd(&ix.counters[3], c_locs);
-    if (STATS) {
-        st_phi = wave_sum(st_phi);
-        st_ent = wave_sum(st_ent);
-        st_chains = wave_sum(st_chains);
-        if (lane == 0) {
-            if (st_phi) atomicAdd(&stats[kLsPhiSteps], st_phi);
-            if (st_ent) atomicAdd(&stats[kLsPhiOvf], st_ent);
-            if (st_chains) atomicAdd(&stats[kLsChains], st_chains);
-            if (c_locs) atomicAdd(&stats[kLsLocs], c_locs);
-        }
-    }
+    chain_fill_walk<P, OUT, STATS, SUB, HI8, kChunkR, 1>(ix, S, lo, hi, k, N, max_hits, loc_off, locs, sub, order, skeys, stats,
+                                                         [&](const uint64_t k1, unsigned long long &cost) { return run_phi<P, STATS>(ix, k1, cost); });
 }
 
 // ---- document hits from the walk itself (rbg_locate_docs.hpp) over the run-indexed layout's phi list: k_locate_fill_runs2's chains and its phi
-// step (the branch for a toehold below zero and lane_phi, as that kernel applies them), the positions resolved and reduced instead of stored ----
+// step (run_phi), the positions resolved and reduced instead of stored ----
 extern __shared__ unsigned long long locate_docs_lds[];
 template <typename P, bool LOCS>
 __global__ __launch_bounds__(kLocDocBlock) void k_locate_docs_runs2(const DevIndex ix, const DocTable t, const uint64_t *__restrict__ lo,
@@ -459,18 +370,8 @@ __global__ __launch_bounds__(kLocDocBlock) void k_locate_docs_runs2(const DevInd
                                                                    const uint64_t *__restrict__ skeys, uint64_t *__restrict__ sets,
                                                                    uint32_t *__restrict__ ndocs_out, uint32_t *__restrict__ nodoc_out,
                                                                    unsigned long long *__restrict__ doc_reads, unsigned long long *__restrict__ doc_locs) {
-    const uint64_t n = ix.n;
     locate_docs_walk<P, LOCS>(ix, t, locate_docs_lds, lo, hi, k, N, max_hits, order, skeys, sets, ndocs_out, nodoc_out, doc_reads, doc_locs,
-                              [&](const uint64_t k1) -> uint64_t {
-        if (k1 >= n) return (ix.phi_last_base + (k1 - ix.phi_last_pos)) % n;   // a toehold below zero (k_locate.hip phi_step)
-        bool found;
-        uint64_t val;
-        uint32_t ents, rounds;
-        lane_phi<P>(ix, k1, found, val, ents, rounds);
-        uint64_t s = found ? val : ix.phi_last_base + k1 + 1;   // no sampled position before k1: the last one, delta = k1 + 1 (toehold_sa.hpp:59,65)
-        if (s >= n) s -= n;
-        return s;
-    });
+                              [&](const uint64_t k1, unsigned long long &cost) { return run_phi<P>(ix, k1, cost); });
 }
 
 }  // namespace
@@ -525,24 +426,11 @@ int launch_locate_fill_runs(const DevIndex &ix, const LaunchCfg &cfg, const uint
                             uint64_t N, uint64_t max_hits, const uint64_t *loc_off, uint64_t *locs, const uint64_t *sub,
                             const void *order, const uint64_t *skeys, void *stream, unsigned long long *stats, uint32_t *locs32) {
     if (N == 0) return 0;
-    if ((stats || locs32) && sub) return static_cast<int>(hipErrorInvalidValue);
     const dim3 grid(grid_for(cfg, N)), block(256);
     const uint32_t *perm = static_cast<const uint32_t *>(order);
-    const bool hi8 = ix.pos_bytes == 8 && ix.n < kChainHi8Limit && chain_hi8_enabled();
-    if (locs32 && ix.pos_bytes != 4) return static_cast<int>(hipErrorInvalidValue);
-    return with_pos(ix.pos_bytes, [&](auto p) {
-        using P = pos_t<decltype(p)>;
-        // the variants that exist: as launch_locate_fill's (k_locate.hip)
-        auto fill = [&](auto sts, auto sb, auto *dst) {
-            return with_flag(hi8, [&](auto h8) {
-                return launch_grid(k_locate_fill_runs2<P, std::remove_pointer_t<decltype(dst)>, decltype(sts)::value, decltype(sb)::value, sizeof(P) == 8 && decltype(h8)::value>,
-                                   grid, block, 0, stream, ix, lo, hi, k, N, max_hits, loc_off, dst, sub, perm, skeys, stats);
-            });
-        };
-        if constexpr (sizeof(P) == 4) { if (locs32) return fill(no, no, locs32); }
-        if (stats) return fill(yes, no, locs);
-        if (sub) return fill(no, yes, locs);
-        return fill(no, no, locs);
+    return chain_fill_variants(ix, stats, sub, locs, locs32, [&](auto p, auto sts, auto sb, auto h8, auto *dst) {
+        return launch_grid(k_locate_fill_runs2<pos_t<decltype(p)>, std::remove_pointer_t<decltype(dst)>, decltype(sts)::value, decltype(sb)::value, decltype(h8)::value>,
+                           grid, block, 0, stream, ix, lo, hi, k, N, max_hits, loc_off, dst, sub, perm, skeys, stats);
     });
 }
 

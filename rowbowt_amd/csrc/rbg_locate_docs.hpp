@@ -1,7 +1,7 @@
 // rbg_locate_docs.hpp -- document hits from the phi walk itself (rbg_locate_doc_hits_dev; include/rbg.h): K3's chains (ToeholdSA::locate_range,
 // toehold_sa.hpp:37-49) with every position resolved to its document as it is produced (rbg_docdir.hpp doc_rank: doclist.hpp:46-50 over :77-79) and
 // nothing stored per location.  What k_locate_fill / k_locate_fill_runs2 stage and flush (ChainStage) and k_doc_hits reads back is replaced by this
-// file; the phi step of each layout stays where it is and comes in as `phi` (k_locate.hip phi_step, k_runs.hip lane_phi).
+// file; the phi step of each layout stays where it is and comes in as `phi`, the one the fill kernels' walk takes (k_locate.hip slot_phi, rbg_runs2_device.hpp run_phi).
 //
 // ONE LANE PER CHAIN, as in K3: the chain is serial, the reads are not; a wave waits for its longest chain.  Nothing crosses lanes inside a chain, so
 // the lanes loop over their own counts.
@@ -13,13 +13,14 @@
 // workgroup met.
 // THE TABLE (sorted starts, directory) is staged in LDS as k_doc_hits stages it; the launch refuses tables above kLocDocLdsDocs (rbg_dev.h; the caller keeps
 // the two-step path there).  The full 64-bit position is at hand: 2^64 - 1 (a toehold that wrapped below zero) has no document by the rule itself.
-// ORDER (the workspace of launch_locate_order): lane j takes read order[j] and decodes its toehold from the sorted keys exactly as the fill kernels
-// do; the count is min(hi - lo + 1, max_hits) from lo[i], hi[i] -- there is no loc_off in this path, so no plan.
+// ORDER (the workspace of launch_locate_order): lane j takes read order[j] and decodes its toehold from the sorted keys as the fill kernels
+// do (rbg_chain_walk.hpp chain_toehold); the count is min(hi - lo + 1, max_hits) from lo[i], hi[i] -- there is no loc_off in this path, so no plan.
 // ix.counters[3] grows by the positions walked, as in K3.
 #pragma once
 
 #include <mutex>
 
+#include "rbg_chain_walk.hpp"
 #include "rbg_docdir.hpp"
 #include "rbg_runs_device.hpp"
 
@@ -48,15 +49,9 @@ __device__ __forceinline__ void locate_docs_count(uint32_t v, const uint32_t fir
         atomicAdd(&hist[d], 1ull);
     }
 }
-// the toehold of a locus key (k_locate.hip locus_key / locus_toehold)
-__device__ __forceinline__ uint64_t locate_docs_locus_toehold(const DevIndex &ix, const uint64_t key, const uint64_t *__restrict__ k, const uint64_t i) {
-    if (key == ~uint64_t(0)) return k[i];
-    const uint32_t low = ix.order_lowbits, db = ix.order_dbits;
-    const uint64_t doc = (key >> low) & ((uint64_t(1) << db) - 1u);
-    return ix.order_docs[doc] + (((key >> (db + low)) << low) | (key & ((uint64_t(1) << low) - 1u)));
-}
 
-// the body of both kernels; lds = the workgroup's dynamic LDS (locate_docs_lds_bytes); phi(k) = the position before k in the chain
+// the body of both kernels; lds = the workgroup's dynamic LDS (locate_docs_lds_bytes); phi(k, cost) = the position before k in the chain, as the fill
+// kernels' walk takes it (rbg_chain_walk.hpp; this walk is not instrumented and drops the cost)
 template <typename P, bool LOCS, typename Phi>
 __device__ __forceinline__ void locate_docs_walk(const DevIndex &ix, const DocTable &t, unsigned long long *lds, const uint64_t *__restrict__ lo,
                                                  const uint64_t *__restrict__ hi, const uint64_t *__restrict__ k, const uint64_t N, const uint64_t max_hits,
@@ -78,26 +73,19 @@ __device__ __forceinline__ void locate_docs_walk(const DevIndex &ix, const DocTa
     const uint64_t *sorted = reinterpret_cast<const uint64_t *>(l_sorted);
     const uint32_t W = (t.ndocs + 63) / 64, W32 = 2 * W;
     unsigned long long *hist = doc_reads ? l_reads : nullptr;
-    unsigned long long c_locs = 0;
+    unsigned long long c_locs = 0, cost = 0;
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kLocDocBlock;
     for (uint64_t j = static_cast<uint64_t>(blockIdx.x) * kLocDocBlock + threadIdx.x; j < N; j += stride) {
         const uint64_t i = order ? order[j] : j;
         if (i >= N) continue;   // (a permutation never holds one)
-        uint64_t k1;
-        if (skeys) {
-            if (ix.order_docs) k1 = locate_docs_locus_toehold(ix, skeys[j], k, i);
-            else if (sizeof(P) == 4) { const uint32_t k32 = reinterpret_cast<const uint32_t *>(skeys)[j]; k1 = k32 == 0xFFFFFFFFu ? k[i] : k32; }   // (k_locate.hip k_keys32)
-            else k1 = skeys[j];
-        } else {
-            k1 = k[i];
-        }
+        uint64_t k1 = skeys ? chain_toehold<P>(ix, skeys, k, i, j) : k[i];
         const uint64_t l = lo[i], h = hi[i];
         uint64_t occ = h >= l ? h - l + 1 : 0;   // toehold_sa.hpp:38-39
         if (occ > max_hits) occ = max_hits;
         for (uint32_t w = 0; w < W32; ++w) set[w * kLocDocBlock] = 0;
         uint32_t miss = 0;
         for (uint64_t s = 0; s < occ; ++s) {
-            if (s) k1 = phi(k1);   // every location but a read's first is phi of the one before (toehold_sa.hpp:44)
+            if (s) k1 = phi(k1, cost);   // every location but a read's first is phi of the one before (toehold_sa.hpp:44)
             const uint32_t r = doc_rank(sorted, l_dir, t.size, t.shift, k1);
             if (r == 0) { ++miss; continue; }
             const uint32_t d = r - 1;

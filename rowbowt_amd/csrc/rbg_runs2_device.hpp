@@ -60,7 +60,7 @@ __device__ __forceinline__ RunSearch2<P> stage_run_search2(const DevIndex &ix, u
     __syncthreads();
     RunSearch2<P> S;
     S.hot = s_hot; S.ghot = ix.run_hot;
- S.gtab = ix.run_tabs2; S.tab_first = s_tab_first; S.ent = s_ent2; S.dir = s_dir2; S.rec = s_rec2;
+    S.gtab = ix.run_tabs2; S.tab_first = s_tab_first; S.ent = s_ent2; S.dir = s_dir2; S.rec = s_rec2;
     S.fill = ix.run_fill_shift;
     S.rec_any = nullptr;
     for (int t = kMaxRunDepth - 1; t >= 0; --t)
@@ -75,7 +75,6 @@ struct RunHot {
 };
 template <typename P>
 __device__ __forceinline__ RunHot load_run_tab(const RunSearch2<P> &S, const uint32_t d, const uint32_t rec) {
-    // uniform geometry (DevIndex::run_uni_*): the table's ordinal in its depth x the depth's stride, one 32 x 32 -> 64 bit multiply, no memory request
     // uniform geometry (DevIndex::run_uni_*): the table's ordinal in its depth x the depth's stride, one 32 x 32 -> 64 bit multiply.  Branch-free: the lanes
     // of the uniform depth all name the depth's FIRST hot word (one request for the wave instead of one per lane) and replace what it returns.
     const uint2 u = *reinterpret_cast<const uint2 *>(S.tab_first + kRunUniAt);   // {first record | depth << 24, stride | shift << 27}
@@ -715,6 +714,24 @@ __device__ __forceinline__ void lane_phi(const DevIndex &ix, const uint64_t q, b
     }
     found = c != 0;
     val = ((static_cast<uint64_t>(kb_hi) << 32) | kb_lo) + static_cast<uint32_t>(qa - ks);
+}
+// The phi step of the chain walks over the list (rbg_chain_walk.hpp, rbg_locate_docs.hpp): the position before k1, for any k1.  Under STATS the step adds
+// the sampled positions its scan and its narrowing rounds needed to `cost` (8 or 12 bytes each; 7 pivot keys per round).
+template <typename P, bool STATS = false>
+__device__ __forceinline__ uint64_t run_phi(const DevIndex &ix, const uint64_t k1, unsigned long long &cost) {
+    const uint64_t n = ix.n;
+    // a toehold below zero (k_locate.hip phi_step): outside phi's domain -- the last sample is its predecessor
+    if (k1 >= n) return (ix.phi_last_base + (k1 - ix.phi_last_pos)) % n;
+    bool found;
+    uint64_t val;
+    uint32_t ents, rounds;
+    lane_phi<P>(ix, k1, found, val, ents, rounds);
+    if (STATS) cost += ents + 7u * rounds;
+    // no sampled position before k1: circular predecessor = the last one, delta = k1 + 1
+    // (sparse_sd_vector.hpp:141-143, toehold_sa.hpp:59,65); else prev_sample + delta (toehold_sa.hpp:65-71)
+    uint64_t s = found ? val : ix.phi_last_base + k1 + 1;
+    if (s >= n) s -= n;
+    return s;
 }
 
 }  // namespace

@@ -146,28 +146,10 @@ def test_locate_chains_in_locus_order(synth, layout, phi, pos_bytes, monkeypatch
     o.close()
 
 
-@pytest.mark.parametrize("layout,phi", [(capi.LAYOUT_SLOTS, 0), (capi.LAYOUT_RUNS, 2), (capi.LAYOUT_RUNS, 1)])
-@pytest.mark.parametrize("pos_bytes", [4, 8, -8])
-def test_k3_staging_at_its_edges(synth, layout, phi, pos_bytes, monkeypatch):
-    """K3's staging (rbg_device.hpp ChainStage, round 6: values at the position width -- 8-byte positions below 2^40 as a low word + one high byte, or whole
-    (pos_bytes -8) --, flush WINDOWS on 64-byte boundaries of the output array taken from a ring, the first location of a chain that is no text position
-    stored by its owner): chains cut by max_hits at, just below and just above the rounds of 8 steps, at every alignment of a read's first location;
-    toeholds that wrapped below zero by one AND by two (LF_w_loc's k - 1, rowbowt.hpp:561, once or twice past text position 0 -- at 4-byte
-    positions the staged word for them is all ones, whatever the value) on chains of several locations; the ordered and the unordered walk;
-    64-bit locations against the oracle (toehold_sa.hpp:37-49), 32-bit ones = their low words, nothing written outside a read's segment."""
-    import subprocess
+def _k3_edge_chains(S, layout, phi, pos_bytes):
+    """The chains that cross K3's staging edges (test_k3_staging_at_its_edges, test_k3_offset_fill_at_the_staging_edges): short reads with long chains,
+    three toeholds that are no text position planted on chains of several locations, the oracle's ranges on the device and the order of the chains."""
     import torch
-    S = synth
-    if pos_bytes < 0:
-        # 8-byte positions staged WHOLE (what an index of 2^40 positions or more gets; below that a value travels as its low word + one high byte): the switch is read
-        # once per process, so this case runs in a child
-        if os.environ.get("RBG_K3_HI8") != "0":
-            env = dict(os.environ, RBG_K3_HI8="0")
-            r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", f"{__file__}::test_k3_staging_at_its_edges[-8-{layout}-{phi}]"], env=env,
-                               capture_output=True, text=True, timeout=600)
-            assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-            return
-        pos_bytes = 8
     with capi.default_option(capi.OPT_RANK_LAYOUT, layout), capi.default_option(capi.OPT_RUN_PHI, phi), capi.default_option(capi.OPT_POS_BYTES, pos_bytes):
         rb = ra.RowBowt.from_runs(S.heads, S.lens, S.ssa, S.esa, device=0)
     o = orc.Oracle.from_runs(S.heads, S.lens, S.ssa, S.esa)
@@ -191,6 +173,32 @@ def test_k3_staging_at_its_edges(synth, layout, phi, pos_bytes, monkeypatch):
     d_tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)
     d_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     assert L.rbg_locate_order_dev(rb.h, d_k.data_ptr(), N, d_ws.data_ptr(), ws_bytes, st) == 0
+    return rb, o, N, wlo, whi, wk, dev, st, L, d_lo, d_hi, d_k, d_loc_off, tmp_bytes, d_tmp, d_ws
+
+
+@pytest.mark.parametrize("layout,phi", [(capi.LAYOUT_SLOTS, 0), (capi.LAYOUT_RUNS, 2), (capi.LAYOUT_RUNS, 1)])
+@pytest.mark.parametrize("pos_bytes", [4, 8, -8])
+def test_k3_staging_at_its_edges(synth, layout, phi, pos_bytes, monkeypatch):
+    """K3's staging (rbg_device.hpp ChainStage, round 6: values at the position width -- 8-byte positions below 2^40 as a low word + one high byte, or whole
+    (pos_bytes -8) --, flush WINDOWS on 64-byte boundaries of the output array taken from a ring, the first location of a chain that is no text position
+    stored by its owner): chains cut by max_hits at, just below and just above the rounds of 8 steps, at every alignment of a read's first location;
+    toeholds that wrapped below zero by one AND by two (LF_w_loc's k - 1, rowbowt.hpp:561, once or twice past text position 0 -- at 4-byte
+    positions the staged word for them is all ones, whatever the value) on chains of several locations; the ordered and the unordered walk;
+    64-bit locations against the oracle (toehold_sa.hpp:37-49), 32-bit ones = their low words, nothing written outside a read's segment."""
+    import subprocess
+    import torch
+    S = synth
+    if pos_bytes < 0:
+        # 8-byte positions staged WHOLE (what an index of 2^40 positions or more gets; below that a value travels as its low word + one high byte): the switch is read
+        # once per process, so this case runs in a child
+        if os.environ.get("RBG_K3_HI8") != "0":
+            env = dict(os.environ, RBG_K3_HI8="0")
+            r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", f"{__file__}::test_k3_staging_at_its_edges[-8-{layout}-{phi}]"], env=env,
+                               capture_output=True, text=True, timeout=600)
+            assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+            return
+        pos_bytes = 8
+    rb, o, N, wlo, whi, wk, dev, st, L, d_lo, d_hi, d_k, d_loc_off, tmp_bytes, d_tmp, d_ws = _k3_edge_chains(S, layout, phi, pos_bytes)
     for mh in (1, 7, 8, 9, 15, 16, 17, 31, 32, 33, MAXU):
         woff, wlocs = o.locs_at_batch(wlo, whi, wk, mh, nthreads=4)
         assert L.rbg_locate_plan_dev(rb.h, d_lo.data_ptr(), d_hi.data_ptr(), N, mh, d_loc_off.data_ptr(), d_tmp.data_ptr(), tmp_bytes, st) == 0
@@ -208,6 +216,39 @@ def test_k3_staging_at_its_edges(synth, layout, phi, pos_bytes, monkeypatch):
                 torch.cuda.synchronize()
                 assert (d_locs32[:total].cpu().numpy().view(np.uint32) == (wlocs & np.uint64(0xFFFFFFFF)).astype(np.uint32)).all(), (mh, order is None)
                 assert d_locs32[total:].tolist() == [-7, -7]
+    rb.close()
+    o.close()
+
+
+@pytest.mark.parametrize("layout,phi", [(capi.LAYOUT_SLOTS, 0), (capi.LAYOUT_RUNS, 2), (capi.LAYOUT_RUNS, 1)])
+@pytest.mark.parametrize("pos_bytes", [4, 8])
+def test_k3_offset_fill_at_the_staging_edges(synth, layout, phi, pos_bytes):
+    """rbg_locate_fill_offset_dev (K3's SUB instantiation: d_sub[i] subtracted from every location of read i, locate_from_longest_seed rowbowt.hpp:681-683) over
+    the chains of test_k3_staging_at_its_edges: the subtrahend staged per lane for the flush and applied by the owner to a first location that is no text
+    position, at the rounds of 8 steps and around them, ordered and unordered.  d_sub is 0 for some reads, below the locations for most and above every
+    location for every seventh, where the difference wraps: (Oracle.locs_at - d_sub[i]) mod 2^64 per read, nothing written past the last segment."""
+    import torch
+    rb, o, N, wlo, whi, wk, dev, st, L, d_lo, d_hi, d_k, d_loc_off, tmp_bytes, d_tmp, d_ws = _k3_edge_chains(synth, layout, phi, pos_bytes)
+    idx = np.arange(N, dtype=np.uint64)
+    sub = idx % np.uint64(23)
+    sub[3::7] += np.uint64(1) << np.uint64(41)                      # (above every text position: the subtraction wraps)
+    assert (sub == 0).any() and int(sub.max()) > synth.n
+    planted = np.flatnonzero(wk >= np.uint64(synth.n))
+    assert len(planted) == 3 and (sub[planted] > 0).any()           # (the owner's store of a toehold outside the text subtracts too)
+    d_sub = torch.from_numpy(sub.view(np.int64)).to(dev)
+    for mh in (1, 7, 8, 9, 16, 17, 33, MAXU):
+        woff, wlocs = o.locs_at_batch(wlo, whi, wk, mh, nthreads=4)
+        want = wlocs - np.repeat(sub, np.diff(woff).astype(np.int64))   # (uint64: wraps as the kernel's subtraction does)
+        assert L.rbg_locate_plan_dev(rb.h, d_lo.data_ptr(), d_hi.data_ptr(), N, mh, d_loc_off.data_ptr(), d_tmp.data_ptr(), tmp_bytes, st) == 0
+        total = int(d_loc_off[-1].item())
+        assert total == int(woff[-1])
+        for order in (d_ws.data_ptr(), None):
+            d_locs = torch.full((total + 2,), -7, dtype=torch.int64, device=dev)
+            assert L.rbg_locate_fill_offset_dev(rb.h, d_lo.data_ptr(), d_hi.data_ptr(), d_k.data_ptr(), N, mh, d_loc_off.data_ptr(), d_locs.data_ptr(),
+                                                d_sub.data_ptr(), order, st) == 0
+            torch.cuda.synchronize()
+            assert (d_locs[:total].cpu().numpy().view(np.uint64) == want).all(), (mh, order is None)
+            assert d_locs[total:].tolist() == [-7, -7]
     rb.close()
     o.close()
 
