@@ -544,6 +544,36 @@ int rbg_extract_dev(rbg_index *, const uint64_t *d_pos, const uint32_t *d_len, c
  * interval j, zeros behind them.  Every interval is cut into pieces of at most RBG_OPT_EXTRACT_CHUNK bases before the upload, each an item that finds its
  * own row; the interval ends at its first short piece, so the result does not depend on the chunk.  RBG_EARG for a pos[j] >= n (nothing is written). */
 int rbg_extract(rbg_index *, const uint64_t *pos, const uint64_t *len, uint64_t M, uint8_t *out, uint64_t *got);
+/* ---- an index from its text: suffix array, runs, samples (sa_build.hip) ---------------------------------------------------------------
+ * The text is n bytes whose LAST byte is its unique smallest one (the terminator; rb_build --fasta writes documents joined by '#' and ends in 0x01).  The
+ * three device calls take no handle and run on the current device, like rbg_sample_reads_dev.  pos_bytes = 4 (n < 2^32 - 16 only) or 8 (any n): the width
+ * of ranks and of suffix-array entries.
+ * rbg_suffix_array_dev: d_sa[i] = the start of the i-th smallest suffix, n entries of pos_bytes; exactly n * pos_bytes bytes are written at d_sa (aligned to
+ * pos_bytes) and nothing outside d_sa and d_tmp (rbg_sa_tmp_bytes(n, pos_bytes) bytes, 256-byte aligned; 0 = a width that does not hold n).  Prefix
+ * doubling over ranks from a first key of eight bytes; suffixes whose rank is unique leave the later rounds.  The rule about the last byte is checked on the
+ * device before anything is sorted: RBG_EARG, d_sa untouched.  RBG_EARG also for n == 0, a NULL or misaligned pointer, too little scratch.  NOT
+ * capturable: the call waits for `stream` once per round and has finished when it returns.
+ * rbg_sa_info: of the last rbg_suffix_array_dev / rbg_build_from_text / rbg_convert_text of the process -- out[0] = rounds (the first key's round included;
+ * at most ceil(log2 n) + 1), out[1] = the elements sorted, summed over the rounds (at most n * rounds), out[2] = the scratch bytes, out[3] = n, out[4] =
+ * pos_bytes, out[5] = the suffixes still tied after the first round, out[6 .. 7] = 0.
+ * rbg_text_runs_plan_dev: *R = the runs of the BWT, BWT[i] = text[(SA[i] - 1) mod n] with byte 0 read as 1 (rle_string.hpp:59,62); the runs are numbered in
+ * d_tmp (rbg_text_runs_tmp_bytes, 256-byte aligned).  Waits for `stream`.  rbg_text_runs_fill_dev, with the same d_tmp: d_heads[R] (u8), d_lens[R], d_ssa[R],
+ * d_esa[R] (u64) -- the arguments of rbg_build_from_runs: the raw SA values at each run's first and last row (toehold_sa.hpp:133-155).  Asynchronous. */
+size_t rbg_sa_tmp_bytes(uint64_t n, uint32_t pos_bytes);
+int rbg_suffix_array_dev(const uint8_t *d_text, uint64_t n, void *d_sa, uint32_t pos_bytes, void *d_tmp, size_t tmp_bytes, void *stream);
+int rbg_sa_info(uint64_t out[8]);
+size_t rbg_text_runs_tmp_bytes(uint64_t n, uint32_t pos_bytes);
+int rbg_text_runs_plan_dev(const uint8_t *d_text, const void *d_sa, uint64_t n, uint32_t pos_bytes, void *d_tmp, size_t tmp_bytes, uint64_t *R, void *stream);
+int rbg_text_runs_fill_dev(const uint8_t *d_text, const void *d_sa, uint64_t n, uint32_t pos_bytes, const void *d_tmp, size_t tmp_bytes, uint64_t R,
+                           uint8_t *d_heads, uint64_t *d_lens, uint64_t *d_ssa, uint64_t *d_esa, void *stream);
+/* The same from a text in HOST memory, to a handle: upload, the three calls above, then rbg_build_from_runs' own path (with RBG_LOAD_SA in flags the toehold
+ * samples are kept, without it none; other flag bits are ignored).  The position width follows RBG_OPT_POS_BYTES.  Before anything is allocated the device
+ * bytes of the build -- n + n * pos_bytes + max(rbg_sa_tmp_bytes, rbg_text_runs_tmp_bytes) -- are compared with hipMemGetInfo's free bytes: RBG_ENOMEM when
+ * they do not fit (the text is not touched).  The run arrays, 25 bytes per run, are checked the same way once the plan has counted the runs: RBG_ENOMEM
+ * again, before any of the four is allocated.  RBG_ENODEV for device = RBG_DEVICE_NONE, RBG_EARG for n == 0, a NULL text, a text that breaks the rule.
+ * rbg_convert_text: the cache file instead of a handle, through rbg_convert_runs_markers (docs_text nullable, as there). */
+int rbg_build_from_text(const uint8_t *text, uint64_t n, int flags, int device, rbg_index **out);
+int rbg_convert_text(const uint8_t *text, uint64_t n, const char *docs_text /* nullable */, int flags, int device, const char *out_path);
 /* ---- rb_markers' report (what the tool prints), made on the device --------------------------------------------------------------
  * Everything rb_markers does between get_markers_greedy_seeding / get_markers_lmems and its output (rb_markers.cpp:228-315, :365-382,
  * :396-413, :429-519), for a batch of RAW reads: both strands (sequence 2i = read i through seq_ntoa_table -- ACGT of either case, N/n -> 'A',

@@ -252,6 +252,14 @@ _PROTOS = [
     ("rbg_isa", C.c_int, [VP, VP, U64, VP]),
     ("rbg_extract_dev", C.c_int, [VP, VP, VP, VP, U64, VP, VP, VP]),
     ("rbg_extract", C.c_int, [VP, VP, VP, U64, VP, VP]),
+    ("rbg_sa_tmp_bytes", C.c_size_t, [U64, C.c_uint32]),
+    ("rbg_suffix_array_dev", C.c_int, [VP, U64, VP, C.c_uint32, VP, C.c_size_t, VP]),
+    ("rbg_sa_info", C.c_int, [VP]),
+    ("rbg_text_runs_tmp_bytes", C.c_size_t, [U64, C.c_uint32]),
+    ("rbg_text_runs_plan_dev", C.c_int, [VP, VP, U64, C.c_uint32, VP, C.c_size_t, C.POINTER(U64), VP]),
+    ("rbg_text_runs_fill_dev", C.c_int, [VP, VP, U64, C.c_uint32, VP, C.c_size_t, U64, VP, VP, VP, VP, VP]),
+    ("rbg_build_from_text", C.c_int, [VP, U64, C.c_int, C.c_int, C.POINTER(VP)]),
+    ("rbg_convert_text", C.c_int, [VP, U64, C.c_char_p, C.c_int, C.c_int, C.c_char_p]),
     ("rbg_set_default_option", C.c_int, [C.c_int, C.c_int64]),
     ("rbg_get_default_option", C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
 ]
@@ -345,6 +353,75 @@ def convert_runs(heads, lens, ssa=None, esa=None, out_path=None, markers=None, d
                                           len(mk[0]) if markers is not None else 0, _p(mk[2]) if markers is not None else None,
                                           _p(mk[3]) if markers is not None else None, docs_text.encode() if docs_text else None,
                                           os.fsencode(out_path)), "rbg_convert_runs_markers")
+
+
+SA_INFO = ("rounds", "sorted", "tmp_bytes", "n", "pos_bytes", "tied_after_first")
+
+
+def _text_bytes(text):
+    return np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+
+
+def convert_text(text, out_path, docs_text=None, sa=True, device=0):
+    """rbg_convert_text: the native cache file from a text in host memory (bytes or uint8 array whose last byte is its unique smallest)"""
+    t = _text_bytes(text)
+    _check(lib().rbg_convert_text(_p(t), len(t), docs_text.encode() if docs_text else None, int(LoadRbwtFlag.SA) if sa else 0, device, os.fsencode(out_path)),
+           "rbg_convert_text")
+
+
+def sa_info():
+    """rbg_sa_info -> dict of SA_INFO: the last suffix-array build of the process"""
+    out = np.zeros(8, np.uint64)
+    _check(lib().rbg_sa_info(_p(out)), "rbg_sa_info")
+    return {k: int(v) for k, v in zip(SA_INFO, out)}
+
+
+def _pos_bytes_of(n, pos_bytes):
+    return pos_bytes or (8 if n >= 0xFFFFFFF0 else 4)
+
+
+def suffix_array(text, pos_bytes=0):
+    """rbg_suffix_array_dev over torch tensors: text uint8[n] on a device (last byte = its unique smallest) -> the suffix array on that device, int32 where
+    n < 2^32 - 16 (the bits are unsigned: .view / & 0xFFFFFFFF above 2^31), else int64; pos_bytes = 8 forces int64.  Waits for the current stream"""
+    import torch
+    n = int(text.numel())
+    pb = _pos_bytes_of(n, pos_bytes)
+    assert text.dtype == torch.uint8 and text.is_contiguous()
+    with torch.cuda.device(text.device):
+        sa = torch.empty(max(n, 1), dtype=torch.int32 if pb == 4 else torch.int64, device=text.device)
+        nb = lib().rbg_sa_tmp_bytes(n, pb)
+        tmp = torch.empty(nb + 256, dtype=torch.uint8, device=text.device)
+        at = (-tmp.data_ptr()) % 256
+        rc = lib().rbg_suffix_array_dev(text.data_ptr() if n else None, n, sa.data_ptr(), pb, tmp.data_ptr() + at, nb, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+    _check(rc, "rbg_suffix_array_dev")
+    return sa[:n]
+
+
+def text_runs(text, sa):
+    """rbg_text_runs_plan_dev + rbg_text_runs_fill_dev over torch tensors (text uint8[n], sa int32[n] or int64[n] on its device) -> numpy dict heads u8[R],
+    lens, ssa, esa u64[R], n, r: what synth_pangenome.index_inputs gives.  Only the run arrays leave the device"""
+    import torch
+    n = int(text.numel())
+    pb = sa.element_size()
+    assert text.dtype == torch.uint8 and text.is_contiguous() and sa.is_contiguous() and int(sa.numel()) == n and pb in (4, 8)
+    L = lib()
+    with torch.cuda.device(text.device):
+        nb = L.rbg_text_runs_tmp_bytes(n, pb)
+        tmp = torch.empty(nb + 256, dtype=torch.uint8, device=text.device)
+        at = (-tmp.data_ptr()) % 256
+        st = torch.cuda.current_stream().cuda_stream
+        R = U64()
+        _check(L.rbg_text_runs_plan_dev(text.data_ptr(), sa.data_ptr(), n, pb, tmp.data_ptr() + at, nb, C.byref(R), st), "rbg_text_runs_plan_dev")
+        r = int(R.value)
+        heads = torch.empty(r, dtype=torch.uint8, device=text.device)
+        lens, ssa, esa = (torch.empty(r, dtype=torch.int64, device=text.device) for _ in range(3))
+        rc = L.rbg_text_runs_fill_dev(text.data_ptr(), sa.data_ptr(), n, pb, tmp.data_ptr() + at, nb, r, heads.data_ptr(), lens.data_ptr(), ssa.data_ptr(),
+                                      esa.data_ptr(), st)
+        torch.cuda.synchronize()
+    _check(rc, "rbg_text_runs_fill_dev")
+    u = lambda t: t.cpu().numpy().view(np.uint64).copy()
+    return dict(heads=heads.cpu().numpy().copy(), lens=u(lens), ssa=u(ssa), esa=u(esa), n=n, r=r)
 
 
 def set_default_option(opt, value):
@@ -463,6 +540,15 @@ class RowBowt:
         h = VP()
         _check(lib().rbg_build_from_runs(_p(heads), _p(lens), len(heads), _p(ssa), _p(esa), device, C.byref(h)),
                "rbg_build_from_runs")
+        return cls(h)
+
+    @classmethod
+    def from_text(cls, text, sa=True, device=0):
+        """rbg_build_from_text: the index of a text in host memory (bytes or a uint8 array; its last byte is its unique smallest), built on the device:
+        suffix array, runs, samples; sa=False keeps no toehold samples"""
+        t = _text_bytes(text)
+        h = VP()
+        _check(lib().rbg_build_from_text(_p(t), len(t), int(LoadRbwtFlag.SA) if sa else 0, device, C.byref(h)), "rbg_build_from_text")
         return cls(h)
 
     @classmethod

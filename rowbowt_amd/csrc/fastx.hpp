@@ -45,6 +45,8 @@ class FastxReader {
             if (c < 0) return c;
             last_char_ = c;
         }
+        rec_char_ = last_char_;
+        rec_qual_ = false;
         // name = up to the first whitespace (kseq.h:189: an error while reading it ends the call with -3,
         // end of file before any byte of it with -1); the rest of the line is the comment (kseq.h:190:
         // its return value is ignored, an error there surfaces in the sequence loop below)
@@ -70,6 +72,7 @@ class FastxReader {
         // FASTA (kseq.h:207): the record read so far is returned even when the stream failed under it;
         // the error is reported by the NEXT call (ks_getc's sticky ks_err, kseq.h:70)
         if (c != '+') return 0;
+        rec_qual_ = true;
         while ((c = getc()) >= 0 && c != '\n') {}  // rest of the '+' line
         if (c == -1) return rollback(-2);          // no quality string (kseq.h:213)
         size_t qlen = 0;
@@ -84,6 +87,10 @@ class FastxReader {
         last_char_ = 0;
         return qlen == seq_len ? 0 : rollback(-2);
     }
+
+    // of the record the last next() == 0 appended: the character that introduced it ('>' or '@'), and whether a '+' line followed its sequence
+    int record_char() const { return rec_char_; }
+    bool record_had_quality() const { return rec_qual_; }
 
    private:
     int getc() {
@@ -123,7 +130,8 @@ class FastxReader {
     std::vector<char> buf_;
     size_t begin_ = 0, end_ = 0;
     bool eof_ = false, err_ = false;
-    int last_char_ = 0;
+    int last_char_ = 0, rec_char_ = 0;
+    bool rec_qual_ = false;
     std::string qual_;
 };
 

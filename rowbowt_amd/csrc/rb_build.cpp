@@ -1,5 +1,6 @@
 // rb_build -- the reference's index builder CLI (reference src/rb_build.cpp) for this engine:
 //   rb_build [-o out_prefix] [-s] [-m] [-l] [-f [-k K]] [-a] <input_prefix>
+//   rb_build --fasta <ref.fa[.gz]> -o out_prefix [-s] [-l] [-f [-k K]] [--gpu n]
 // reads <input_prefix>.bwt (+ .ssa/.esa with -s, + .docs with -l) exactly as the reference's
 // constructors do (rle_string.hpp:44-97, toehold_sa.hpp:27-35,133-155) and writes the engine's
 // native cache <out_prefix>.rbgpu, which rb_align / rb_markers / rbg_load pick up when no .rbwt is
@@ -10,6 +11,9 @@
 //   -m   the reference parses the raw <input_prefix>.ma with pfbwt-f's MarkerArray constructor, which
 //        is not vendored; here -m folds an already serialised <input_prefix>.mab into the cache.
 //   -x   fbb_string indexes are not supported.
+//   --fasta  the reference has no builder from a sequence file (its inputs are pfbwt-f's).  Here the text of the FASTA (rbg_fasta_text.hpp: documents joined
+//        by '#', a final 0x01) goes to the device, which makes the suffix array, the runs and the samples (rbg_convert_text); -l writes <out>.docs and
+//        stores it in the cache; -m is refused: a FASTA carries no markers.
 //   The sdsl-serialised .rbwt/.tsa are not written (this engine does not need them; an existing
 //   reference-built index converts with `rb_build --from-index <prefix>`).
 #include <getopt.h>
@@ -21,11 +25,12 @@
 #include <string>
 
 #include "../../include/rbg.h"
+#include "rbg_fasta_text.hpp"
 
 namespace {
 
 struct Args {  // RowBowtConstructArgs, rowbowt_io.hpp:30-47
-    std::string prefix, inpre;
+    std::string prefix, inpre, fasta;
     int ma = 0, tsa = 0, dl = 0, ft = 0, ft_only = 0, fbb = 0, from_index = 0, device = 0;
     uint64_t k = 10;
 };
@@ -40,7 +45,8 @@ void print_help() {  // rb_build.cpp:11-20
     fprintf(stderr, "    --ft/-f [-k <int>]               construct offset table <out>.ftab\n");
     fprintf(stderr, "    --ftab-only/-a                   only construct the offset table from an existing index\n");
     fprintf(stderr, "    --from-index                     convert <pre>.rbwt/.tsa/.mab/.docs instead of raw inputs\n");
-    fprintf(stderr, "    --gpu <n>                        HIP device ordinal for -f/-a (default 0)\n");
+    fprintf(stderr, "    --fasta <ref.fa[.gz]>            build from a FASTA on the GPU (needs -o; no <index_prefix>; not with -m)\n");
+    fprintf(stderr, "    --gpu <n>                        HIP device ordinal for -f/-a/--fasta (default 0)\n");
     fprintf(stderr, "    <input_prefix>                   index prefix\n");
 }
 
@@ -55,6 +61,7 @@ Args parse_args(int argc, char **argv) {  // rb_build.cpp:22-95
                                            {"fbb", no_argument, 0, 'x'},
                                            {"from-index", no_argument, &args.from_index, 1},
                                            {"gpu", required_argument, 0, 'G'},
+                                           {"fasta", required_argument, 0, 'F'},
                                            {0, 0, 0, 0}};
     int c, long_index = 0;
     while ((c = getopt_long(argc, argv, "xo:k:lfsmha", long_options, &long_index)) != -1) {
@@ -69,10 +76,19 @@ Args parse_args(int argc, char **argv) {  // rb_build.cpp:22-95
             case 'a': args.ft_only = 1; break;
             case 'k': args.k = std::strtoull(optarg, nullptr, 10); break;
             case 'G': args.device = atoi(optarg); break;
+            case 'F': args.fasta = optarg; break;
             case 'h': print_help(); exit(0);
             case '?': break;  // the reference ignores unknown options (rb_build.cpp:64-65)
             default: print_help(); exit(1);
         }
+    }
+    if (!args.fasta.empty()) {  // the input is the FASTA: no <index_prefix>, and the outputs need a name
+        if (args.prefix.empty()) {
+            fprintf(stderr, "rb_build: --fasta needs -o <output prefix>\n");
+            exit(1);
+        }
+        args.inpre = args.prefix;
+        return args;
     }
     if (argc - optind < 1) {
         fprintf(stderr, "no argument provided\n");
@@ -105,6 +121,32 @@ void write_ftab(const Args &args) {
     rbg_free(ix);
 }
 
+int build_from_fasta(const Args &args) {
+    if (args.ma) {
+        std::cerr << "rb_build: -m cannot be combined with --fasta: a FASTA carries no markers" << std::endl;
+        return 1;
+    }
+    rbg_cli::FastaText t;
+    std::string why;
+    int rc = rbg_cli::fasta_text(args.fasta.c_str(), t, &why);
+    if (rc) {
+        std::cerr << "rb_build: " << why << ": " << rbg_strerror(rc) << std::endl;
+        return 1;
+    }
+    const std::string out = args.prefix + ".rbgpu", docs = t.docs_text();
+    std::cerr << "constructing from " << args.fasta << ": " << t.names.size() << " documents, " << t.text.size() << " symbols" << std::endl;
+    rc = rbg_convert_text(reinterpret_cast<const uint8_t *>(t.text.data()), t.text.size(), args.dl ? docs.c_str() : nullptr, args.tsa ? RBG_LOAD_SA : RBG_LOAD_NONE,
+                          args.device, out.c_str());
+    if (rc) die("building " + out, rc);
+    if (args.dl) {
+        std::ofstream ofs(args.prefix + ".docs", std::ios::binary);
+        ofs << docs;
+        if (!ofs.good()) die("writing " + args.prefix + ".docs", RBG_EIO);
+    }
+    if (args.ft) write_ftab(args);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -113,6 +155,7 @@ int main(int argc, char **argv) {
         std::cerr << "rb_build: fbb_string indexes are not supported by this engine" << std::endl;
         return 1;
     }
+    if (!args.fasta.empty()) return build_from_fasta(args);
     if (args.ft_only) {  // rb_build.cpp:108-109
         write_ftab(args);
         return 0;

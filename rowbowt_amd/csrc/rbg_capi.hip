@@ -51,5 +51,6 @@
 #include "capi/docs.ipp"          // the document table on the device, documents of located positions (rbg_doc_hits*, rbg_resolve_offsets_dev*)
 #include "capi/fl.ipp"            // the FL index on the device (rbg_fl_prepare), FL of rows, the right extension of located seeds (fl_extend.hip)
 #include "capi/extract.ipp"       // the ISA sample on the device (rbg_extract_prepare), rows of text positions, the text of intervals (extract.hip)
+#include "capi/build_text.ipp"    // an index from its text: suffix array, runs and samples on the device (sa_build.hip), rbg_build_from_text, rbg_convert_text
 #include "capi/sam.ipp"           // rbg_align_sam: SAM lines of raw reads, both strands, written on the device; rbg_sam_header
 #include "capi/replicas.ipp"      // replicas in one process, counters, RCCL

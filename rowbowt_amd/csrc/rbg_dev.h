@@ -591,6 +591,16 @@ int launch_isa_rows(const FlView &fl, const IsaView &isa, uint32_t pos_bytes, co
                     void *stream);
 int launch_extract(const FlView &fl, const IsaView &isa, uint32_t pos_bytes, const uint64_t *pos, const uint32_t *len, const uint64_t *out_off, uint64_t M,
                    uint8_t *out, uint32_t *got, unsigned int *d_err, uint32_t cap, void *stream);
+// an index from its text (sa_build.hip; rbg_suffix_array_dev, rbg_text_runs_*_dev): the suffix array by prefix doubling, then the BWT's runs with the samples of
+// their first and last rows.  Each returns 0, 2 for a HIP error (or scratch that is too small), sa_build also 1 for a text whose last byte is not its unique
+// smallest (d_sa untouched).  sa_build and text_runs_plan wait for the stream.  info: rounds, elements sorted (summed over the rounds), scratch bytes, n,
+// pos_bytes, the suffixes still tied after the first round.
+size_t sa_tmp_bytes(uint64_t n, uint32_t pos_bytes);
+int sa_build(const uint8_t *text, uint64_t n, void *sa, uint32_t pos_bytes, void *tmp, size_t tmp_bytes, void *stream, uint64_t info[8]);
+size_t text_runs_tmp_bytes(uint64_t n, uint32_t pos_bytes);
+int text_runs_plan(const uint8_t *text, const void *sa, uint64_t n, uint32_t pos_bytes, void *tmp, size_t tmp_bytes, uint64_t *R, void *stream);
+int text_runs_fill(const uint8_t *text, const void *sa, uint64_t n, uint32_t pos_bytes, const void *tmp, size_t tmp_bytes, uint64_t R, uint8_t *heads,
+                   uint64_t *lens, uint64_t *ssa, uint64_t *esa, void *stream);
 // run-indexed layout from run lists already on the device (k_build.hip): the tables' directories, 8-byte samples packed to 6
 int launch_run_dirs(uint32_t pos_bytes, const void *ent, const uint64_t *first, const uint64_t *nruns, const uint64_t *doff, const uint32_t *dshift,
                     uint32_t T, uint64_t total, uint32_t *dir, void *stream);

@@ -731,4 +731,14 @@ RowBowt<StringT> load_rowbowt(std::string prefix, LoadRbwtFlag flag, int device 
     return rb;
 }
 
+// The index of a text in memory (rbg_build_from_text): `text` ends in its unique smallest byte -- rb_build --fasta's text is the documents joined by '#'
+// and a final 0x01 --; the suffix array, the BWT's runs and their samples are made on the device.  The reference has no builder from a text (its rb_build
+// starts from pfbwt-f's files, rb_build.cpp:83-93).  LoadRbwtFlag::SA keeps the toehold samples.
+template <typename StringT = rle_string_t>
+RowBowt<StringT> build_from_text(const std::string &text, LoadRbwtFlag flag = LoadRbwtFlag::SA, int device = 0) {
+    rbg_index *ix = nullptr;
+    detail::check(rbg_build_from_text(reinterpret_cast<const uint8_t *>(text.data()), text.size(), static_cast<int>(flag), device, &ix), "build_from_text");
+    return RowBowt<StringT>(ix);
+}
+
 }  // namespace rbwt
