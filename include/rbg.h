@@ -558,7 +558,10 @@ int rbg_extract(rbg_index *, const uint64_t *pos, const uint64_t *len, uint64_t 
  * pos_bytes, out[5] = the suffixes still tied after the first round, out[6 .. 7] = 0.
  * rbg_text_runs_plan_dev: *R = the runs of the BWT, BWT[i] = text[(SA[i] - 1) mod n] with byte 0 read as 1 (rle_string.hpp:59,62); the runs are numbered in
  * d_tmp (rbg_text_runs_tmp_bytes, 256-byte aligned).  Waits for `stream`.  rbg_text_runs_fill_dev, with the same d_tmp: d_heads[R] (u8), d_lens[R], d_ssa[R],
- * d_esa[R] (u64) -- the arguments of rbg_build_from_runs: the raw SA values at each run's first and last row (toehold_sa.hpp:133-155).  Asynchronous. */
+ * d_esa[R] (u64) -- the arguments of rbg_build_from_runs: the raw SA values at each run's first and last row (toehold_sa.hpp:133-155).  Asynchronous.
+ * Both read d_sa as n entries of pos_bytes, aligned to pos_bytes.  R is the plan's count; with a smaller R (>= 1) the call returns 0, writes the first R
+ * runs in full and nothing behind entry R - 1 of any array.  RBG_EARG, nothing written: n == 0, R == 0 or R > n, a NULL or misaligned pointer (d_tmp,
+ * d_sa), too little scratch, a pos_bytes that is not 4 or 8 or does not hold n. */
 size_t rbg_sa_tmp_bytes(uint64_t n, uint32_t pos_bytes);
 int rbg_suffix_array_dev(const uint8_t *d_text, uint64_t n, void *d_sa, uint32_t pos_bytes, void *d_tmp, size_t tmp_bytes, void *stream);
 int rbg_sa_info(uint64_t out[8]);

@@ -119,7 +119,7 @@ size_t rbg_text_runs_tmp_bytes(uint64_t n, uint32_t pos_bytes) { return pos_byte
 int rbg_text_runs_plan_dev(const uint8_t *d_text, const void *d_sa, uint64_t n, uint32_t pos_bytes, void *d_tmp, size_t tmp_bytes, uint64_t *R, void *stream) {
     return guarded([&]() -> int {
     if (!d_text || !d_sa || !d_tmp || !R || n == 0 || !pos_bytes_ok(n, pos_bytes)) return RBG_EARG;
-    if (tmp_bytes < text_runs_tmp_bytes(n, pos_bytes) || (reinterpret_cast<uintptr_t>(d_tmp) & 255)) return RBG_EARG;
+    if (tmp_bytes < text_runs_tmp_bytes(n, pos_bytes) || (reinterpret_cast<uintptr_t>(d_tmp) & 255) || (reinterpret_cast<uintptr_t>(d_sa) & (pos_bytes - 1))) return RBG_EARG;
     return sa_rc(text_runs_plan(d_text, d_sa, n, pos_bytes, d_tmp, tmp_bytes, R, stream));
     });
 }
@@ -128,7 +128,7 @@ int rbg_text_runs_fill_dev(const uint8_t *d_text, const void *d_sa, uint64_t n, 
                            uint8_t *d_heads, uint64_t *d_lens, uint64_t *d_ssa, uint64_t *d_esa, void *stream) {
     return guarded([&]() -> int {
     if (!d_text || !d_sa || !d_tmp || !d_heads || !d_lens || !d_ssa || !d_esa || n == 0 || R == 0 || R > n || !pos_bytes_ok(n, pos_bytes)) return RBG_EARG;
-    if (tmp_bytes < text_runs_tmp_bytes(n, pos_bytes) || (reinterpret_cast<uintptr_t>(d_tmp) & 255)) return RBG_EARG;
+    if (tmp_bytes < text_runs_tmp_bytes(n, pos_bytes) || (reinterpret_cast<uintptr_t>(d_tmp) & 255) || (reinterpret_cast<uintptr_t>(d_sa) & (pos_bytes - 1))) return RBG_EARG;
     return sa_rc(text_runs_fill(d_text, d_sa, n, pos_bytes, d_tmp, tmp_bytes, R, d_heads, d_lens, d_ssa, d_esa, stream));
     });
 }

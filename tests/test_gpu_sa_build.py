@@ -16,6 +16,7 @@ import torch
 
 import naive
 import rowbowt_amd as ra
+import sa_scale_cases as SC
 from rowbowt_amd import capi
 from rowbowt_amd.tools import synth_pangenome as SP
 from arena import Arena
@@ -114,6 +115,12 @@ def expected(name):
     return np.asarray(sa, np.int64), heads, lens, ssa, esa
 
 
+@functools.lru_cache(maxsize=None)
+def counters(name):
+    """{rounds, sorted, tied_after_first} of the build by the counter model: once per text, shared by both widths"""
+    return SC.counter_model(texts()[name], expected(name)[0])
+
+
 def run_sa(text, pb, want_rc=0):
     """rbg_suffix_array_dev on a guarded arena -> (rc, the bytes of d_sa, the arena); the text's region and every guard byte are checked"""
     L = ra.lib()
@@ -166,6 +173,8 @@ def test_suffix_array_and_runs_of_every_text(pb):
         bad = np.flatnonzero(got.astype(np.int64) != sa)
         assert len(bad) == 0, (name, pb, bad[:5], got[bad[:5]], sa[bad[:5]])
         info = check_info(len(t), pb)
+        # exactly what the LCP array says: a suffix leaves the list when no other shares its first 8 * 2^k symbols (sa_scale_cases.counter_model)
+        assert {k: info[k] for k in ("rounds", "sorted", "tied_after_first")} == counters(name), (name, pb, info, counters(name))
         if name == "near copies":
             lcp = max_lcp(t, sa)
             assert lcp >= 3000 and rounds_model(lcp) >= 10 and info["rounds"] == rounds_model(lcp), (lcp, info)
