@@ -215,8 +215,16 @@ typedef struct rbg_jump_info_t {
     uint64_t bytes;      /* HBM of the table (counted in rbg_info().hbm_bytes) */
     uint64_t buckets;    /* 64-byte buckets of two slots */
     double build_ms;     /* wall time of enumerating, searching and inserting the keys */
+    /* Level 2 (RBG_OPT_JUMP2_K), a second table probed after a hit of the first: the state after every occurring word of k + k2 symbols,
+     * keyed by the k2 symbols and the first table's lo.  Only rbg_jump_info_sized fills these; all zero when there is none. */
+    uint64_t k2;         /* symbols per key of level 2 */
+    uint64_t keys2;
+    uint64_t bytes2;     /* (counted in rbg_info().hbm_bytes as well) */
+    uint64_t buckets2;
+    double build2_ms;    /* wall time of level 2 alone; build_ms does not include it */
 } rbg_jump_info_t;
-int rbg_jump_info(const rbg_index *, rbg_jump_info_t *out);
+int rbg_jump_info(const rbg_index *, rbg_jump_info_t *out);   /* the first five fields (40 bytes), as before level 2 existed */
+int rbg_jump_info_sized(const rbg_index *, rbg_jump_info_t *out, uint64_t out_bytes);   /* min(out_bytes, sizeof) bytes; fields are only added at the end */
 
 /* RowBowt::get_f(), rowbowt.hpp:719 / build_f :770-778: 256 entries. */
 int rbg_get_f(const rbg_index *, uint64_t f_out[256]);
@@ -1064,7 +1072,7 @@ int rbg_sample_reads_pangenome_dev(const uint8_t *d_base, const uint64_t *d_site
  * RBG_RUN_FILL_SHIFT / RBG_PHI_SUPER_SHIFT lower the filler distance / super-count spacing of 8-byte positions so that tests
  * meet both on small indexes;  RBG_HOST_THREADS, RBG_HOST_CHUNK_READS, RBG_HOST_DIRECT_OUT=0, RBG_HOST_COMBINE=0,
  * RBG_HOST_TRACE=1|2 tune / trace the host-pointer pipeline;  RBG_LAYOUT=auto|slots|runs|prefer-slots, RBG_RUN_DEPTHS,
- * RBG_KMER_STEPS, RBG_HBM_BUDGET_MB, RBG_FTAB_K, RBG_JUMP_K, RBG_RUN_PHI, RBG_RUN_REC give the options of the same names their initial values (for
+ * RBG_KMER_STEPS, RBG_HBM_BUDGET_MB, RBG_FTAB_K, RBG_JUMP_K, RBG_JUMP2_K, RBG_RUN_PHI, RBG_RUN_REC give the options of the same names their initial values (for
  * the command-line tools, which keep the reference's flags; rbg_set_default_option overrides them);  RBG_H2D_STAGED=0 uploads the big
  * arrays of a load by plain hipMemcpy;  RBG_VERBOSE=1 prints what the budget rule did and the seconds of every stage of a load. */
 enum { RBG_OPT_BLOCK_THREADS = 1, RBG_OPT_RANK_BUCKET_SHIFT = 2, RBG_OPT_PHI_BUCKET_SHIFT = 3, RBG_OPT_POS_BYTES = 4,
@@ -1099,7 +1107,10 @@ enum { RBG_OPT_BLOCK_THREADS = 1, RBG_OPT_RANK_BUCKET_SHIFT = 2, RBG_OPT_PHI_BUC
        RBG_OPT_EXTRACT_CHUNK = 20 /* rbg_extract: the bases per piece an interval is cut into before the upload (1 .. 2^30; default 128, the fastest of 64 .. 4096 in profiles/extract_rate.txt).  The result
                                   does not depend on it */,
        RBG_OPT_JUMP_K = 19 /* the jump table (rbg_jump_info): 0 = none, 16..64 = a table of that many symbols per key, -1 (default) = 60 symbols
-                                  when the replica is larger than the device's 256 MB last-level cache and the table adds at most half of it, none otherwise.  RBG_JUMP_K gives the initial value. */ };
+                                  when the replica is larger than the device's 256 MB last-level cache and the table adds at most half of it, none otherwise.  RBG_JUMP_K gives the initial value. */,
+       RBG_OPT_JUMP2_K = 21 /* level 2 of the jump table (rbg_jump_info_sized), built only where the first table is: 0 = none, 16..48 = that many more symbols, -1 (default) = 40
+                                  where the first table is the automatic one of 60 symbols and both tables together add at most the replica, none otherwise.  RBG_JUMP2_K gives
+                                  the initial value. */ };
 int rbg_set_default_option(int opt, int64_t value);
 /* the value a later load would use (so that a caller can change a knob for one load and put it back) */
 int rbg_get_default_option(int opt, int64_t *value);

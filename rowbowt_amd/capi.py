@@ -24,6 +24,7 @@ OPT_BLOCK_THREADS, OPT_RANK_BUCKET_SHIFT, OPT_PHI_BUCKET_SHIFT, OPT_POS_BYTES, O
 OPT_RUN_DEPTHS, OPT_RUN_PHI, OPT_RUN_REC, OPT_RUN_REC_DEPTHS = 14, 16, 17, 18   # (12, 13, 15 were TREE_TOP_KB, SLOT_BYTES, RUN_FMT: retired with ABI 3)
 OPT_EXTRACT_CHUNK = 20   # rbg_extract: bases per piece of a split interval (the result does not depend on it)
 OPT_JUMP_K = 19          # the jump table (rbg_jump_info): 0 = off, -1 = automatic, 16..64 = symbols per key
+OPT_JUMP2_K = 21         # level 2 of the jump table: 0 = off, -1 = automatic, 16..48 = symbols per key after the first table's
 ABI_VERSION = 3          # include/rbg.h RBG_ABI_VERSION this binding is written against
 MAX_KMER_DEPTH = 8       # RBG_OPT_KMER_STEPS / the depth arrays of Info and LayoutInfo
 LAYOUT_AUTO, LAYOUT_SLOTS, LAYOUT_RUNS, LAYOUT_PREFER_SLOTS = 0, 1, 2, 3
@@ -69,7 +70,8 @@ class LayoutInfo(C.Structure):
 
 class JumpInfo(C.Structure):
     """rbg_jump_info_t"""
-    _fields_ = [("k", U64), ("keys", U64), ("bytes", U64), ("buckets", U64), ("build_ms", C.c_double)]
+    _fields_ = [("k", U64), ("keys", U64), ("bytes", U64), ("buckets", U64), ("build_ms", C.c_double),
+                ("k2", U64), ("keys2", U64), ("bytes2", U64), ("buckets2", U64), ("build2_ms", C.c_double)]   # level 2 (rbg_jump_info_sized)
 
 
 class ReportParams(C.Structure):
@@ -132,6 +134,7 @@ _PROTOS = [
     ("rbg_info_sized", C.c_int, [VP, C.POINTER(Info), U64]),
     ("rbg_layout_info", C.c_int, [VP, C.POINTER(LayoutInfo), U64]),
     ("rbg_jump_info", C.c_int, [VP, C.POINTER(JumpInfo)]),
+    ("rbg_jump_info_sized", C.c_int, [VP, C.POINTER(JumpInfo), U64]),
     ("rbg_get_f", C.c_int, [VP, VP]),
     ("rbg_last_run_sample", C.c_int, [VP, C.POINTER(U64)]),
     ("rbg_host_array", C.c_int, [VP, C.c_int, VP, U64, C.POINTER(U64)]),
@@ -264,7 +267,7 @@ _PROTOS = [
     ("rbg_get_default_option", C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
 ]
 EXPORTS = [p[0] for p in _PROTOS]
-_OPTIONAL = {"rbg_jump_info"}
+_OPTIONAL = {"rbg_jump_info", "rbg_jump_info_sized"}
 
 _lib = None
 
@@ -602,7 +605,10 @@ class RowBowt:
     def jump_info(self):
         """the jump table of this replica (rbg_jump_info_t; all zero when none was built)"""
         i = JumpInfo()
-        _check(self.L.rbg_jump_info(self.h, C.byref(i)), "rbg_jump_info")
+        if hasattr(self.L, "rbg_jump_info_sized"):
+            _check(self.L.rbg_jump_info_sized(self.h, C.byref(i), C.sizeof(i)), "rbg_jump_info_sized")
+        else:   # (a library of before level 2: its five fields; the rest stay zero)
+            _check(self.L.rbg_jump_info(self.h, C.byref(i)), "rbg_jump_info")
         return i
 
     def layout_info(self):

@@ -45,6 +45,9 @@ struct rbg_index {
     // the jump table (rbg_jump_info): K, keys, bytes, buckets, build time (0 when none was built)
     uint64_t jump_k = 0, jump_keys = 0, jump_bytes = 0, jump_buckets = 0;
     double jump_build_ms = 0.0;
+    // ... and its level 2 (0 when none was built)
+    uint64_t jump2_k = 0, jump2_keys = 0, jump2_bytes = 0, jump2_buckets = 0;
+    double jump2_build_ms = 0.0;
     // what the load decided about the run-indexed layout (rbg_layout_info): nothing is left out without a line here
     struct RunsReport {
         uint32_t fmt = 0, depth_mask_asked = 0, depth_mask_kept = 0, depths_composed = 0;
@@ -134,6 +137,16 @@ int64_t env_jump_k() {
     return v;
 }
 std::atomic<int64_t> g_opt_jump_k{env_jump_k()};
+// RBG_OPT_JUMP2_K: -1 = automatic (kJump2DefaultK where level 1 was built automatically), 0 = off, kJump2MinK..kJump2MaxK = that K2
+int64_t env_jump2_k() {
+    const int64_t v = env_opt("RBG_JUMP2_K", -1, -1, kJump2MaxK);
+    if (v > 0 && v < static_cast<int64_t>(kJump2MinK)) {
+        std::fprintf(stderr, "rbg: RBG_JUMP2_K=%lld ignored (expected -1, 0 or %u..%u)\n", static_cast<long long>(v), kJump2MinK, kJump2MaxK);
+        return -1;
+    }
+    return v;
+}
+std::atomic<int64_t> g_opt_jump2_k{env_jump2_k()};
 std::atomic<int64_t> g_opt_deep_shift{-1};
 std::atomic<int64_t> g_opt_dense_overflow{1};
 std::atomic<int64_t> g_opt_rank_layout{env_opt("RBG_LAYOUT", RBG_LAYOUT_AUTO, RBG_LAYOUT_AUTO, RBG_LAYOUT_PREFER_SLOTS)};    // RBG_LAYOUT_AUTO / _SLOTS / _RUNS / _PREFER_SLOTS

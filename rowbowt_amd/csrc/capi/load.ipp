@@ -278,10 +278,14 @@ int build_jump_table(rbg_index *ix) {
     d.jump = nullptr;
     d.jump_buckets = 0;
     d.jump_k = 0;
+    d.jump2_buckets = 0;
+    d.jump2_k = 0;
     int64_t jk = g_opt_jump_k.load();
     const bool jump_auto = jk < 0;
     if (jump_auto) jk = auto_jump_k(ix->hbm_bytes);
     if (jk <= 0) return RBG_OK;
+    // level 2 (rbg_jump.h): only where level 1 is, after it, from what the budget still leaves
+    const int64_t jk2 = jump2_k_for(g_opt_jump2_k.load(), jump_auto, jk);
     VStage vs("jump table");
     const auto t0 = std::chrono::steady_clock::now();
     size_t free_b = 0, total_b = 0;
@@ -290,14 +294,16 @@ int build_jump_table(rbg_index *ix) {
     void *tab = nullptr;
     uint64_t bytes = 0, nb = 0, keys = 0;
     const char *why = nullptr;
-    int rc = launch_build_jump(d, ix->cfg, static_cast<uint32_t>(jk), jb.table_budget, jb.peak_budget, &tab, &bytes, &nb, &keys, &why, nullptr);
+    JumpLevel2 l2;
+    int rc = launch_build_jump(d, ix->cfg, static_cast<uint32_t>(jk), jb.table_budget, jb.peak_budget, &tab, &bytes, &nb, &keys, &why, nullptr,
+                               static_cast<uint32_t>(jk2), jb.both_budget, &l2);
     if (rc == static_cast<int>(hipErrorOutOfMemory)) { (void)hipGetLastError(); rc = 0; why = "out of device memory while building it"; }
     if (rc) return RBG_ENODEV;
     HIP_TRY(hipMemset(d.counters, 0, 4 * sizeof(uint64_t)));  // (the build's own searches are not user queries)
-    ix->jump_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ix->jump_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - l2.build_ms;
     if (tab) {
-        ix->allocs.push_back({tab, static_cast<size_t>(bytes)});
-        ix->hbm_bytes += bytes;
+        ix->allocs.push_back({tab, static_cast<size_t>(bytes + l2.bytes)});   // (level 2 lies behind level 1 in the same array)
+        ix->hbm_bytes += bytes + l2.bytes;
         d.jump = tab;
         d.jump_buckets = nb;
         d.jump_k = static_cast<uint32_t>(jk);
@@ -308,6 +314,21 @@ int build_jump_table(rbg_index *ix) {
         if (std::getenv("RBG_VERBOSE"))
             std::fprintf(stderr, "rbg: device %d: jump table of %lld-mers: %llu keys, %.2f GB, %.0f ms\n", ix->device, static_cast<long long>(jk),
                          static_cast<unsigned long long>(keys), bytes / 1e9, ix->jump_build_ms);
+        if (l2.tab) {
+            d.jump2_buckets = l2.buckets;
+            d.jump2_k = static_cast<uint32_t>(jk2);
+            ix->jump2_k = static_cast<uint64_t>(jk2);
+            ix->jump2_keys = l2.keys;
+            ix->jump2_bytes = l2.bytes;
+            ix->jump2_buckets = l2.buckets;
+            ix->jump2_build_ms = l2.build_ms;
+            if (std::getenv("RBG_VERBOSE"))
+                std::fprintf(stderr, "rbg: device %d: jump table, level 2, of %lld + %lld symbols: %llu keys, %.2f GB, %.0f ms\n", ix->device,
+                             static_cast<long long>(jk), static_cast<long long>(jk2), static_cast<unsigned long long>(l2.keys), l2.bytes / 1e9, l2.build_ms);
+        } else if (jk2 > 0 && std::getenv("RBG_VERBOSE")) {
+            std::fprintf(stderr, "rbg: device %d: no level 2 of the jump table (%lld + %lld symbols; %llu words occur): %s\n", ix->device, static_cast<long long>(jk),
+                         static_cast<long long>(jk2), static_cast<unsigned long long>(l2.keys), l2.why ? l2.why : "skipped");
+        }
     } else if (std::getenv("RBG_VERBOSE")) {
         std::fprintf(stderr, "rbg: device %d: no jump table of %lld-mers (%llu occur): %s\n", ix->device, static_cast<long long>(jk),
                      static_cast<unsigned long long>(keys), why ? why : "skipped");
@@ -680,6 +701,9 @@ int rbg_set_default_option(int opt, int64_t value) {
         case RBG_OPT_JUMP_K:
             if (value < -1 || value > static_cast<int64_t>(kJumpMaxK) || (value > 0 && value < static_cast<int64_t>(kJumpMinK))) return RBG_EARG;
             g_opt_jump_k = value; return RBG_OK;
+        case RBG_OPT_JUMP2_K:
+            if (value < -1 || value > static_cast<int64_t>(kJump2MaxK) || (value > 0 && value < static_cast<int64_t>(kJump2MinK))) return RBG_EARG;
+            g_opt_jump2_k = value; return RBG_OK;
         case RBG_OPT_EXTRACT_CHUNK:
             if (value < 1 || value > (int64_t(1) << 30)) return RBG_EARG;
             g_opt_extract_chunk = value; return RBG_OK;
@@ -708,6 +732,7 @@ int rbg_get_default_option(int opt, int64_t *value) {
         case RBG_OPT_RUN_REC: *value = g_opt_run_rec.load(); return RBG_OK;
         case RBG_OPT_RUN_REC_DEPTHS: *value = g_opt_run_rec_depths.load(); return RBG_OK;
         case RBG_OPT_JUMP_K: *value = g_opt_jump_k.load(); return RBG_OK;
+        case RBG_OPT_JUMP2_K: *value = g_opt_jump2_k.load(); return RBG_OK;
         case RBG_OPT_EXTRACT_CHUNK: *value = g_opt_extract_chunk.load(); return RBG_OK;
         default: return RBG_EARG;
     }
@@ -1101,19 +1126,35 @@ int rbg_info_sized(const rbg_index *ix, rbg_info_t *out, uint64_t out_bytes) {
     return RBG_OK;
 }
 
-int rbg_jump_info(const rbg_index *ix, rbg_jump_info_t *out) {
+// min(out_bytes, sizeof(rbg_jump_info_t)) bytes: the struct grew by level 2, at its end (as rbg_info_sized)
+int rbg_jump_info_sized(const rbg_index *ix, rbg_jump_info_t *out, uint64_t out_bytes) {
     return guarded([&]() -> int {
-    if (!ix || !out) return RBG_EARG;
-    const rbg_index *s = ix->primary ? ix->primary : ix;   // (a replica holds a copy of its primary's table)
-    std::memset(out, 0, sizeof(*out));
-    if (!ix->dev.jump) return RBG_OK;
-    out->k = ix->dev.jump_k;
-    out->keys = s->jump_keys;
-    out->bytes = s->jump_bytes;
-    out->buckets = ix->dev.jump_buckets;
-    out->build_ms = s->jump_build_ms;
+    if (!ix || !out || out_bytes < 8) return RBG_EARG;
+    const rbg_index *s = ix->primary ? ix->primary : ix;   // (a replica holds a copy of its primary's tables)
+    rbg_jump_info_t v;
+    std::memset(&v, 0, sizeof(v));
+    if (ix->dev.jump) {
+        v.k = ix->dev.jump_k;
+        v.keys = s->jump_keys;
+        v.bytes = s->jump_bytes;
+        v.buckets = ix->dev.jump_buckets;
+        v.build_ms = s->jump_build_ms;
+    }
+    if (ix->dev.jump2_k) {
+        v.k2 = ix->dev.jump2_k;
+        v.keys2 = s->jump2_keys;
+        v.bytes2 = s->jump2_bytes;
+        v.buckets2 = ix->dev.jump2_buckets;
+        v.build2_ms = s->jump2_build_ms;
+    }
+    std::memcpy(out, &v, static_cast<size_t>(std::min<uint64_t>(out_bytes, sizeof(v))));
     return RBG_OK;
     });
+}
+
+// the caller of before level 2: the five fields the struct had then, and not a byte more
+int rbg_jump_info(const rbg_index *ix, rbg_jump_info_t *out) {
+    return rbg_jump_info_sized(ix, out, offsetof(rbg_jump_info_t, k2));
 }
 
 int rbg_info(const rbg_index *ix, rbg_info_t *out) {

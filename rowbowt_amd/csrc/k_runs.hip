@@ -75,6 +75,20 @@ __device__ __forceinline__ bool jump_probe_wave(const void *__restrict__ tab, co
     return state <= kJumpHit1;
 }
 
+// a 64-bit value every lane holds alike (read from LDS), as scalars
+__device__ __forceinline__ uint64_t uniform_u64(const uint64_t v) {
+    // (the builtin returns int: through uint32_t, or the low half is sign-extended over the high one)
+    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v)));
+    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32)));
+    return static_cast<uint64_t>(lo) | (static_cast<uint64_t>(hi) << 32);
+}
+
+// word j of a lane's staged read (rbg_runs_device.hpp: the lane's column, word w at codes[64 w]), for jump_key_from_codes
+struct StagedWords {
+    const lds_u32 *codes;
+    __device__ __forceinline__ uint32_t operator()(const uint32_t j) const { return codes[64u * j]; }
+};
+
 // (the staging of a wave's reads as 2-bit codes in LDS -- stage_read, StageTab, kStageCap -- lives in rbg_runs_device.hpp: the seeding kernels use it too)
 // GLDS: the bucket records arrive by LDS-direct loads (rbg_runs2_device.hpp lane_lf2_quad) instead of quad permutes
 // STAGE (byte form only): the wave stages its reads as 2-bit codes in LDS first (above)
@@ -96,9 +110,19 @@ __global__ __launch_bounds__(512, STATS ? 2 : 4) void k_find_range_runs(const De
     __shared__ uint8_t s_mslot[4];
     __shared__ __align__(16) unsigned char s_tile[GLDS ? 8 * kTileBytes : 16];   // (eight waves per workgroup)
     __shared__ uint32_t s_codes[STAGE ? 8 * kStageWords * 64 : 1];               // STAGE: the waves' reads as 2-bit codes
+    // the jump table's levels {table, buckets, K} (STAGE): the probe loop reads its level's from here -- both levels' held in scalar
+    // registers across the loop were nine more than the kernel has
+    __shared__ uint64_t s_jump[STAGE ? 4 : 1];
+    __shared__ uint32_t s_jump_k[STAGE ? 2 : 1];
     for (int t = threadIdx.x; t < 256; t += blockDim.x) {
         s_lut[t] = ix.lut[t];
         s_lut2[t] = ix.nmajor ? ix.lut2[t] : 0xFFu;
+    }
+    if (STAGE && threadIdx.x < 2) {
+        const uint32_t t = threadIdx.x;
+        s_jump[2 * t] = reinterpret_cast<uint64_t>(ix.jump) + (t ? ix.jump_buckets * kJumpBucketBytes : 0u);   // (level 2 lies behind level 1)
+        s_jump[2 * t + 1] = t ? ix.jump2_buckets : ix.jump_buckets;
+        s_jump_k[t] = t ? ix.jump2_k : ix.jump_k;
     }
     RBG_RUN_SEARCH2_SHARED;
     const RunSearch2<P> S2 = stage_run_search2<P>(ix, s_tab_first, s_ent2, s_dir2, s_rec2, s_dyn);
@@ -164,18 +188,32 @@ __global__ __launch_bounds__(512, STATS ? 2 : 4) void k_find_range_runs(const De
             bool jumped = false;
             if constexpr (STAGED && sizeof(P) == 4) {
                 if (ix.jump) {                                     // (wave-uniform)
-                    const bool probing = valid && m32 >= ix.jump_k;
-                    JumpKey key{{codes[0], codes[64], codes[128], codes[192]}};   // the first 64 symbols in consumption order
-                    jump_key_mask(key, ix.jump_k);
-                    uint32_t v[3] = {0, 0, 0}, nbk = 0;
-                    if (jump_probe_wave<GLDS>(ix.jump, ix.jump_buckets, probing, key, v, nbk, tile)) {
-                        lo = v[0]; hi = v[1];
-                        if (TOEHOLD) k = v[2] == 0xFFFFFFFFu ? ~uint64_t(0) : static_cast<uint64_t>(v[2]);
-                        p -= ix.jump_k;
-                        jumped = true;
-                        if (STATS) st[kStSymbols] += ix.jump_k;
+                    // Level 2 (ix.jump2_k): a lane that hit level 1 and has jump2_k symbols left looks {those symbols, its lo} up in the second
+                    // table; a hit replaces the state once more, an absent key leaves level 1's and the steps go on from there.  One loop over
+                    // the levels: the probe is inlined once.
+                    const uint32_t nlev = ix.jump2_k ? 2u : 1u;
+                    bool hit = valid;                              // of the level before
+                    uint32_t from = 0;                             // symbols the levels before consumed
+#pragma unroll 1
+                    for (uint32_t lev = 0; lev < nlev; ++lev) {
+                        const uint32_t K = __builtin_amdgcn_readfirstlane(s_jump_k[lev]);
+                        const uint64_t tab = uniform_u64(s_jump[2 * lev]), nb = uniform_u64(s_jump[2 * lev + 1]);
+                        const bool probing = hit && static_cast<uint32_t>(p) >= K;
+                        // level 1: the first jump_k symbols in consumption order; level 2: the jump2_k after them, and lo in the last word
+                        JumpKey key = jump_key_from_codes(StagedWords{codes}, from, K);
+                        if (lev) key.w[3] = static_cast<uint32_t>(lo);
+                        from = K;
+                        uint32_t v[3] = {0, 0, 0}, nbk = 0;
+                        hit = jump_probe_wave<GLDS>(reinterpret_cast<const void *>(tab), nb, probing, key, v, nbk, tile);
+                        if (hit) {
+                            lo = v[0]; hi = v[1];
+                            if (TOEHOLD) k = v[2] == 0xFFFFFFFFu ? ~uint64_t(0) : static_cast<uint64_t>(v[2]);
+                            p -= K;
+                            jumped = true;
+                            if (STATS) st[kStSymbols] += K;
+                        }
+                        if (STATS) st[kStFtab] += nbk;               // (the ftab slot counts probed buckets too: 64 bytes each, of either level)
                     }
-                    if (STATS) st[kStFtab] += nbk;                   // (the ftab slot counts probed buckets too: 64 bytes each)
                 }
             }
             if (!jumped && valid && ix.ftab_k && p - beg >= ix.ftab_k) {      // rowbowt.hpp:124-125, :745-758 (k_search.hip)

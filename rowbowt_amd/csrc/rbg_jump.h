@@ -107,6 +107,53 @@ RBG_JUMP_HD bool jump_probe(const Load &load, uint64_t nb, const JumpKey &key, u
     return false;
 }
 
+// ---- level 2: a second table, probed after a hit of the first --------------------------------------------------------------------
+// The state after K1 + K2 symbols is a function of those symbols alone, but a key holds 64.  `lo` of a non-empty range after K1 symbols
+// names that K1-mer uniquely (two different K1-mers have disjoint ranges), so the key of level 2 is {the K2 <= 48 symbols that follow
+// the first K1 in consumption order (w[0..2], masked to K2), the parent range's lo (w[3])}: 128 bits again, same slot, same bucket,
+// same probe.  Level 2 is a table of its own (DevIndex::jump2_buckets, behind the first in its allocation): its keys never meet a key of level 1.
+constexpr uint32_t kJump2MaxK = 48;     // 96 bits of symbols beside the parent's lo
+constexpr uint32_t kJump2MinK = 16;
+constexpr uint32_t kJump2DefaultK = 40;  // RBG_OPT_JUMP2_K = -1 where level 1 is automatic at K1 = 60: 60 + 40 = 100
+
+// the key of level 2 from three words of symbols (the K2 symbols in consumption order from bit 0; anything above 2 K2 is dropped) and the parent's lo
+RBG_JUMP_HD JumpKey jump2_key(uint32_t s0, uint32_t s1, uint32_t s2, uint32_t K2, uint32_t parent_lo) {
+    JumpKey key{{s0, s1, s2, 0u}};
+    jump_key_mask(key, K2);
+    key.w[3] = parent_lo;
+    return key;
+}
+
+// The K symbols of a read from symbol `from` on, as a key: word(j) = the read's symbols [16 j, 16 j + 16) in consumption order, 2 bits each
+// (the staged read's LDS words, a packed chunk's).  Reads words from / 16 .. from / 16 + 4 (the last one only for its low bits; it must
+// exist).  from = 0, K = K1: the key of level 1.
+template <typename Word>
+RBG_JUMP_HD JumpKey jump_key_from_codes(const Word &word, uint32_t from, uint32_t K) {
+    const uint32_t w0 = from >> 4, sh = 2u * (from & 15u);
+    const uint32_t c0 = word(w0), c1 = word(w0 + 1), c2 = word(w0 + 2), c3 = word(w0 + 3), c4 = word(w0 + 4);
+    const auto funnel = [sh](uint32_t lo, uint32_t hi) { return static_cast<uint32_t>(((static_cast<uint64_t>(hi) << 32) | lo) >> sh); };
+    JumpKey key{{funnel(c0, c1), funnel(c1, c2), funnel(c2, c3), funnel(c3, c4)}};   // (written out: no array is indexed by a loop variable)
+    jump_key_mask(key, K);
+    return key;
+}
+
+// ... the key of level 2 from a read's codes: the K2 <= 48 symbols from symbol K1 on, and the parent's lo
+template <typename Word>
+RBG_JUMP_HD JumpKey jump2_key_from_codes(const Word &word, uint32_t K1, uint32_t K2, uint32_t parent_lo) {
+    JumpKey key = jump_key_from_codes(word, K1, K2);   // (K2 <= 48: w[3] is masked to zero)
+    key.w[3] = parent_lo;
+    return key;
+}
+
+// ... from a text word (the host model): text[0 .. K1 + K2) as 2-bit codes, the LAST symbol consumed first (backward search), so symbol t of
+// the level-2 key is text[K2 - 1 - t] -- the K2 symbols to the left of the K1-mer text[K2 .. K2 + K1)
+RBG_JUMP_HD JumpKey jump2_key_from_text(const uint8_t *codes, uint32_t K2, uint32_t parent_lo) {
+    JumpKey key{{0, 0, 0, 0}};
+    for (uint32_t t = 0; t < K2; ++t) jump_key_set(key, t, codes[K2 - 1 - t]);
+    key.w[3] = parent_lo;
+    return key;
+}
+
 // buckets of a table holding `keys` keys at a load of at most one half (two slots per bucket), at least one
 inline uint64_t jump_buckets_for(uint64_t keys) { return keys ? keys : 1; }
 

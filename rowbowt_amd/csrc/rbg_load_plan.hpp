@@ -447,16 +447,28 @@ inline int64_t auto_jump_k(uint64_t hbm_bytes) { return hbm_bytes > kJumpAutoMin
 // what the HBM budget leaves after the replica holds the build at its peak (scratch + table), and at most half of the free memory; by default the table
 // may add at most half of the replica: on a text of few repeats -- nearly every K-mer distinct -- it would outgrow the index it serves (the bench index's
 // is a third)
+// Level 2 comes after level 1 and changes nothing of its rule: the first table is decided as if there were no second.  The two TOGETHER may
+// take what the budget leaves and at most half of the free memory (the build's peak, scratch included, stays within that too); by default
+// they may add at most the replica itself -- the bench index's two are three quarters of it.
 struct JumpBudgets {
-    uint64_t room, peak_budget, table_budget;
+    uint64_t room, peak_budget, table_budget, both_budget;
 };
 inline JumpBudgets jump_budgets(uint64_t hbm_budget, uint64_t hbm_bytes, size_t free_b, bool jump_auto) {
     JumpBudgets j;
     j.room = hbm_budget > hbm_bytes ? hbm_budget - hbm_bytes : 0;
     j.peak_budget = std::min<uint64_t>(j.room, free_b / 2);
     j.table_budget = std::min<uint64_t>(j.room, free_b / 4);
-    if (jump_auto) j.table_budget = std::min<uint64_t>(j.table_budget, hbm_bytes / 2);
+    j.both_budget = j.peak_budget;
+    if (jump_auto) {
+        j.table_budget = std::min<uint64_t>(j.table_budget, hbm_bytes / 2);
+        j.both_budget = std::min<uint64_t>(j.both_budget, hbm_bytes);
+    }
     return j;
+}
+// level 2: asked for (16..48), or automatic -- 40 symbols where level 1 is the automatic one at its default of 60 (60 + 40 = 100), none otherwise
+inline int64_t jump2_k_for(int64_t opt, bool jump_auto, int64_t jk) {
+    if (opt >= 0) return opt;
+    return jump_auto && jk == static_cast<int64_t>(kJumpDefaultK) ? static_cast<int64_t>(kJump2DefaultK) : 0;
 }
 
 }  // namespace rbg
