@@ -222,6 +222,11 @@ typedef struct rbg_jump_info_t {
     uint64_t bytes2;     /* (counted in rbg_info().hbm_bytes as well) */
     uint64_t buckets2;
     double build2_ms;    /* wall time of level 2 alone; build_ms does not include it */
+    /* The levels that are complete: bit 0 = level 1, bit 1 = level 2.  Every word that occurs in the text is in a complete table, so a read whose
+     * key it lacks has an empty range and ends at the probe instead of walking the ftab path to the same answer.  A level whose build left a word
+     * out is not complete; RBG_JUMP_ABSENT_ENDS=0 in the environment of a load leaves none (same tables, same answers).  Only rbg_jump_info_sized
+     * with a buffer of at least 88 bytes fills it. */
+    uint64_t complete;
 } rbg_jump_info_t;
 int rbg_jump_info(const rbg_index *, rbg_jump_info_t *out);   /* the first five fields (40 bytes), as before level 2 existed */
 int rbg_jump_info_sized(const rbg_index *, rbg_jump_info_t *out, uint64_t out_bytes);   /* min(out_bytes, sizeof) bytes; fields are only added at the end */
@@ -1073,7 +1078,8 @@ int rbg_sample_reads_pangenome_dev(const uint8_t *d_base, const uint64_t *d_site
  * meet both on small indexes;  RBG_HOST_THREADS, RBG_HOST_CHUNK_READS, RBG_HOST_DIRECT_OUT=0, RBG_HOST_COMBINE=0,
  * RBG_HOST_TRACE=1|2 tune / trace the host-pointer pipeline;  RBG_LAYOUT=auto|slots|runs|prefer-slots, RBG_RUN_DEPTHS,
  * RBG_KMER_STEPS, RBG_HBM_BUDGET_MB, RBG_FTAB_K, RBG_JUMP_K, RBG_JUMP2_K, RBG_RUN_PHI, RBG_RUN_REC give the options of the same names their initial values (for
- * the command-line tools, which keep the reference's flags; rbg_set_default_option overrides them);  RBG_H2D_STAGED=0 uploads the big
+ * the command-line tools, which keep the reference's flags; rbg_set_default_option overrides them);  RBG_JUMP_ABSENT_ENDS=0 lets no level of the jump table
+ * count as complete (rbg_jump_info_t::complete; read at every load);  RBG_H2D_STAGED=0 uploads the big
  * arrays of a load by plain hipMemcpy;  RBG_VERBOSE=1 prints what the budget rule did and the seconds of every stage of a load. */
 enum { RBG_OPT_BLOCK_THREADS = 1, RBG_OPT_RANK_BUCKET_SHIFT = 2, RBG_OPT_PHI_BUCKET_SHIFT = 3, RBG_OPT_POS_BYTES = 4,
        RBG_OPT_KMER_STEPS = 5, RBG_OPT_HBM_BUDGET_MB = 6, RBG_OPT_FTAB_K = 7, RBG_OPT_PACKED_READS = 8,

@@ -74,6 +74,11 @@ class JumpInfo(C.Structure):
                 ("k2", U64), ("keys2", U64), ("bytes2", U64), ("buckets2", U64), ("build2_ms", C.c_double)]   # level 2 (rbg_jump_info_sized)
 
 
+class JumpInfoComplete(C.Structure):
+    """rbg_jump_info_t with the field added after level 2; JumpInfo stays the 80-byte prefix it was (rbg_jump_info_sized writes what it is given room for)"""
+    _fields_ = JumpInfo._fields_ + [("complete", U64)]   # bit 0 / bit 1: an absent key of level 1 / level 2 ends the read at the probe
+
+
 class ReportParams(C.Structure):
     """rbg_report_params_t"""
     _fields_ = [(n, U64) for n in ("wsize", "max_range", "min_range", "ftab_k", "read_len", "min_seed_len")] + [("flags", C.c_uint32)]
@@ -610,6 +615,14 @@ class RowBowt:
         else:   # (a library of before level 2: its five fields; the rest stay zero)
             _check(self.L.rbg_jump_info(self.h, C.byref(i)), "rbg_jump_info")
         return i
+
+    def jump_complete(self):
+        """the levels of this replica's jump table that are complete (rbg_jump_info_t.complete: bit 0 = level 1, bit 1 = level 2; 0 without a table,
+        under RBG_JUMP_ABSENT_ENDS=0, or from a library of before the field)"""
+        i = JumpInfoComplete()
+        if hasattr(self.L, "rbg_jump_info_sized"):
+            _check(self.L.rbg_jump_info_sized(self.h, C.cast(C.byref(i), C.POINTER(JumpInfo)), C.sizeof(i)), "rbg_jump_info_sized")
+        return int(i.complete)
 
     def layout_info(self):
         """what the load decided about the run-indexed layout (rbg_layout_info_t; all zero on the slot layout)"""

@@ -280,6 +280,7 @@ int build_jump_table(rbg_index *ix) {
     d.jump_k = 0;
     d.jump2_buckets = 0;
     d.jump2_k = 0;
+    d.jump_complete = 0;
     int64_t jk = g_opt_jump_k.load();
     const bool jump_auto = jk < 0;
     if (jump_auto) jk = auto_jump_k(ix->hbm_bytes);
@@ -292,11 +293,11 @@ int build_jump_table(rbg_index *ix) {
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     const JumpBudgets jb = jump_budgets(ix->hbm_budget, ix->hbm_bytes, free_b, jump_auto);
     void *tab = nullptr;
-    uint64_t bytes = 0, nb = 0, keys = 0;
+    uint64_t bytes = 0, nb = 0, keys = 0, words = 0;
     const char *why = nullptr;
     JumpLevel2 l2;
     int rc = launch_build_jump(d, ix->cfg, static_cast<uint32_t>(jk), jb.table_budget, jb.peak_budget, &tab, &bytes, &nb, &keys, &why, nullptr,
-                               static_cast<uint32_t>(jk2), jb.both_budget, &l2);
+                               static_cast<uint32_t>(jk2), jb.both_budget, &l2, &words);
     if (rc == static_cast<int>(hipErrorOutOfMemory)) { (void)hipGetLastError(); rc = 0; why = "out of device memory while building it"; }
     if (rc) return RBG_ENODEV;
     HIP_TRY(hipMemset(d.counters, 0, 4 * sizeof(uint64_t)));  // (the build's own searches are not user queries)
@@ -329,6 +330,14 @@ int build_jump_table(rbg_index *ix) {
             std::fprintf(stderr, "rbg: device %d: no level 2 of the jump table (%lld + %lld symbols; %llu words occur): %s\n", ix->device, static_cast<long long>(jk),
                          static_cast<long long>(jk2), static_cast<unsigned long long>(l2.keys), l2.why ? l2.why : "skipped");
         }
+        // the levels whose absent keys end a read at the probe (rbg_jump.h jump_complete_mask).  RBG_JUMP_ABSENT_ENDS=0, read at every load, leaves
+        // none: the same tables, every absent key on the ftab path (the A/B of profiles/r10_jump_absent.md)
+        const char *ae = std::getenv("RBG_JUMP_ABSENT_ENDS");
+        d.jump_complete = jump_complete_mask(JumpBuilt{true, words, keys}, JumpBuilt{l2.tab != nullptr, l2.words, l2.keys}, !(ae && ae[0] == '0'));
+        if (std::getenv("RBG_VERBOSE"))
+            std::fprintf(stderr, "rbg: device %d: jump table: level 1 %llu of %llu words inserted, level 2 %llu of %llu; an absent key ends the read at level%s\n",
+                         ix->device, static_cast<unsigned long long>(keys), static_cast<unsigned long long>(words), static_cast<unsigned long long>(l2.tab ? l2.keys : 0),
+                         static_cast<unsigned long long>(l2.words), d.jump_complete == 3 ? "s 1 and 2" : d.jump_complete == 1 ? " 1" : d.jump_complete == 2 ? " 2" : " none");
     } else if (std::getenv("RBG_VERBOSE")) {
         std::fprintf(stderr, "rbg: device %d: no jump table of %lld-mers (%llu occur): %s\n", ix->device, static_cast<long long>(jk),
                      static_cast<unsigned long long>(keys), why ? why : "skipped");
@@ -1126,7 +1135,7 @@ int rbg_info_sized(const rbg_index *ix, rbg_info_t *out, uint64_t out_bytes) {
     return RBG_OK;
 }
 
-// min(out_bytes, sizeof(rbg_jump_info_t)) bytes: the struct grew by level 2, at its end (as rbg_info_sized)
+// min(out_bytes, sizeof(rbg_jump_info_t)) bytes: the struct grew by level 2 and by `complete`, each time at its end (as rbg_info_sized)
 int rbg_jump_info_sized(const rbg_index *ix, rbg_jump_info_t *out, uint64_t out_bytes) {
     return guarded([&]() -> int {
     if (!ix || !out || out_bytes < 8) return RBG_EARG;
@@ -1147,6 +1156,7 @@ int rbg_jump_info_sized(const rbg_index *ix, rbg_jump_info_t *out, uint64_t out_
         v.buckets2 = ix->dev.jump2_buckets;
         v.build2_ms = s->jump2_build_ms;
     }
+    if (ix->dev.jump) v.complete = ix->dev.jump_complete;
     std::memcpy(out, &v, static_cast<size_t>(std::min<uint64_t>(out_bytes, sizeof(v))));
     return RBG_OK;
     });

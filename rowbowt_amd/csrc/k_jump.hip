@@ -149,8 +149,8 @@ constexpr uint64_t kJumpChunkParents = uint64_t(1) << 24;
 // *retry: a build with a level 2 outgrew the budget before the first table stood (nothing is built; every scratch is freed on return)
 static int build_jump(const DevIndex &ix, const LaunchCfg &cfg, uint32_t K, uint64_t table_budget, uint64_t peak_budget, void **tab,
                       uint64_t *tab_bytes, uint64_t *buckets, uint64_t *keys, const char **why, void *stream, uint32_t K2, uint64_t both_budget,
-                      JumpLevel2 *l2, bool *retry) {
-    *tab = nullptr; *tab_bytes = 0; *buckets = 0; *keys = 0; *why = nullptr;
+                      JumpLevel2 *l2, bool *retry, uint64_t *words) {
+    *tab = nullptr; *tab_bytes = 0; *buckets = 0; *keys = 0; *words = 0; *why = nullptr;
     if (l2) *l2 = JumpLevel2{};
     if (!l2) K2 = 0;
     if (ix.pos_bytes != 4) { *why = "8-byte positions (the table holds 4-byte states)"; return 0; }
@@ -164,6 +164,7 @@ static int build_jump(const DevIndex &ix, const LaunchCfg &cfg, uint32_t K, uint
     plain.jump_k = 0;
     plain.jump2_buckets = 0;
     plain.jump2_k = 0;
+    plain.jump_complete = 0;
     // a build with a level 2 that outgrows the budget before the first table stands starts again without it: level 1 is decided as if there were no level 2
     auto again_without_level2 = [&]() { *retry = true; return 0; };
     const bool wide = K2 != 0;
@@ -270,6 +271,7 @@ static int build_jump(const DevIndex &ix, const LaunchCfg &cfg, uint32_t K, uint
         return 0;
     }
     *keys = F;
+    *words = F;
     const uint64_t nb = jump_buckets_for(F);
     const uint64_t bytes = nb * kJumpBucketBytes;
     if (F == 0 || nb >= (uint64_t(1) << 32)) { *why = F ? "more keys than the table addresses" : "no K-mer occurs"; return 0; }
@@ -329,6 +331,7 @@ static int build_jump(const DevIndex &ix, const LaunchCfg &cfg, uint32_t K, uint
     if (int err = extend(K, K + K2)) return fail2(err);
     if (over) return give_up("its build scratch exceeds what the HBM budget leaves");
     l2->keys = F;
+    l2->words = F;
     const uint64_t nb2 = jump_buckets_for(F);
     const uint64_t bytes2 = nb2 * kJumpBucketBytes;
     if (F == 0 || nb2 >= (uint64_t(1) << 32)) return give_up(F ? "more keys than the table addresses" : "no word of K + K2 symbols occurs");
@@ -360,11 +363,13 @@ static int build_jump(const DevIndex &ix, const LaunchCfg &cfg, uint32_t K, uint
 
 int launch_build_jump(const DevIndex &ix, const LaunchCfg &cfg, uint32_t K, uint64_t table_budget, uint64_t peak_budget, void **tab,
                       uint64_t *tab_bytes, uint64_t *buckets, uint64_t *keys, const char **why, void *stream, uint32_t K2, uint64_t both_budget,
-                      JumpLevel2 *l2) {
+                      JumpLevel2 *l2, uint64_t *words) {
     bool retry = false;
-    int rc = build_jump(ix, cfg, K, table_budget, peak_budget, tab, tab_bytes, buckets, keys, why, stream, K2, both_budget, l2, &retry);
+    uint64_t words1 = 0;
+    if (!words) words = &words1;
+    int rc = build_jump(ix, cfg, K, table_budget, peak_budget, tab, tab_bytes, buckets, keys, why, stream, K2, both_budget, l2, &retry, words);
     if (!retry) return rc;
-    rc = build_jump(ix, cfg, K, table_budget, peak_budget, tab, tab_bytes, buckets, keys, why, stream, 0, 0, nullptr, &retry);
+    rc = build_jump(ix, cfg, K, table_budget, peak_budget, tab, tab_bytes, buckets, keys, why, stream, 0, 0, nullptr, &retry, words);
     l2->why = "its build scratch exceeds what the HBM budget leaves";
     return rc;
 }

@@ -183,13 +183,14 @@ __global__ __launch_bounds__(512, STATS ? 2 : 4) void k_find_range_runs(const De
             uint64_t pend_e = 0;
             ByteCursor rd{reinterpret_cast<const uint4 *>(seqs), ~uint64_t(0), make_uint4(0, 0, 0, 0)};
             // JUMP (rbg_jump.h): a staged read of at least jump_k symbols looks its last jump_k up in the table of the K-mers that occur -- one
-            // probe in place of the ftab entry and the first (jump_k - ftab_k) / 8 steps; a key that is absent takes the ftab path below.
+            // probe in place of the ftab entry and the first (jump_k - ftab_k) / 8 steps; a key that is absent ends the read where its level is complete, and takes the ftab path below where it is not.
             // The probe is the wave's (jump_probe_wave): every lane enters it, `probing` is a predicate.
             bool jumped = false;
             if constexpr (STAGED && sizeof(P) == 4) {
                 if (ix.jump) {                                     // (wave-uniform)
                     // Level 2 (ix.jump2_k): a lane that hit level 1 and has jump2_k symbols left looks {those symbols, its lo} up in the second
-                    // table; a hit replaces the state once more, an absent key leaves level 1's and the steps go on from there.  One loop over
+                    // table; a hit replaces the state once more; an absent key ends the read where level 2 is complete (below), and where it is not leaves level
+                    // 1's state and the steps go on from there.  One loop over
                     // the levels: the probe is inlined once.
                     const uint32_t nlev = ix.jump2_k ? 2u : 1u;
                     bool hit = valid;                              // of the level before
@@ -213,6 +214,15 @@ __global__ __launch_bounds__(512, STATS ? 2 : 4) void k_find_range_runs(const De
                             if (STATS) st[kStSymbols] += K;
                         }
                         if (STATS) st[kStFtab] += nbk;               // (the ftab slot counts probed buckets too: 64 bytes each, of either level)
+                        // A COMPLETE level (rbg_jump.h jump_complete_mask) holds every word that occurs, so a key it lacks ends the read here: its
+                        // range is empty, the ftab path and the steps would only walk to the {1, 0, 0} below.  The argument needs the key to be one
+                        // the enumeration could have reached, and it is: a wave is staged only if stage_read found none but major bytes in every
+                        // read (stage_tables keeps one byte per major code and refuses every other), and k_jump.hip extends every word by exactly
+                        // those four.  A predicate, not a way out of the loop: the next level's `hit` is false for this lane, the ballots of the
+                        // probe and of the steps stay the wave's.  The instrumented kernel keeps walking: its sums describe the walk without this end.
+                        if constexpr (!STATS) {
+                            if (probing && !hit && jump_absent_ends(ix.jump_complete, lev)) { alive = false; p = beg; }
+                        }
                     }
                 }
             }

@@ -324,6 +324,9 @@ struct DevIndex {
     // behind the first in the same allocation, at `jump` + jump_buckets x 64 bytes; exists only where `jump` does.  jump2_k = 0: none.
     uint32_t jump2_k;
     uint64_t jump2_buckets;
+    // the levels that are COMPLETE (rbg_jump.h jump_complete_mask: kJumpComplete1 | kJumpComplete2): every word that occurs is in the table, so
+    // a key it lacks ends the read at the probe.  0: an absent key takes the ftab path.  (It takes the four bytes that padded tmk_shift.)
+    uint32_t jump_complete;
     // the marker table keyed by TEXT position (rbg_set_text_markers / <prefix>.midx; k_loc_markers.hip): the fields of the SA-row table above a second
     // time -- inclusive, ascending, disjoint runs of text positions in [0, n), built by the same code under the same gates (capi/upload_runs.ipp).
     // All nullptr / 0 until a table is set.  Kept at the end: the kernels that never read it find every other field where it was.
@@ -756,15 +759,17 @@ size_t ftab_build_scratch_bytes(uint64_t words, uint32_t k);  // device scratch 
 // K2 != 0 (with l2): after the first table, a second one (level 2, rbg_jump.h) of the words of K + K2 symbols, under the same rules with
 // `both_budget` for its bytes and what `peak_budget` leaves after the first table for its build; l2->tab = nullptr with l2->why set when
 // it was skipped -- the first table stands all the same.  l2->tab lies in *tab's allocation, l2->bytes behind its *tab_bytes: the caller owns ONE array.
+// *words (l2->words) = the words of the level's final enumeration, beside *keys (l2->keys) = those inserted once the table stands: what
+// rbg_jump.h jump_complete_mask judges a level by.
 struct JumpLevel2 {
     void *tab = nullptr;
-    uint64_t bytes = 0, buckets = 0, keys = 0;
+    uint64_t bytes = 0, buckets = 0, keys = 0, words = 0;
     double build_ms = 0.0;
     const char *why = nullptr;
 };
 int launch_build_jump(const DevIndex &ix, const LaunchCfg &cfg, uint32_t K, uint64_t table_budget, uint64_t peak_budget, void **tab,
                       uint64_t *tab_bytes, uint64_t *buckets, uint64_t *keys, const char **why, void *stream, uint32_t K2 = 0,
-                      uint64_t both_budget = 0, JumpLevel2 *l2 = nullptr);
+                      uint64_t both_budget = 0, JumpLevel2 *l2 = nullptr, uint64_t *words = nullptr);
 int launch_sample_reads(const uint8_t *text, uint64_t unit, uint64_t H, uint64_t L, uint64_t m, uint64_t seed, uint64_t first,
                         uint64_t N, uint32_t sub_ppm, uint8_t *seqs, uint64_t *off, uint64_t *start_out /*nullable*/, void *stream);
 int launch_sample_reads_pg(const uint8_t *base, const uint64_t *sites, const uint8_t *alt, const uint8_t *G, uint64_t S, const uint32_t *site_dir, uint32_t site_dir_shift,

@@ -3,7 +3,7 @@
 // ftab_k symbols, this table only the words that occur, so K can be four or five times longer.  A read of at least K symbols
 // looks up its last K in one probe (usually one 64-byte bucket) instead of the ftab entry and (K - ftab_k) / 8 bucket records;
 // a key that is absent -- the read has a symbol in its last K that the text does not -- costs one probe and the read takes the
-// ftab path.  A probe reads whole buckets: the search kernel fetches a bucket as ONE 64-byte request of the owner's quad of lanes (k_runs.hip
+// ftab path, or ends there when the table is complete (below).  A probe reads whole buckets: the search kernel fetches a bucket as ONE 64-byte request of the owner's quad of lanes (k_runs.hip
 // jump_probe_wave) and jump_bucket below settles both of its slots from those sixteen words.  Built at load by the library's own kernels (k_jump.hip), result-neutral by construction.
 //
 // Key: the K symbols as 2-bit major codes in CONSUMPTION order (symbol t of the key = the read's symbol m - 1 - t at bits
@@ -156,5 +156,26 @@ RBG_JUMP_HD JumpKey jump2_key_from_text(const uint8_t *codes, uint32_t K2, uint3
 
 // buckets of a table holding `keys` keys at a load of at most one half (two slots per bucket), at least one
 inline uint64_t jump_buckets_for(uint64_t keys) { return keys ? keys : 1; }
+
+// ---- complete levels: an absent key ends the read ---------------------------------------------------------------------------------
+// A level is COMPLETE when its build ran to the end (the table stands) and every word of its final enumeration level was inserted.  The
+// enumeration (k_jump.hip) holds every word over the major symbols whose range is non-empty, so a complete table lacks a key only when
+// the range after that key's symbols is empty: the search may end the read at the probe.  A word the insert skips (a
+// toehold the slot cannot express, a range the search found empty), a table that was skipped or declined, a build that stopped early:
+// each leaves its level incomplete, and an absent key goes on to the ftab path as before.  The levels are judged apart: a key of level 2
+// is probed only after a hit of level 1, and its table is filled from the enumeration alone, whatever level 1 inserted.
+constexpr uint32_t kJumpComplete1 = 1u, kJumpComplete2 = 2u;   // DevIndex::jump_complete, rbg_jump_info_t::complete
+struct JumpBuilt {
+    bool stands;                 // the build ran to the end and its table is the one the index probes
+    uint64_t words, inserted;    // words of the final enumeration level; those k_jump_insert counted
+};
+RBG_JUMP_HD bool jump_level_complete(const JumpBuilt &b) { return b.stands && b.words != 0 && b.inserted == b.words; }
+// `absent_ends` = the switch (RBG_JUMP_ABSENT_ENDS, default on): off, no level counts as complete.  Level 2 exists only where level 1 does.
+RBG_JUMP_HD uint32_t jump_complete_mask(const JumpBuilt &l1, const JumpBuilt &l2, bool absent_ends) {
+    if (!absent_ends || !l1.stands) return 0u;
+    return (jump_level_complete(l1) ? kJumpComplete1 : 0u) | (jump_level_complete(l2) ? kJumpComplete2 : 0u);
+}
+// does an absent key of level `lev` (0, 1) end the read?
+RBG_JUMP_HD bool jump_absent_ends(uint32_t mask, uint32_t lev) { return ((mask >> lev) & 1u) != 0; }
 
 }  // namespace rbg
