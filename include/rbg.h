@@ -590,6 +590,40 @@ int rbg_text_runs_fill_dev(const uint8_t *d_text, const void *d_sa, uint64_t n, 
  * rbg_convert_text: the cache file instead of a handle, through rbg_convert_runs_markers (docs_text nullable, as there). */
 int rbg_build_from_text(const uint8_t *text, uint64_t n, int flags, int device, rbg_index **out);
 int rbg_convert_text(const uint8_t *text, uint64_t n, const char *docs_text /* nullable */, int flags, int device, const char *out_path);
+/* ---- the marker array from variant sites, over the suffix array (mk_build.hip) --------------------------------------------------------
+ * A SITE RECORD is (pos, first, val): pos = the text position of a variant site in one haplotype copy; first = the first text position of its window,
+ * max(start of pos's document, pos - w + 1); val = the MarkerT (allele index in bits 60-63, contig index in bits 48-59, 0-based reference position in the
+ * low 48 bits).  The S records are strictly ascending in pos; first does not descend, first <= pos < n and pos - first < w (1 <= w <= 64).
+ *   - the row i with p = SA[i] carries the values of every record with first <= p <= pos: a contiguous stretch of the list, at most w long;
+ *   - within a row the values are ascending; a row with no record is in no run;
+ *   - a covered row continues the run of the covered row before it only if the two rows are adjacent (i == prev + 1), both carry exactly one value, and it is
+ *     the same value; otherwise it starts a run; a run's values are those of its first row.
+ * The output is the argument set of rbg_set_markers: inclusive run_start[nruns], run_end[nruns], mk_off[nruns + 1], mk_vals[nvals].
+ * Both calls take no handle and run on the current device.  d_sa: n entries of pos_bytes (rbg_suffix_array_dev's); d_pos, d_first, d_val: S u64 each (may be
+ * NULL when S == 0); d_tmp: rbg_marker_runs_tmp_bytes(n, S, w, pos_bytes) bytes, 256-byte aligned -- 256 + n / 8 + n / 32 + 32 * min(n, S * w) bytes and
+ * hipCUB's own, no array of n positions (0 = arguments no plan takes).  Nothing outside d_tmp and the outputs is written.
+ * rbg_marker_runs_plan_dev: checks the rule about the records on the device, finds the covered rows and numbers the runs in d_tmp; *nruns, *nvals = the
+ * sizes of the output.  It reads d_val, because whether two rows share a run depends on their values.  Waits for `stream`.
+ * rbg_marker_runs_fill_dev, with the same arguments and d_tmp and the plan's counts: writes the four arrays.  It reads the plan's header back from d_tmp
+ * (one wait for `stream`), then queues its kernel and returns.  d_sa, d_pos and d_first are checked but not read again.
+ * RBG_EARG, nothing written to the outputs: n == 0, w outside 1..64, S > n, a NULL or misaligned pointer (d_tmp to 256, d_sa to pos_bytes, the rest to 8),
+ * too little scratch, a pos_bytes that is not 4 or 8 or does not hold n, records that break the rule (plan), a d_tmp that does not hold the plan of these
+ * n, S, w, pos_bytes, or counts that are not that plan's (fill).  S == 0 is RBG_OK with *nruns = *nvals = 0, and the fill then writes mk_off[0] = 0 only. */
+size_t rbg_marker_runs_tmp_bytes(uint64_t n, uint64_t S, uint32_t w, uint32_t pos_bytes);
+int rbg_marker_runs_plan_dev(const void *d_sa, uint64_t n, uint32_t pos_bytes, const uint64_t *d_pos, const uint64_t *d_first, const uint64_t *d_val, uint64_t S,
+                             uint32_t w, void *d_tmp, size_t tmp_bytes, uint64_t *nruns, uint64_t *nvals, void *stream);
+int rbg_marker_runs_fill_dev(const void *d_sa, uint64_t n, uint32_t pos_bytes, const uint64_t *d_pos, const uint64_t *d_first, const uint64_t *d_val, uint64_t S,
+                             uint32_t w, const void *d_tmp, size_t tmp_bytes, uint64_t nruns, uint64_t nvals, uint64_t *d_run_start, uint64_t *d_run_end,
+                             uint64_t *d_mk_off, uint64_t *d_mk_vals, void *stream);
+/* rbg_build_from_text / rbg_convert_text with the marker pass run while the suffix array is still on the device: the records (host memory) are uploaded, the
+ * two calls above run in the build's own scratch, and the arrays go on through rbg_set_markers / rbg_convert_runs_markers.  The scratch of the pass and 24
+ * bytes per record are part of the bytes compared with hipMemGetInfo before anything is allocated; the marker arrays (16 bytes per run, 8 per value) are
+ * checked once the plan has counted them.  RBG_EARG also for records that break the rule or w outside 1..64.  With S == 0 the calls are rbg_build_from_text
+ * / rbg_convert_text exactly (pos, first, val and w are not looked at). */
+int rbg_build_from_text_markers(const uint8_t *text, uint64_t n, const uint64_t *pos, const uint64_t *first, const uint64_t *val, uint64_t S, uint32_t w, int flags,
+                                int device, rbg_index **out);
+int rbg_convert_text_markers(const uint8_t *text, uint64_t n, const uint64_t *pos, const uint64_t *first, const uint64_t *val, uint64_t S, uint32_t w,
+                             const char *docs_text /* nullable */, int flags, int device, const char *out_path);
 /* ---- rb_markers' report (what the tool prints), made on the device --------------------------------------------------------------
  * Everything rb_markers does between get_markers_greedy_seeding / get_markers_lmems and its output (rb_markers.cpp:228-315, :365-382,
  * :396-413, :429-519), for a batch of RAW reads: both strands (sequence 2i = read i through seq_ntoa_table -- ACGT of either case, N/n -> 'A',

@@ -268,6 +268,11 @@ _PROTOS = [
     ("rbg_text_runs_fill_dev", C.c_int, [VP, VP, U64, C.c_uint32, VP, C.c_size_t, U64, VP, VP, VP, VP, VP]),
     ("rbg_build_from_text", C.c_int, [VP, U64, C.c_int, C.c_int, C.POINTER(VP)]),
     ("rbg_convert_text", C.c_int, [VP, U64, C.c_char_p, C.c_int, C.c_int, C.c_char_p]),
+    ("rbg_marker_runs_tmp_bytes", C.c_size_t, [U64, U64, C.c_uint32, C.c_uint32]),
+    ("rbg_marker_runs_plan_dev", C.c_int, [VP, U64, C.c_uint32, VP, VP, VP, U64, C.c_uint32, VP, C.c_size_t, C.POINTER(U64), C.POINTER(U64), VP]),
+    ("rbg_marker_runs_fill_dev", C.c_int, [VP, U64, C.c_uint32, VP, VP, VP, U64, C.c_uint32, VP, C.c_size_t, U64, U64, VP, VP, VP, VP, VP]),
+    ("rbg_build_from_text_markers", C.c_int, [VP, U64, VP, VP, VP, U64, C.c_uint32, C.c_int, C.c_int, C.POINTER(VP)]),
+    ("rbg_convert_text_markers", C.c_int, [VP, U64, VP, VP, VP, U64, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_char_p]),
     ("rbg_set_default_option", C.c_int, [C.c_int, C.c_int64]),
     ("rbg_get_default_option", C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
 ]
@@ -432,6 +437,55 @@ def text_runs(text, sa):
     return dict(heads=heads.cpu().numpy().copy(), lens=u(lens), ssa=u(ssa), esa=u(esa), n=n, r=r)
 
 
+def marker_runs(sa, pos, first, val, w, pos_bytes=0):
+    """rbg_marker_runs_plan_dev + rbg_marker_runs_fill_dev over torch tensors: sa int32[n] or int64[n] on its device (capi.suffix_array's), the site records
+    pos, first, val int64[S] on the same device, 1 <= w <= 64 -> numpy (run_start, run_end, mk_off, mk_vals), uint64: the arguments of set_markers.
+    pos_bytes, when given, must be the width of sa.  Only the marker arrays leave the device"""
+    import torch
+    n, S = int(sa.numel()), int(pos.numel())
+    pb = sa.element_size()
+    assert sa.is_contiguous() and pb in (4, 8) and pos_bytes in (0, pb)
+    for t in (pos, first, val):
+        assert t.dtype == torch.int64 and t.is_contiguous() and int(t.numel()) == S and t.device == sa.device
+    L = lib()
+    with torch.cuda.device(sa.device):
+        nb = L.rbg_marker_runs_tmp_bytes(n, S, w, pb)
+        tmp = torch.empty(nb + 256, dtype=torch.uint8, device=sa.device)
+        at = (-tmp.data_ptr()) % 256
+        st = torch.cuda.current_stream().cuda_stream
+        ptrs = [t.data_ptr() if S else None for t in (pos, first, val)]
+        nruns, nvals = U64(), U64()
+        _check(L.rbg_marker_runs_plan_dev(sa.data_ptr(), n, pb, *ptrs, S, w, tmp.data_ptr() + at, nb, C.byref(nruns), C.byref(nvals), st),
+               "rbg_marker_runs_plan_dev")
+        r, v = int(nruns.value), int(nvals.value)
+        run_start, run_end = (torch.empty(max(r, 1), dtype=torch.int64, device=sa.device) for _ in range(2))
+        mk_off = torch.empty(r + 1, dtype=torch.int64, device=sa.device)
+        mk_vals = torch.empty(max(v, 1), dtype=torch.int64, device=sa.device)
+        rc = L.rbg_marker_runs_fill_dev(sa.data_ptr(), n, pb, *ptrs, S, w, tmp.data_ptr() + at, nb, r, v, run_start.data_ptr(), run_end.data_ptr(),
+                                        mk_off.data_ptr(), mk_vals.data_ptr(), st)
+        torch.cuda.synchronize()
+    _check(rc, "rbg_marker_runs_fill_dev")
+    u = lambda t, k: t[:k].cpu().numpy().view(np.uint64).copy()
+    return u(run_start, r), u(run_end, r), u(mk_off, r + 1), u(mk_vals, v)
+
+
+def _site_records(markers):
+    """(pos, first, val, w) -> three contiguous uint64 arrays of one length, and w"""
+    pos, first, val, w = markers
+    a = [np.ascontiguousarray(x, dtype=np.uint64) for x in (pos, first, val)]
+    if not (len(a[0]) == len(a[1]) == len(a[2])):
+        raise ValueError("pos, first and val differ in length")
+    return a, int(w)
+
+
+def convert_text_markers(text, markers, out_path, docs_text=None, sa=True, device=0):
+    """rbg_convert_text_markers: convert_text with the marker array of the site records markers = (pos, first, val, w) stored in the cache file"""
+    t = _text_bytes(text)
+    a, w = _site_records(markers)
+    _check(lib().rbg_convert_text_markers(_p(t), len(t), _p(a[0]), _p(a[1]), _p(a[2]), len(a[0]), w, docs_text.encode() if docs_text else None,
+                                          int(LoadRbwtFlag.SA) if sa else 0, device, os.fsencode(out_path)), "rbg_convert_text_markers")
+
+
 def set_default_option(opt, value):
     _check(lib().rbg_set_default_option(opt, value), "rbg_set_default_option")
 
@@ -551,12 +605,18 @@ class RowBowt:
         return cls(h)
 
     @classmethod
-    def from_text(cls, text, sa=True, device=0):
+    def from_text(cls, text, sa=True, device=0, markers=None):
         """rbg_build_from_text: the index of a text in host memory (bytes or a uint8 array; its last byte is its unique smallest), built on the device:
-        suffix array, runs, samples; sa=False keeps no toehold samples"""
+        suffix array, runs, samples; sa=False keeps no toehold samples.  markers = (pos, first, val, w), the site records of include/rbg.h: the marker
+        array is built from them while the suffix array is on the device and set on the index (rbg_build_from_text_markers)"""
         t = _text_bytes(text)
         h = VP()
-        _check(lib().rbg_build_from_text(_p(t), len(t), int(LoadRbwtFlag.SA) if sa else 0, device, C.byref(h)), "rbg_build_from_text")
+        if markers is None:
+            _check(lib().rbg_build_from_text(_p(t), len(t), int(LoadRbwtFlag.SA) if sa else 0, device, C.byref(h)), "rbg_build_from_text")
+            return cls(h)
+        a, w = _site_records(markers)
+        _check(lib().rbg_build_from_text_markers(_p(t), len(t), _p(a[0]), _p(a[1]), _p(a[2]), len(a[0]), w, int(LoadRbwtFlag.SA) if sa else 0, device,
+                                                 C.byref(h)), "rbg_build_from_text_markers")
         return cls(h)
 
     @classmethod

@@ -1,6 +1,7 @@
 // rb_build -- the reference's index builder CLI (reference src/rb_build.cpp) for this engine:
 //   rb_build [-o out_prefix] [-s] [-m] [-l] [-f [-k K]] [-a] <input_prefix>
 //   rb_build --fasta <ref.fa[.gz]> -o out_prefix [-s] [-l] [-f [-k K]] [--gpu n]
+//   rb_build --fasta <ref.fa[.gz]> --vcf <calls.vcf[.gz]> [--samples a,b,...] [--ma-wsize w] -m -o out_prefix [-s] [-l] [-f [-k K]] [--gpu n]
 // reads <input_prefix>.bwt (+ .ssa/.esa with -s, + .docs with -l) exactly as the reference's
 // constructors do (rle_string.hpp:44-97, toehold_sa.hpp:27-35,133-155) and writes the engine's
 // native cache <out_prefix>.rbgpu, which rb_align / rb_markers / rbg_load pick up when no .rbwt is
@@ -13,7 +14,11 @@
 //   -x   fbb_string indexes are not supported.
 //   --fasta  the reference has no builder from a sequence file (its inputs are pfbwt-f's).  Here the text of the FASTA (rbg_fasta_text.hpp: documents joined
 //        by '#', a final 0x01) goes to the device, which makes the suffix array, the runs and the samples (rbg_convert_text); -l writes <out>.docs and
-//        stores it in the cache; -m is refused: a FASTA carries no markers.
+//        stores it in the cache; -m alone is refused: a FASTA carries no markers.
+//   --vcf  with --fasta and -m: the documents are the reference's contigs and every selected sample's haplotypes (rbg_vcf.hpp: phased single-base variants
+//        applied; indels, symbolic alleles, unknown contigs and duplicate positions are skipped and counted on stderr), and the marker array is built on the
+//        device from one site record per document and site with windows of --ma-wsize (default 10) bases (rbg_convert_text_markers).  The cache has no field
+//        for the window: it is stored as rbg_convert_runs_markers stores it.  Not built: indels, the text-keyed .midx of rb_locs, a text beyond the device.
 //   The sdsl-serialised .rbwt/.tsa are not written (this engine does not need them; an existing
 //   reference-built index converts with `rb_build --from-index <prefix>`).
 #include <getopt.h>
@@ -23,14 +28,18 @@
 #include <fstream>
 #include <iostream>
 #include <string>
+#include <vector>
 
 #include "../../include/rbg.h"
 #include "rbg_fasta_text.hpp"
+#include "rbg_vcf.hpp"
 
 namespace {
 
 struct Args {  // RowBowtConstructArgs, rowbowt_io.hpp:30-47
-    std::string prefix, inpre, fasta;
+    std::string prefix, inpre, fasta, vcf, samples;
+    int has_samples = 0, has_wsize = 0;
+    uint64_t ma_wsize = 10;
     int ma = 0, tsa = 0, dl = 0, ft = 0, ft_only = 0, fbb = 0, from_index = 0, device = 0;
     uint64_t k = 10;
 };
@@ -45,7 +54,12 @@ void print_help() {  // rb_build.cpp:11-20
     fprintf(stderr, "    --ft/-f [-k <int>]               construct offset table <out>.ftab\n");
     fprintf(stderr, "    --ftab-only/-a                   only construct the offset table from an existing index\n");
     fprintf(stderr, "    --from-index                     convert <pre>.rbwt/.tsa/.mab/.docs instead of raw inputs\n");
-    fprintf(stderr, "    --fasta <ref.fa[.gz]>            build from a FASTA on the GPU (needs -o; no <index_prefix>; not with -m)\n");
+    fprintf(stderr, "    --fasta <ref.fa[.gz]>            build from a FASTA on the GPU (needs -o; no <index_prefix>; -m only with --vcf)\n");
+    fprintf(stderr, "    --vcf <calls.vcf[.gz]>           with --fasta and -m: index the reference and the samples' haplotypes, and build the marker\n");
+    fprintf(stderr, "                                     array on the GPU (phased single-base variants; indels, symbolic alleles, unknown contigs and\n");
+    fprintf(stderr, "                                     duplicate positions are skipped and counted; no .midx for rb_locs; the text must fit the device)\n");
+    fprintf(stderr, "    --samples <a,b,...>              the samples of the VCF to take (default: all), in VCF column order\n");
+    fprintf(stderr, "    --ma-wsize <w>                   marker window, 1..64 bases (default 10)\n");
     fprintf(stderr, "    --gpu <n>                        HIP device ordinal for -f/-a/--fasta (default 0)\n");
     fprintf(stderr, "    <input_prefix>                   index prefix\n");
 }
@@ -62,6 +76,9 @@ Args parse_args(int argc, char **argv) {  // rb_build.cpp:22-95
                                            {"from-index", no_argument, &args.from_index, 1},
                                            {"gpu", required_argument, 0, 'G'},
                                            {"fasta", required_argument, 0, 'F'},
+                                           {"vcf", required_argument, 0, 'V'},
+                                           {"samples", required_argument, 0, 'S'},
+                                           {"ma-wsize", required_argument, 0, 'W'},
                                            {0, 0, 0, 0}};
     int c, long_index = 0;
     while ((c = getopt_long(argc, argv, "xo:k:lfsmha", long_options, &long_index)) != -1) {
@@ -77,10 +94,21 @@ Args parse_args(int argc, char **argv) {  // rb_build.cpp:22-95
             case 'k': args.k = std::strtoull(optarg, nullptr, 10); break;
             case 'G': args.device = atoi(optarg); break;
             case 'F': args.fasta = optarg; break;
+            case 'V': args.vcf = optarg; break;
+            case 'S': args.samples = optarg; args.has_samples = 1; break;
+            case 'W': args.ma_wsize = std::strtoull(optarg, nullptr, 10); args.has_wsize = 1; break;
             case 'h': print_help(); exit(0);
             case '?': break;  // the reference ignores unknown options (rb_build.cpp:64-65)
             default: print_help(); exit(1);
         }
+    }
+    if (!args.vcf.empty() && (args.fasta.empty() || !args.ma)) {
+        fprintf(stderr, "rb_build: --vcf needs --fasta and -m (it is the source of the marker array)\n");
+        exit(1);
+    }
+    if (args.vcf.empty() && (args.has_samples || args.has_wsize)) {
+        fprintf(stderr, "rb_build: --samples and --ma-wsize belong to --vcf\n");
+        exit(1);
     }
     if (!args.fasta.empty()) {  // the input is the FASTA: no <index_prefix>, and the outputs need a name
         if (args.prefix.empty()) {
@@ -121,7 +149,52 @@ void write_ftab(const Args &args) {
     rbg_free(ix);
 }
 
+// --fasta --vcf -m: the haplotype documents and their site records, the index and its marker array in one device build
+int build_from_vcf(const Args &args) {
+    if (args.ma_wsize < 1 || args.ma_wsize > 64) {
+        std::cerr << "rb_build: --ma-wsize must be 1..64" << std::endl;
+        return 1;
+    }
+    std::vector<std::string> samples;
+    for (size_t a = 0; args.has_samples && a <= args.samples.size();) {
+        size_t b = args.samples.find(',', a);
+        if (b == std::string::npos) b = args.samples.size();
+        samples.push_back(args.samples.substr(a, b - a));
+        a = b + 1;
+    }
+    rbg_cli::VcfText v;
+    std::string why;
+    int rc = rbg_cli::vcf_text(args.fasta.c_str(), args.vcf.c_str(), args.has_samples ? &samples : nullptr, static_cast<uint32_t>(args.ma_wsize), v, &why);
+    if (rc) {
+        std::cerr << "rb_build: " << why << ": " << rbg_strerror(rc) << std::endl;
+        return 1;
+    }
+    std::cerr << "skipped sites: " << v.skipped[rbg_cli::VCF_SKIP_INDEL] << " indel or MNV, " << v.skipped[rbg_cli::VCF_SKIP_SYMBOLIC] << " symbolic or non-ACGT, "
+              << v.skipped[rbg_cli::VCF_SKIP_CONTIG] << " on a contig the FASTA lacks, " << v.skipped[rbg_cli::VCF_SKIP_DUPLICATE] << " duplicate position" << std::endl;
+    for (const std::string &name : v.no_haplotypes)
+        std::cerr << "rb_build: warning: sample " << name << " has no accepted site: its ploidy is unknown and it gets no documents" << std::endl;
+    if (v.pos.empty()) {      // (-m was asked for: an index without a marker array is not what the caller wants)
+        std::cerr << "rb_build: no site of " << args.vcf << " was accepted: there would be no marker array" << std::endl;
+        return 1;
+    }
+    const std::string out = args.prefix + ".rbgpu", docs = v.t.docs_text();
+    std::cerr << "constructing from " << args.fasta << " and " << args.vcf << ": " << v.t.names.size() << " documents, " << v.t.text.size() << " symbols, " << v.sites
+              << " sites, " << v.pos.size() << " site records, windows of " << args.ma_wsize << std::endl;
+    rc = rbg_convert_text_markers(reinterpret_cast<const uint8_t *>(v.t.text.data()), v.t.text.size(), v.pos.data(), v.first.data(), v.val.data(), v.pos.size(),
+                                  static_cast<uint32_t>(args.ma_wsize), args.dl ? docs.c_str() : nullptr, args.tsa ? RBG_LOAD_SA : RBG_LOAD_NONE, args.device,
+                                  out.c_str());
+    if (rc) die("building " + out, rc);
+    if (args.dl) {
+        std::ofstream ofs(args.prefix + ".docs", std::ios::binary);
+        ofs << docs;
+        if (!ofs.good()) die("writing " + args.prefix + ".docs", RBG_EIO);
+    }
+    if (args.ft) write_ftab(args);
+    return 0;
+}
+
 int build_from_fasta(const Args &args) {
+    if (!args.vcf.empty()) return build_from_vcf(args);
     if (args.ma) {
         std::cerr << "rb_build: -m cannot be combined with --fasta: a FASTA carries no markers" << std::endl;
         return 1;

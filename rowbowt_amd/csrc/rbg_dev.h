@@ -609,6 +609,14 @@ size_t text_runs_tmp_bytes(uint64_t n, uint32_t pos_bytes);
 int text_runs_plan(const uint8_t *text, const void *sa, uint64_t n, uint32_t pos_bytes, void *tmp, size_t tmp_bytes, uint64_t *R, void *stream);
 int text_runs_fill(const uint8_t *text, const void *sa, uint64_t n, uint32_t pos_bytes, const void *tmp, size_t tmp_bytes, uint64_t R, uint8_t *heads,
                    uint64_t *lens, uint64_t *ssa, uint64_t *esa, void *stream);
+// the marker array from site records and the suffix array (mk_build.hip; rbg_marker_runs_*_dev).  Each returns 0, 1 for what the caller did wrong (arguments
+// no plan takes, records that break their rule, a scratch that does not hold the plan of these arguments and counts), 2 for a HIP error.  The plan waits for
+// the stream; the fill reads the plan's header back (one wait), then queues its kernels.  marker_runs_tmp_bytes: 0 for arguments no plan takes.
+size_t marker_runs_tmp_bytes(uint64_t n, uint64_t S, uint32_t w);
+int marker_runs_plan(const void *sa, uint64_t n, uint32_t pos_bytes, const uint64_t *pos, const uint64_t *first, const uint64_t *val, uint64_t S, uint32_t w,
+                     void *tmp, size_t tmp_bytes, uint64_t *nruns, uint64_t *nvals, void *stream);
+int marker_runs_fill(uint64_t n, uint32_t pos_bytes, const uint64_t *val, uint64_t S, uint32_t w, const void *tmp, size_t tmp_bytes, uint64_t nruns,
+                     uint64_t nvals, uint64_t *run_start, uint64_t *run_end, uint64_t *mk_off, uint64_t *mk_vals, void *stream);
 // run-indexed layout from run lists already on the device (k_build.hip): the tables' directories, 8-byte samples packed to 6
 int launch_run_dirs(uint32_t pos_bytes, const void *ent, const uint64_t *first, const uint64_t *nruns, const uint64_t *doff, const uint32_t *dshift,
                     uint32_t T, uint64_t total, uint32_t *dir, void *stream);

@@ -741,4 +741,17 @@ RowBowt<StringT> build_from_text(const std::string &text, LoadRbwtFlag flag = Lo
     return RowBowt<StringT>(ix);
 }
 
+// The same with the marker array made from site records (rbg_build_from_text_markers; include/rbg.h states the rule): pos, first and val of one length,
+// windows of w bases.  No records: the build above.
+template <typename StringT = rle_string_t>
+RowBowt<StringT> build_from_text(const std::string &text, const std::vector<uint64_t> &pos, const std::vector<uint64_t> &first, const std::vector<uint64_t> &val,
+                                 uint32_t w, LoadRbwtFlag flag = LoadRbwtFlag::SA, int device = 0) {
+    if (pos.size() != first.size() || pos.size() != val.size()) detail::check(RBG_EARG, "build_from_text");
+    rbg_index *ix = nullptr;
+    detail::check(rbg_build_from_text_markers(reinterpret_cast<const uint8_t *>(text.data()), text.size(), pos.data(), first.data(), val.data(), pos.size(), w,
+                                              static_cast<int>(flag), device, &ix),
+                  "build_from_text");
+    return RowBowt<StringT>(ix);
+}
+
 }  // namespace rbwt
